@@ -35,16 +35,9 @@ import subprocess
 import sys
 import time
 
-# Every extractor handle runs its blur on a side stream and this script adds matcher, copy and collective streams of its
-# own (a dozen over all legs); the ROCm runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES hardware queues
-# (default 4), and two streams that land on one queue serialise -- measured here: the PCIe-inclusive leg drops from 177 k
-# to 95-118 k frames/s when a copy stream shares a queue with a kernel stream (4 and 8 queues), 16 keep them apart
-# ("streams").  Must be set before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.distributed as dist  # noqa: E402
+import numpy as np
+import torch
+import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -437,7 +430,13 @@ def main():
                     "the maximum count of a probe step rounded up to 64: 1024 of 1088 slots at 1000 features)")
     ap.add_argument("--rccl-channels", type=int, default=None, help="N > 1: NCCL_MAX_NCHANNELS for RCCL (its copy kernels take compute "
                     "units from a VALU-bound step; fewer channels = fewer of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "computed on rank 0 as DIR/<name>.npy (see dump_outputs); extract_match path only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.path != "extract_match":
+        ap.error("--dump-outputs covers the extract_match path only")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(respawn(args))
@@ -554,6 +553,8 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed = timed(args.steps)
+    if args.dump_outputs and rank == 0:   # before anything below runs the step again
+        dump_outputs(args.dump_outputs, eng, (counter[0] - 1) % len(eng.outs))
     exch = None
     if gather:  # retire the work handles of the last gathers (already complete: fence() synchronised the device)
         for k in range(len(eng.outs)):
@@ -663,6 +664,49 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
     os.dup2(2, 1)   # nothing may follow the JSON line on stdout (buffers flushed at exit by native libraries)
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
+DUMP_FRAMES = 256       # frames of the keypoint / descriptor / match sample
+
+
+def dump_outputs(path, eng, out_set, seed=2026):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy, so that two builds run with the same
+    arguments (hence the same input frames) can be compared array by array.
+      keypoint_counts [B] float64, match_counts [B] float64   every frame of the step
+      frames [K] float64                                       a fixed seeded sample of K frame indices (K <= DUMP_FRAMES)
+      keypoints [K, cap, 7] float32                            x, y, size, angle, response, octave, class_id of the sample
+      descriptors [K, cap, 32] float32                         descriptor bytes
+      matches [K, cap] float32                                 index into the previous frame's keypoints, -1 = none
+    Slots at or past a frame's count are not part of the output: zero (-1 for matches)."""
+    kps, desc, n = eng.outs[out_set]
+    match = getattr(eng, "match", False)
+    B, cap = kps.shape[0], kps.shape[1]
+    out = {"keypoint_counts": n.cpu().numpy().astype(np.float64)}
+    if match:
+        out["match_counts"] = eng.d_nm.cpu().numpy().astype(np.float64)
+    per_frame = cap * (7 + 32 + int(match)) * 4 + 8
+    k = max(1, min(B, DUMP_FRAMES, (DUMP_BYTES - sum(a.nbytes for a in out.values()) - 4096) // per_frame))
+    frames = np.sort(np.random.default_rng(seed).choice(B, k, replace=False))
+    out["frames"] = frames.astype(np.float64)
+    idx = torch.from_numpy(frames).to(kps.device)
+    valid = (torch.arange(cap, device=kps.device)[None, :] < n[idx][:, None]).cpu().numpy()
+    raw = kps[idx].cpu().numpy()
+    kp = np.zeros(raw.shape, np.float32)
+    kp[..., :5] = raw[..., :5].view(np.float32)
+    kp[..., 5:] = raw[..., 5:]
+    kp[~valid] = 0
+    d = desc[idx].cpu().numpy().astype(np.float32)
+    d[~valid] = 0
+    out["keypoints"], out["descriptors"] = kp, d
+    if match:
+        m = eng.d_match[idx].cpu().numpy().astype(np.float32)
+        m[~valid] = -1
+        out["matches"] = m
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def gathered_check(eng, gather, d_gray, out_set, nf, rank, world):
@@ -1034,7 +1078,7 @@ def extras(args, eng, d_gray, value, result, rank, local_rank, world, fence, ste
         result["host_api_frames_per_s"] = result["host_api"]["frames_per_s"]
 
     # ---- PCIe-inclusive leg (SURVEY 8(d) config 3 as worded: host frames in, host results out) through the library's host entry
-    # point.  The host path is bound by the PCIe link, not by the kernels, and every stream of a process shares 16 hardware queues
+    # point.  The host path is bound by the PCIe link, not by the kernels, and every stream of a process shares its hardware queues
     # with the two copy streams: it runs on a pipeline of its own with 3 pipes (what a host application streaming frames would
     # create; 0.96 of the link against 0.88 through the 12-pipe pipeline of the resident loop), made after that one is closed.
     if world == 1:

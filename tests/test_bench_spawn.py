@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 ARGS = ["--fake", "--steps", "2", "--warmup", "1", "--frames", "8", "--launches", "2", "--width", "64", "--height", "48"]
@@ -51,3 +53,20 @@ def test_bench_under_the_drivers_launcher():
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == 2
+
+
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: float32 / float64 .npy files within 64 MB, the same arrays from two runs with the same arguments"""
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dump-outputs", str(d)] + ARGS, env=_env(), capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        dumps.append({f: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == {"keypoint_counts.npy", "frames.npy", "keypoints.npy", "descriptors.npy"}
+    assert a["keypoint_counts.npy"].shape == (16,) and a["keypoints.npy"].shape == (16, 64, 7)
+    for name, x in a.items():
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, b[name], equal_nan=True), name

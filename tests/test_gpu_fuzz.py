@@ -250,16 +250,24 @@ def test_sequence_batched_device_call(oracle, gen, nframes):
     assert (ncand[0] > 20000) if gen == "S" else (1000 < ncand[0] < 12000)
 
 
-def test_tum_sequence(oracle):
-    """BASELINE config 2 on the real sequence when it is present ($TUM_FR3_WALKING_XYZ): every associated frame through
-    batched device calls, compared per frame with the oracle.  Skipped where the dataset does not exist (this container,
-    the GPU box of the driver)."""
-    from orb_slam2_ssd_semantic_amd import ORBextractor, tum
-    if tum.sequence_dir() is None:
-        pytest.skip("REAL-DATA PARITY NOT RUN: TUM fr3/walking_xyz (BASELINE configs 1-3) is not on this box; set $TUM_FR3_WALKING_XYZ. "
-                    "The substitute for real camera frames is tests/test_gpu_real_photos.py (30 real photographs incl. a stereo pair "
-                    "and JPEG re-encodes == the compiled reference, stage by stage); this file's frames are synthetic S / S_tum.")
-    frames = tum.load_gray_frames()
+def test_tum_sequence(oracle, tmp_path):
+    """BASELINE config 2 on the real sequence when it is present ($TUM_FR3_WALKING_XYZ); elsewhere on a miniature sequence in
+    the same layout (rgb/<timestamp>.png + associate.txt) made of the committed 640x480 photographs of tests/golden/real/vga.
+    Every associated frame goes through the caller's gray conversion and batched device calls, compared per frame with the
+    oracle."""
+    import shutil
+    from orb_slam2_ssd_semantic_amd import ORBextractor, photos, tum
+    seq = tum.sequence_dir()
+    if seq is None:
+        seq = str(tmp_path)
+        os.makedirs(os.path.join(seq, "rgb"))
+        names = sorted(f for f in os.listdir(os.path.join(photos.ROOT, "vga")) if f.endswith(".png"))
+        with open(os.path.join(seq, "associate.txt"), "w") as f:
+            for i, name in enumerate(names):
+                t = 1341846313.5 + i * 0.03
+                shutil.copy(os.path.join(photos.ROOT, "vga", name), os.path.join(seq, "rgb", f"{t:.6f}.png"))
+                f.write(f"{t:.6f} rgb/{t:.6f}.png {t + 0.01:.6f} depth/{t + 0.01:.6f}.png\n")
+    frames = tum.load_gray_frames(seq)
     N, h, w = frames.shape
     e = ORBextractor(1000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=128)
     oe = oracle.OracleExtractor(1000, 1.2, 8, 20, 7)

@@ -3,7 +3,6 @@ exactly 32)?  Stream A: the extractor on 1024 frames, repeated; stream B: a fill
 moving the pyramid's bytes (1.6 GB per 1024 frames), with 0 / 10 / 40 integer operations per 16 bytes, repeated.
 Reports the times alone and together."""
 import ctypes as C, json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,5 @@
 """PCIe-inclusive leg alone (orbfe_pipeline_extract_match), for a few pipe counts / chunk sizes.  usage: python tools/pcie_probe.py"""
 import json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,5 @@
 """config 4 / config 5 shapes through the sequence pipeline (extract only) against one batched call on one handle"""
 import json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
