@@ -496,7 +496,9 @@ orbfe_status orbfe_search_for_triangulation(orbfe_matcher *m, const uint8_t *des
  *   kpsL/descL/nL, kpsR/descR/nR  what those two calls returned (mvKeys / mDescriptors, mvKeysRight / mDescriptorsRight)
  *   mbf, mb                       baseline * fx and the baseline; the reference reads mb before assigning it (:682,
  *                                 undefined) -- here minZ = mb is an explicit argument
- *   uRight[nL], depth[nL]         mvuRight / mvDepth, -1 where no match.  HOST buffers. */
+ *   uRight[nL], depth[nL]         mvuRight / mvDepth, -1 where no match.  HOST buffers.
+ * The two extractors must have the same level count, scale factors and level sizes (as the reference's stereo Frame,
+ * whose two extractors share its settings and image size); ORBFE_ERR_ARG otherwise.  So must the batched form below. */
 orbfe_status orbfe_stereo_matches(orbfe_matcher *m, orbfe_handle *left, orbfe_handle *right, const orbfe_keypoint *kpsL,
                                   const uint8_t *descL, int32_t nL, const orbfe_keypoint *kpsR, const uint8_t *descR,
                                   int32_t nR, float mbf, float mb, float *uRight, float *depth);

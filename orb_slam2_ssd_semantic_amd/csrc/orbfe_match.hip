@@ -2504,6 +2504,17 @@ __global__ __launch_bounds__(1024) void k_stereo_filter(int nL, float *__restric
     }
 }
 
+// The kernel takes the row band from the right extractor's scale table and the SAD bounds from the right pyramid; the
+// reference takes both from the left side (Frame::mvScaleFactors, the left image's size).  They agree only when the two
+// pyramids have the same scale factors and level sizes, which is every stereo Frame the reference builds.
+static bool same_pyramid_shape(const OrbPyrView &L, const OrbPyrView &R)
+{
+    if (L.nlevels != R.nlevels) return false;
+    for (int l = 0; l < L.nlevels; ++l)
+        if (L.scale[l] != R.scale[l] || L.inv_scale[l] != R.inv_scale[l] || L.w[l] != R.w[l] || L.h[l] != R.h[l]) return false;
+    return true;
+}
+
 extern "C" orbfe_status orbfe_stereo_matches(orbfe_matcher *m, orbfe_handle *left, orbfe_handle *right,
                                              const orbfe_keypoint *kpsL, const uint8_t *descL, int32_t nL,
                                              const orbfe_keypoint *kpsR, const uint8_t *descR, int32_t nR, float mbf,
@@ -2520,7 +2531,7 @@ extern "C" orbfe_status orbfe_stereo_matches(orbfe_matcher *m, orbfe_handle *lef
     if (s != ORBFE_OK) return s;
     s = (orbfe_status)orbfe_internal_pyramid_view(right, 0, &a.R);
     if (s != ORBFE_OK) return s;
-    if (a.L.device != m->device || a.R.device != m->device || a.L.nlevels != a.R.nlevels) {
+    if (a.L.device != m->device || a.R.device != m->device || !same_pyramid_shape(a.L, a.R)) {
         orbfe_set_error("stereo: the two extractors and the matcher must share a device and a pyramid shape");
         return ORBFE_ERR_ARG;
     }
@@ -2581,7 +2592,7 @@ extern "C" orbfe_status orbfe_stereo_matches_batch_device(orbfe_matcher *m, orbf
     if (s != ORBFE_OK) return s;
     s = (orbfe_status)orbfe_internal_pyramid_view(right, 0, &a.R);
     if (s != ORBFE_OK) return s;
-    if (a.L.device != m->device || a.R.device != m->device || a.L.nlevels != a.R.nlevels) {
+    if (a.L.device != m->device || a.R.device != m->device || !same_pyramid_shape(a.L, a.R)) {
         orbfe_set_error("stereo: the two extractors and the matcher must share a device and a pyramid shape");
         return ORBFE_ERR_ARG;
     }

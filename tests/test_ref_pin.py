@@ -380,6 +380,32 @@ def test_stereo_matches_equal_sliced_reference(ref, oracle):
     assert matched > 300
 
 
+
+@pytest.mark.parametrize("name", ["kitti_2000", "w643", "sf1.5", "nl12", "hand:band", "hand:edge", "hand:zero", "hand:maxd"])
+def test_stereo_matches_equal_sliced_reference_at_the_edges(ref, oracle, name):
+    """8(f).2b at the shapes of tests/test_gpu_stereo_edges.py: more than 1024 keypoints (kitti_2000), a width of 643, scale
+    factor 1.5, 12 levels, and the hand-placed lists (band edges, octave band, tied distances, endu at the level width, disparity
+    exactly 0, maxD) fed to both; the reference runs on the pyramids its own extractors built; mvuRight / mvDepth bits."""
+    from test_gpu_stereo_edges import PAIRS, oracle_case, oracle_hand
+    if name.startswith("hand:"):
+        c = oracle_hand(name[5:])
+        ext, mbf, mb = c["ext"], c["mbf"], c["mb"]
+        nl0, nr0 = c["nreal"]
+    else:
+        c = oracle_case(name)
+        _, _, _, _, ext, mbf, mb = PAIRS[name]
+        nl0, nr0 = len(c["kL"]), len(c["kR"])
+    rl, rr = ref.RefExtractor(*ext, 20, 7), ref.RefExtractor(*ext, 20, 7)
+    kL, _ = rl(c["left"])
+    kR, _ = rr(c["right"])
+    assert np.array_equal(kL.view(np.uint8), c["kL"][:nl0].view(np.uint8)) and np.array_equal(kR.view(np.uint8), c["kR"][:nr0].view(np.uint8))
+    ru, rd = ref.stereo_matches(rl, rr, c["kL"], c["dL"], c["kR"], c["dR"], mbf, mb)
+    assert np.array_equal(ru.view(np.uint32), c["u"].view(np.uint32)), name
+    assert np.array_equal(rd.view(np.uint32), c["d"].view(np.uint32)), name
+    assert (ru >= 0).sum() > 40
+    if name == "kitti_2000":
+        assert len(c["kL"]) > 1024
+
 # ---------------------------------------------------------------------------------------------- M4 / M9
 def test_search_by_projection_last_frame_equals_reference(ref, oracle):
     """SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1578-1724), the
