@@ -767,6 +767,51 @@ orbfe_status orbfe_vocfile_arrays(const orbfe_vocfile *v, const uint32_t **child
 orbfe_status orbfe_vocfile_save_binary(const orbfe_vocfile *v, const char *path);
 orbfe_status orbfe_vocabulary_create_from_file(int32_t device, const orbfe_vocfile *v, orbfe_vocabulary **out);
 
+/* ---- the fork's optical-flow dynamic-point mask (csrc/orbfe_flow.hip, DESIGN.md "Optical-flow mask") ----------------------
+ * FlowSLAM::Flow::ComputeMask(GrayImg, mask, th) (perfect/src/Flow.cc:15-52): th = max(th, 40); pyrDown to (w/2, h/2);
+ * with a previous half-size frame, Farneback flow (0.5, 3, 15, 3, 5, 1.2, 0) from it to this one, pyrUp (not rescaled),
+ * mask = 0 where fx*fx + fy*fy >= th, then erode, erode, dilate with the 21x21 ellipse; without one, all ones.  The state
+ * becomes this frame's half-size image.  Bit-exact against tests/flow_oracle.py (an unpinned restatement of OpenCV 3.2).
+ * Frames are at least 16 x 16 and at most max_width x max_height.  A frame whose half size differs from the stored
+ * previous frame's returns ORBFE_ERR_SIZE and leaves the state unchanged (OpenCV would throw). */
+typedef struct orbfe_flow orbfe_flow;   /* one FlowSLAM::Flow: device scratch, own stream, the previous half-size frame */
+orbfe_status orbfe_flow_create(int32_t device, int32_t max_width, int32_t max_height, int32_t max_batch, orbfe_flow **out);
+void orbfe_flow_destroy(orbfe_flow *f);
+orbfe_status orbfe_flow_reset(orbfe_flow *f);            /* forget the previous frame (mImGrayLast empty) */
+void *orbfe_flow_get_stream(orbfe_flow *f);
+/* one HOST frame in, HOST mask out (w x h, row pitch mask_stride), state advanced; synchronous */
+orbfe_status orbfe_flow_compute_mask(orbfe_flow *f, const uint8_t *gray, int32_t w, int32_t h, int32_t stride, float threshold,
+                                     uint8_t *mask, int32_t mask_stride);
+/* Sequence form, DEVICE buffers: mask i comes from (frame i-1, frame i); mask 0 from the previous call's last frame, or all ones
+ * when there is none.  d_mask_ones[i] = sum of mask i (may be NULL).  At most max_batch frames.  Enqueued on `stream`
+ * (NULL = HIP's default stream), no synchronisation; the handle's scratch is reused by the next call on any stream. */
+orbfe_status orbfe_flow_compute_masks_device(orbfe_flow *f, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t h,
+                                             int32_t stride, size_t frame_stride, float threshold, uint8_t *d_mask,
+                                             int32_t mask_stride, size_t mask_frame_stride, int32_t *d_mask_ones, void *stream);
+/* perfect/src/Frame.cc:360-377 on the padded device blocks of orbfe_extract_batch_device, in place: frame i keeps only the
+ * keypoints with mask[(int)y][(int)x] == 1 when d_mask_ones[i] > w*h*0.65, in order, descriptors following; slots >= the new
+ * d_n[i] are zero-filled again (the all-gather invariant).  Enqueued on `stream`. */
+orbfe_status orbfe_mask_keypoints_device(const uint8_t *d_mask, int32_t w, int32_t h, int32_t mask_stride, size_t mask_frame_stride,
+                                         const int32_t *d_mask_ones, int32_t nframes, orbfe_keypoint *d_kps, uint8_t *d_desc,
+                                         int32_t *d_n, int32_t cap, void *stream);
+/* Test taps of the last compute call (synchronises the handle's last stream).  `frame` counts in that call, among its last
+ * min(max_batch, 64) frames.  stage / what / dst layout (w, h receive the size):
+ *   0 ORBFE_FLOW_TAP_HALF    the half-size frame                           uint8  [h][w]
+ *   1 ORBFE_FLOW_TAP_FLOW    flow of pyramid level `level` (0 = finest)    float  [h][w][2]
+ *   2 ORBFE_FLOW_TAP_FLOW2   the pyrUp'ed flow                             float  [h][w][2]
+ *   3 ORBFE_FLOW_TAP_PRE     the thresholded mask before morphology       uint8  [h][w]
+ *   4 ORBFE_FLOW_TAP_MASK    the final mask                                uint8  [h][w]
+ *   5 ORBFE_FLOW_TAP_POLY    PolyExp of the frame at `level`               float  [h][w][5]
+ * Stages 1-3 of a frame that had no previous frame return ORBFE_ERR_STATE. */
+enum { ORBFE_FLOW_TAP_HALF = 0, ORBFE_FLOW_TAP_FLOW = 1, ORBFE_FLOW_TAP_FLOW2 = 2, ORBFE_FLOW_TAP_PRE = 3, ORBFE_FLOW_TAP_MASK = 4,
+       ORBFE_FLOW_TAP_POLY = 5 };
+orbfe_status orbfe_flow_tap(orbfe_flow *f, int32_t frame, int32_t stage, int32_t level, void *dst, size_t cap, int32_t *w, int32_t *h);
+/* Host-side constants, no device needed: the level plan of a w x h frame's half-size image (level 0 = finest; lw, lh, ksize
+ * [4], taps [4][19]: the GaussianBlur taps of each level) and FarnebackPrepareGaussian's g, xg, xxg ([3][11], x = -5..5)
+ * and ig11, ig03, ig33, ig55. */
+orbfe_status orbfe_flow_plan(int32_t w, int32_t h, int32_t *nlevels, int32_t *lw, int32_t *lh, int32_t *ksize, float *taps);
+orbfe_status orbfe_flow_poly_constants(float *g, double *ig);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,8 @@ SYMBOLS = (
     "orbfe_pipeline_create", "orbfe_pipeline_destroy", "orbfe_pipeline_pipes", "orbfe_pipeline_capacity", "orbfe_pipeline_sub_batch",
     "orbfe_pipeline_extractor", "orbfe_pipeline_matcher", "orbfe_pipeline_extract_match_device", "orbfe_pipeline_join",
     "orbfe_pipeline_synchronize", "orbfe_pipeline_reset_sequence", "orbfe_pipeline_get_overflow", "orbfe_pipeline_extract_match", "orbfe_pipeline_set_host_pipes",
+    "orbfe_flow_create", "orbfe_flow_destroy", "orbfe_flow_reset", "orbfe_flow_get_stream", "orbfe_flow_compute_mask",
+    "orbfe_flow_compute_masks_device", "orbfe_mask_keypoints_device", "orbfe_flow_tap", "orbfe_flow_plan", "orbfe_flow_poly_constants",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -226,6 +228,18 @@ def _configure(L):
     L.orbfe_pipeline_set_host_pipes.argtypes = [vp, i32]
     L.orbfe_pipeline_extract_match.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, f32, i32, i32, i32]
     L.orbfe_pipeline_get_overflow.argtypes = [vp, vp]
+    L.orbfe_flow_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
+    L.orbfe_flow_destroy.argtypes = [vp]
+    L.orbfe_flow_destroy.restype = None
+    L.orbfe_flow_reset.argtypes = [vp]
+    L.orbfe_flow_get_stream.argtypes = [vp]
+    L.orbfe_flow_get_stream.restype = vp
+    L.orbfe_flow_compute_mask.argtypes = [vp, vp, i32, i32, i32, f32, vp, i32]
+    L.orbfe_flow_compute_masks_device.argtypes = [vp, vp, i32, i32, i32, i32, sz, f32, vp, i32, sz, vp, vp]
+    L.orbfe_mask_keypoints_device.argtypes = [vp, i32, i32, i32, sz, vp, i32, vp, vp, vp, i32, vp]
+    L.orbfe_flow_tap.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp]
+    L.orbfe_flow_plan.argtypes = [i32, i32, vp, vp, vp, vp, vp]
+    L.orbfe_flow_poly_constants.argtypes = [vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default -> orbfe_status / int32

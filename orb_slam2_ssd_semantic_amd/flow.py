@@ -1,0 +1,110 @@
+"""FlowSLAM::Flow on the GPU: the fork's optical-flow dynamic-point mask (perfect/src/Flow.cc:15-52) and the masked-Frame
+keypoint rule (perfect/src/Frame.cc:360-377), through the C-ABI of csrc/orbfe_flow.hip.  No CPU fallback."""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+
+TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY = range(6)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def plan(w, h):
+    """The Farneback level plan of a w x h frame's half-size image, level 0 first: [(lw, lh, ksize, blur taps)]."""
+    L = _ffi.lib()
+    n = C.c_int32()
+    lw, lh, ks = (np.zeros(4, np.int32) for _ in range(3))
+    taps = np.zeros((4, 19), np.float32)
+    _ffi.check(L.orbfe_flow_plan(w, h, C.byref(n), _ffi.ptr(lw), _ffi.ptr(lh), _ffi.ptr(ks), _ffi.ptr(taps)), "orbfe_flow_plan")
+    return [(int(lw[i]), int(lh[i]), int(ks[i]), taps[i, :ks[i]].copy()) for i in range(n.value)]
+
+
+def poly_constants():
+    """FarnebackPrepareGaussian(5, 1.2) as the library computes it: (g, xg, xxg) float32 [11] each, (ig11, ig03, ig33, ig55)."""
+    g = np.zeros(33, np.float32)
+    ig = np.zeros(4, np.float64)
+    _ffi.check(_ffi.lib().orbfe_flow_poly_constants(_ffi.ptr(g), _ffi.ptr(ig)), "orbfe_flow_poly_constants")
+    return g[:11], g[11:22], g[22:], tuple(float(v) for v in ig)
+
+
+class Flow:
+    """One FlowSLAM::Flow: its previous half-size frame lives on the device.  compute_mask() is Flow::ComputeMask on one host
+    frame; compute_masks() the same over a device-resident sequence; mask_keypoints() the masked-Frame rule on the padded
+    device blocks of ORBextractor.extract_batch_device-style outputs."""
+
+    def __init__(self, max_width=640, max_height=480, max_batch=1, device=0):
+        self._L = _ffi.lib()
+        self.h = C.c_void_p()
+        _ffi.check(self._L.orbfe_flow_create(device, max_width, max_height, max_batch, C.byref(self.h)), "orbfe_flow_create")
+        self.device = device
+
+    def close(self):
+        if self.h:
+            self._L.orbfe_flow_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stream(self):
+        return self._L.orbfe_flow_get_stream(self.h)
+
+    def reset(self):
+        _ffi.check(self._L.orbfe_flow_reset(self.h), "orbfe_flow_reset")
+
+    def compute_mask(self, gray, threshold):
+        """Flow::ComputeMask(GrayImg, mask, threshold): uint8 [h, w] of 0 / 1."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        h, w = gray.shape
+        mask = np.empty((h, w), np.uint8)
+        _ffi.check(self._L.orbfe_flow_compute_mask(self.h, _ffi.ptr(gray), w, h, w, float(threshold), _ffi.ptr(mask), w),
+                   "orbfe_flow_compute_mask")
+        return mask
+
+    def compute_masks(self, frames, threshold, masks=None, ones=None, stream=None):
+        """frames: torch uint8 [n, h, w] on the device.  Returns (masks uint8 [n, h, w], ones int32 [n]) on the device; mask i
+        comes from frames i-1 and i (mask 0 from the previous call's last frame).  Enqueued on `stream` (default: torch's
+        current stream), no synchronisation."""
+        import torch
+        n, h, w = frames.shape
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.stride(2) == 1 and frames.stride(1) == w
+        if masks is None:
+            masks = torch.empty((n, h, w), dtype=torch.uint8, device=frames.device)
+        if ones is None:
+            ones = torch.empty(n, dtype=torch.int32, device=frames.device)
+        st = torch.cuda.current_stream(frames.device).cuda_stream if stream is None else stream
+        _ffi.check(self._L.orbfe_flow_compute_masks_device(self.h, _ptr(frames), n, w, h, w, frames.stride(0), float(threshold),
+                                                           _ptr(masks), w, masks.stride(0), _ptr(ones), C.c_void_p(st)),
+                   "orbfe_flow_compute_masks_device")
+        return masks, ones
+
+    def tap(self, frame, stage, level=0):
+        """A stage of the last call (frame index within it): see orbfe_flow_tap."""
+        per = {TAP_HALF: (np.uint8, 1), TAP_FLOW: (np.float32, 2), TAP_FLOW2: (np.float32, 2), TAP_PRE: (np.uint8, 1),
+               TAP_MASK: (np.uint8, 1), TAP_POLY: (np.float32, 5)}
+        dt, ch = per[stage]
+        cap = 4096 * 4096 * 20
+        buf = np.empty(cap, np.uint8)
+        w, h = C.c_int32(), C.c_int32()
+        _ffi.check(self._L.orbfe_flow_tap(self.h, frame, stage, level, _ffi.ptr(buf), cap, C.byref(w), C.byref(h)), "orbfe_flow_tap")
+        n = w.value * h.value * ch * np.dtype(dt).itemsize
+        a = buf[:n].view(dt).reshape(h.value, w.value, ch)
+        return a[:, :, 0].copy() if ch == 1 else a.copy()
+
+
+def mask_keypoints(masks, ones, kps, desc, n, cap, stream=None):
+    """perfect/src/Frame.cc:360-377 in place on device blocks: masks uint8 [b, h, w], ones int32 [b], kps [b*cap*28] bytes
+    (orbfe_keypoint), desc uint8 [b*cap*32], n int32 [b] -- all torch tensors on the device."""
+    import torch
+    b, h, w = masks.shape
+    st = torch.cuda.current_stream(masks.device).cuda_stream if stream is None else stream
+    _ffi.check(_ffi.lib().orbfe_mask_keypoints_device(_ptr(masks), w, h, w, masks.stride(0), _ptr(ones), b, _ptr(kps), _ptr(desc),
+                                                      _ptr(n), cap, C.c_void_p(st)), "orbfe_mask_keypoints_device")
