@@ -788,6 +788,22 @@ orbfe_status orbfe_flow_compute_mask(orbfe_flow *f, const uint8_t *gray, int32_t
 orbfe_status orbfe_flow_compute_masks_device(orbfe_flow *f, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t h,
                                              int32_t stride, size_t frame_stride, float threshold, uint8_t *d_mask,
                                              int32_t mask_stride, size_t mask_frame_stride, int32_t *d_mask_ones, void *stream);
+/* ComputeMask(GrayImg, Homo, mask, th) (perfect/src/Flow.cc:73-80): warpPerspective(GrayImg, dest, Homo, GrayImg.size()) as
+ * OpenCV 3.2 computes it (INTER_LINEAR, BORDER_CONSTANT 0: M inverted by invert(DECOMP_LU), all zeros when singular; the
+ * invoker's 64-column blocks; 1/32-pixel fixed-point bilinear remap), then the plain ComputeMask on the warped frame.  homo: 9
+ * doubles, row-major, as findHomography returns it (NOT inverted).  The state becomes the WARPED frame's half-size image, so
+ * the next pair compares two warped frames (the reference's behaviour, kept).  Host frame in, host mask out, synchronous.
+ * A NULL homo returns ORBFE_ERR_ARG; size and state rules as orbfe_flow_compute_mask. */
+orbfe_status orbfe_flow_compute_mask_homo(orbfe_flow *f, const uint8_t *gray, int32_t w, int32_t h, int32_t stride,
+                                          const double *homo, float threshold, uint8_t *mask, int32_t mask_stride);
+/* Sequence form.  d_homo: DEVICE [nframes][9] doubles; d_use_homo: DEVICE int32 [nframes], frame i is warped iff nonzero
+ * (NULL = every frame), so a replay can mix tracked and lost frames as TrackHomo does.  Otherwise as
+ * orbfe_flow_compute_masks_device: enqueued on `stream`, no synchronisation, passes of at most 64 frames, state carried. */
+orbfe_status orbfe_flow_compute_masks_homo_device(orbfe_flow *f, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t h,
+                                                  int32_t stride, size_t frame_stride, const double *d_homo,
+                                                  const int32_t *d_use_homo, float threshold, uint8_t *d_mask,
+                                                  int32_t mask_stride, size_t mask_frame_stride, int32_t *d_mask_ones,
+                                                  void *stream);
 /* perfect/src/Frame.cc:360-377 on the padded device blocks of orbfe_extract_batch_device, in place: frame i keeps only the
  * keypoints with mask[(int)y][(int)x] == 1 when d_mask_ones[i] > w*h*0.65, in order, descriptors following; slots >= the new
  * d_n[i] are zero-filled again (the all-gather invariant).  Enqueued on `stream`. */
@@ -802,9 +818,10 @@ orbfe_status orbfe_mask_keypoints_device(const uint8_t *d_mask, int32_t w, int32
  *   3 ORBFE_FLOW_TAP_PRE     the thresholded mask before morphology       uint8  [h][w]
  *   4 ORBFE_FLOW_TAP_MASK    the final mask                                uint8  [h][w]
  *   5 ORBFE_FLOW_TAP_POLY    PolyExp of the frame at `level`               float  [h][w][5]
- * Stages 1-3 of a frame that had no previous frame return ORBFE_ERR_STATE. */
+ *   6 ORBFE_FLOW_TAP_WARP    the warped full-size frame pyrDown read        uint8  [h][w]
+ * Stages 1-3 of a frame that had no previous frame return ORBFE_ERR_STATE, and so does stage 6 of a frame that was not warped. */
 enum { ORBFE_FLOW_TAP_HALF = 0, ORBFE_FLOW_TAP_FLOW = 1, ORBFE_FLOW_TAP_FLOW2 = 2, ORBFE_FLOW_TAP_PRE = 3, ORBFE_FLOW_TAP_MASK = 4,
-       ORBFE_FLOW_TAP_POLY = 5 };
+       ORBFE_FLOW_TAP_POLY = 5, ORBFE_FLOW_TAP_WARP = 6 };
 orbfe_status orbfe_flow_tap(orbfe_flow *f, int32_t frame, int32_t stage, int32_t level, void *dst, size_t cap, int32_t *w, int32_t *h);
 /* Host-side constants, no device needed: the level plan of a w x h frame's half-size image (level 0 = finest; lw, lh, ksize
  * [4], taps [4][19]: the GaussianBlur taps of each level) and FarnebackPrepareGaussian's g, xg, xxg ([3][11], x = -5..5)

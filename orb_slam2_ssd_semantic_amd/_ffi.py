@@ -46,6 +46,7 @@ SYMBOLS = (
     "orbfe_pipeline_synchronize", "orbfe_pipeline_reset_sequence", "orbfe_pipeline_get_overflow", "orbfe_pipeline_extract_match", "orbfe_pipeline_set_host_pipes",
     "orbfe_flow_create", "orbfe_flow_destroy", "orbfe_flow_reset", "orbfe_flow_get_stream", "orbfe_flow_compute_mask",
     "orbfe_flow_compute_masks_device", "orbfe_mask_keypoints_device", "orbfe_flow_tap", "orbfe_flow_plan", "orbfe_flow_poly_constants",
+    "orbfe_flow_compute_mask_homo", "orbfe_flow_compute_masks_homo_device",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -236,6 +237,8 @@ def _configure(L):
     L.orbfe_flow_get_stream.restype = vp
     L.orbfe_flow_compute_mask.argtypes = [vp, vp, i32, i32, i32, f32, vp, i32]
     L.orbfe_flow_compute_masks_device.argtypes = [vp, vp, i32, i32, i32, i32, sz, f32, vp, i32, sz, vp, vp]
+    L.orbfe_flow_compute_mask_homo.argtypes = [vp, vp, i32, i32, i32, vp, f32, vp, i32]
+    L.orbfe_flow_compute_masks_homo_device.argtypes = [vp, vp, i32, i32, i32, i32, sz, vp, vp, f32, vp, i32, sz, vp, vp]
     L.orbfe_mask_keypoints_device.argtypes = [vp, i32, i32, i32, sz, vp, i32, vp, vp, vp, i32, vp]
     L.orbfe_flow_tap.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp]
     L.orbfe_flow_plan.argtypes = [i32, i32, vp, vp, vp, vp, vp]

@@ -2,6 +2,7 @@
 // (perfect/src/Frame.cc:360-377) on the GPU.  Every kernel restates one stage of tests/flow_oracle.py (OpenCV 3.2's
 // generic C++ paths) operation for operation, float where the C++ uses float, double where it uses double, no FMA
 // (-ffp-contract=off), so the outputs are bit-exact against it.  Layout and reuse: DESIGN.md "Optical-flow mask".
+#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
@@ -172,14 +173,9 @@ static void prepare_gaussian(PolyConst &c)
 // ---- kernels ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int refl101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-// pyrDown (u8): the 5x5 [1 4 6 4 1]^2 sum, BORDER_REFLECT_101, (s + 128) >> 8.  Frame b of the call -> slot b + slot0.
-__global__ void k_flow_pyrdown(const uint8_t *src, int stride, size_t fstride, int w, int h, uint8_t *half, int w2, int h2,
-                               int slot0)
+// pyrDown (u8): the 5x5 [1 4 6 4 1]^2 sum, BORDER_REFLECT_101, (s + 128) >> 8, at half-size pixel (x, y) of frame s
+__device__ __forceinline__ uint8_t pyrdown_at(const uint8_t *s, int stride, int w, int h, int x, int y)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= w2 * h2) return;
-    int x = i % w2, y = i / w2;
-    const uint8_t *s = src + blockIdx.y * fstride;
     const int k[5] = {1, 4, 6, 4, 1};
     int acc = 0;
     for (int a = 0; a < 5; a++) {
@@ -188,7 +184,109 @@ __global__ void k_flow_pyrdown(const uint8_t *src, int stride, size_t fstride, i
         for (int b = 0; b < 5; b++) r += k[b] * row[refl101(2 * x + b - 2, w)];
         acc += k[a] * r;
     }
-    half[(size_t)(slot0 + blockIdx.y) * w2 * h2 + i] = (uint8_t)((acc + 128) >> 8);
+    return (uint8_t)((acc + 128) >> 8);
+}
+
+// Frame b of the call -> slot b + slot0.
+__global__ void k_flow_pyrdown(const uint8_t *src, int stride, size_t fstride, int w, int h, uint8_t *half, int w2, int h2,
+                               int slot0)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= w2 * h2) return;
+    half[(size_t)(slot0 + blockIdx.y) * w2 * h2 + i] = pyrdown_at(src + blockIdx.y * fstride, stride, w, h, i % w2, i / w2);
+}
+
+// ---- warpPerspective(src, dst, H, src.size()), INTER_LINEAR, BORDER_CONSTANT 0 (modules/imgproc/src/imgwarp.cpp) ----------
+// std::min / std::max as <algorithm> defines them (a NaN argument in second place loses)
+__device__ __forceinline__ double std_min(double a, double b) { return (b < a) ? b : a; }
+__device__ __forceinline__ double std_max(double a, double b) { return (a < b) ? b : a; }
+
+// One thread per frame: warped[b] = (use == NULL || use[b] != 0); inv[b] = invert(H[b]) (DECOMP_LU, n = 3: the closed form of
+// lapack.cpp, det3 in its macro order, d = 1./d, each cofactor difference times d; all zeros when det3 == 0).
+__global__ void k_flow_homo_prep(const double *H, const int32_t *use, int n, double *inv, int32_t *warped)
+{
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    warped[b] = use ? (use[b] != 0) : 1;
+    const double *m = H + (size_t)b * 9;
+    double *t = inv + (size_t)b * 9;
+#define Md(r, c) m[(r) * 3 + (c)]
+    double d = Md(0, 0) * (Md(1, 1) * Md(2, 2) - Md(1, 2) * Md(2, 1)) - Md(0, 1) * (Md(1, 0) * Md(2, 2) - Md(1, 2) * Md(2, 0)) +
+               Md(0, 2) * (Md(1, 0) * Md(2, 1) - Md(1, 1) * Md(2, 0));
+    if (d != 0.) {
+        d = 1. / d;
+        double r[9];
+        r[0] = (Md(1, 1) * Md(2, 2) - Md(1, 2) * Md(2, 1)) * d;
+        r[1] = (Md(0, 2) * Md(2, 1) - Md(0, 1) * Md(2, 2)) * d;
+        r[2] = (Md(0, 1) * Md(1, 2) - Md(0, 2) * Md(1, 1)) * d;
+        r[3] = (Md(1, 2) * Md(2, 0) - Md(1, 0) * Md(2, 2)) * d;
+        r[4] = (Md(0, 0) * Md(2, 2) - Md(0, 2) * Md(2, 0)) * d;
+        r[5] = (Md(0, 2) * Md(1, 0) - Md(0, 0) * Md(1, 2)) * d;
+        r[6] = (Md(1, 0) * Md(2, 1) - Md(1, 1) * Md(2, 0)) * d;
+        r[7] = (Md(0, 1) * Md(2, 0) - Md(0, 0) * Md(2, 1)) * d;
+        r[8] = (Md(0, 0) * Md(1, 1) - Md(0, 1) * Md(1, 0)) * d;
+        for (int k = 0; k < 9; k++) t[k] = r[k];
+    } else {
+        for (int k = 0; k < 9; k++) t[k] = 0.;
+    }
+#undef Md
+}
+
+// One thread per destination pixel of the warped frames: WarpPerspectiveInvoker's coordinates (blocks of bw0 = min(64, w)
+// columns; the block start xb enters X0 / Y0 / W0, the offset x1 = x - xb is added per pixel: the split changes bits), then
+// remapBilinear<FixedPtCast<int, uchar, 15>> with the INTER_LINEAR table (32 x 32 sub-pixel steps, weights in 1/32768).
+// Frames with warped[b] == 0 are skipped (pyrDown reads the caller's frame for them).
+__global__ void k_flow_warp(const uint8_t *src, int stride, size_t fstride, int w, int h, const double *inv, const int32_t *warped,
+                            uint8_t *dst)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int b = blockIdx.y;
+    if (i >= w * h || !warped[b]) return;
+    int x = i % w, y = i / w;
+    const double *M = inv + (size_t)b * 9;
+    const int bw0 = min(64, w);
+    int xb = x - x % bw0, x1 = x - xb;
+    double X0 = M[0] * xb + M[1] * y + M[2];
+    double Y0 = M[3] * xb + M[4] * y + M[5];
+    double W0 = M[6] * xb + M[7] * y + M[8];
+    double W = W0 + M[6] * x1;
+    W = W != 0. ? 32.0 / W : 0.;
+    double fX = std_max((double)INT_MIN, std_min((double)INT_MAX, (X0 + M[0] * x1) * W));
+    double fY = std_max((double)INT_MIN, std_min((double)INT_MAX, (Y0 + M[3] * x1) * W));
+    int X = (int)rint(fX), Y = (int)rint(fY);   // cvRound: nearest, ties to even
+    int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
+    int tx = X & 31, ty = Y & 31;
+    const uint8_t *S = src + (size_t)b * fstride;
+    int out;
+    if ((unsigned)sx < (unsigned)(w - 1) && (unsigned)sy < (unsigned)(h - 1)) {
+        const uint8_t *p = S + (size_t)sy * stride + sx;
+        int v0 = p[0], v1 = p[1], v2 = p[stride], v3 = p[stride + 1];
+        out = (v0 * ((32 - ty) * (32 - tx) * 32) + v1 * ((32 - ty) * tx * 32) + v2 * (ty * (32 - tx) * 32) + v3 * (ty * tx * 32) +
+               16384) >> 15;
+    } else if (sx >= w || sx + 1 < 0 || sy >= h || sy + 1 < 0) {
+        out = 0;
+    } else {
+        bool x0in = sx >= 0, x1in = sx + 1 < w, y0in = sy >= 0, y1in = sy + 1 < h;
+        int v0 = x0in && y0in ? S[(size_t)sy * stride + sx] : 0;
+        int v1 = x1in && y0in ? S[(size_t)sy * stride + sx + 1] : 0;
+        int v2 = x0in && y1in ? S[(size_t)(sy + 1) * stride + sx] : 0;
+        int v3 = x1in && y1in ? S[(size_t)(sy + 1) * stride + sx + 1] : 0;
+        out = (v0 * ((32 - ty) * (32 - tx) * 32) + v1 * ((32 - ty) * tx * 32) + v2 * (ty * (32 - tx) * 32) + v3 * (ty * tx * 32) +
+               16384) >> 15;
+    }
+    dst[(size_t)b * w * h + i] = (uint8_t)out;
+}
+
+// pyrDown of the homography path: frame b reads its warped plane (w x h, packed) when warped[b], the caller's frame otherwise
+__global__ void k_flow_pyrdown_sel(const uint8_t *src, int stride, size_t fstride, const uint8_t *wsrc, const int32_t *warped, int w,
+                                   int h, uint8_t *half, int w2, int h2, int slot0)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= w2 * h2) return;
+    int b = blockIdx.y;
+    uint8_t v = warped[b] ? pyrdown_at(wsrc + (size_t)b * w * h, w, w, h, i % w2, i / w2)
+                          : pyrdown_at(src + (size_t)b * fstride, stride, w, h, i % w2, i / w2);
+    half[(size_t)(slot0 + b) * w2 * h2 + i] = v;
 }
 
 // GaussianBlur row filter on the u8 half-size image converted to float (SymmRowSmallFilter for 3 taps, RowFilter otherwise)
@@ -637,15 +735,19 @@ struct orbfe_flow {
     float *d_T = nullptr, *d_B = nullptr, *d_I = nullptr, *d_R = nullptr, *d_FL = nullptr, *d_M = nullptr, *d_F2 = nullptr;
     double *d_V = nullptr;
     int32_t *d_ones = nullptr;
+    // the homography path: one chunk of warped full-size frames, their inverse matrices and warped flags, the host call's H
+    uint8_t *d_warp = nullptr;
+    double *d_hinv = nullptr, *d_homo1 = nullptr;
+    int32_t *d_warped = nullptr;
     // what the taps read: the last chunk of the last call
-    int tap_valid = 0, tap_n = 0, tap_first = 0, tap_pair0 = 0, tap_w = 0, tap_h = 0;
+    int tap_valid = 0, tap_n = 0, tap_first = 0, tap_pair0 = 0, tap_w = 0, tap_h = 0, tap_homo = 0;
     FlowPlan tap_plan;
 };
 
 static void flow_free(orbfe_flow *f)
 {
     void *ptrs[] = {f->d_last, f->d_half, f->d_gray, f->d_mask_host, f->d_m0, f->d_m1, f->d_mfinal, f->d_T, f->d_B, f->d_I, f->d_R,
-                    f->d_FL, f->d_M, f->d_F2, f->d_V, f->d_ones};
+                    f->d_FL, f->d_M, f->d_F2, f->d_V, f->d_ones, f->d_warp, f->d_hinv, f->d_homo1, f->d_warped};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (f->stream) (void)hipStreamDestroy(f->stream);
@@ -721,7 +823,9 @@ extern "C" orbfe_status orbfe_flow_create(int32_t device, int32_t max_width, int
               hipMalloc(&f->d_M, pairs * hw2 * 5 * sizeof(float)) == hipSuccess &&
               hipMalloc(&f->d_V, pairs * hw2 * 5 * sizeof(double)) == hipSuccess &&
               hipMalloc(&f->d_F2, pairs * f2 * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_ones, pairs * sizeof(int32_t)) == hipSuccess;
+              hipMalloc(&f->d_ones, pairs * sizeof(int32_t)) == hipSuccess &&
+              hipMalloc(&f->d_warp, pairs * hw) == hipSuccess && hipMalloc(&f->d_hinv, pairs * 9 * sizeof(double)) == hipSuccess &&
+              hipMalloc(&f->d_homo1, 9 * sizeof(double)) == hipSuccess && hipMalloc(&f->d_warped, pairs * sizeof(int32_t)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         orbfe_set_error("orbfe_flow_create: device allocation failed");
@@ -753,9 +857,12 @@ extern "C" orbfe_status orbfe_flow_reset(orbfe_flow *f)
 
 extern "C" void *orbfe_flow_get_stream(orbfe_flow *f) { return f ? (void *)f->stream : nullptr; }
 
-// One chunk: frames [0, n) of d_gray; slot 0 holds the previous frame's half-size image when have_prev.
+// One chunk: frames [0, n) of d_gray; slot 0 holds the previous frame's half-size image when have_prev.  With d_homo
+// ([n][9], device) the frames with a nonzero d_use entry (all when d_use is NULL) are warped first and pyrDown reads the warped
+// planes; without it the launches are those of the plain ComputeMask.
 static orbfe_status flow_chunk(orbfe_flow *f, const uint8_t *d_gray, int n, int w, int h, int stride, size_t fstride, float th,
-                               uint8_t *d_mask, int mstride, size_t mfs, int32_t *d_ones, bool have_prev, hipStream_t st)
+                               uint8_t *d_mask, int mstride, size_t mfs, int32_t *d_ones, bool have_prev, const double *d_homo,
+                               const int32_t *d_use, hipStream_t st)
 {
     const int w2 = w / 2, h2 = h / 2;
     const size_t hw2 = (size_t)w2 * h2;
@@ -767,7 +874,14 @@ static orbfe_status flow_chunk(orbfe_flow *f, const uint8_t *d_gray, int n, int 
     }
     const int T = 256;
     if (have_prev) ORBFE_HIP(hipMemcpyAsync(f->d_half, f->d_last, hw2, hipMemcpyDeviceToDevice, st));
-    k_flow_pyrdown<<<dim3(nblk(hw2, T), n), T, 0, st>>>(d_gray, stride, fstride, w, h, f->d_half, w2, h2, 1);
+    if (d_homo) {
+        k_flow_homo_prep<<<nblk(n, 64), 64, 0, st>>>(d_homo, d_use, n, f->d_hinv, f->d_warped);
+        k_flow_warp<<<dim3(nblk((size_t)w * h, T), n), T, 0, st>>>(d_gray, stride, fstride, w, h, f->d_hinv, f->d_warped, f->d_warp);
+        k_flow_pyrdown_sel<<<dim3(nblk(hw2, T), n), T, 0, st>>>(d_gray, stride, fstride, f->d_warp, f->d_warped, w, h, f->d_half, w2,
+                                                                 h2, 1);
+    } else {
+        k_flow_pyrdown<<<dim3(nblk(hw2, T), n), T, 0, st>>>(d_gray, stride, fstride, w, h, f->d_half, w2, h2, 1);
+    }
     const int s0 = have_prev ? 0 : 1;            // first slot with an image
     const int nslots = n + 1 - s0;
     const int pair0 = have_prev ? 0 : 1;         // first frame of the chunk with a pair (frame b pairs slots b, b + 1)
@@ -837,6 +951,7 @@ static orbfe_status flow_chunk(orbfe_flow *f, const uint8_t *d_gray, int n, int 
     f->tap_pair0 = pair0;
     f->tap_w = w;
     f->tap_h = h;
+    f->tap_homo = d_homo != nullptr;
     f->tap_plan = P;
     return ORBFE_OK;
 }
@@ -855,7 +970,8 @@ static orbfe_status flow_check(orbfe_flow *f, int w, int h, int stride)
 }
 
 static orbfe_status flow_run(orbfe_flow *f, const uint8_t *d_gray, int n, int w, int h, int stride, size_t fstride, float th,
-                             uint8_t *d_mask, int mstride, size_t mfs, int32_t *d_ones, hipStream_t st)
+                             uint8_t *d_mask, int mstride, size_t mfs, int32_t *d_ones, const double *d_homo, const int32_t *d_use,
+                             hipStream_t st)
 {
     if (th < 40.0) th = 40.0f;   // if (BInaryThreshold < 40.0) BInaryThreshold = 40.0
     // the mask of a frame lives in d_mask; the pre-morphology / erosion scratch is one chunk of w*h planes
@@ -863,7 +979,8 @@ static orbfe_status flow_run(orbfe_flow *f, const uint8_t *d_gray, int n, int w,
     for (int c0 = 0; c0 < n; c0 += f->chunk) {
         int m = std::min(f->chunk, n - c0);
         orbfe_status s = flow_chunk(f, d_gray + (size_t)c0 * fstride, m, w, h, stride, fstride, th, d_mask + (size_t)c0 * mfs, mstride,
-                                    mfs, d_ones ? d_ones + c0 : nullptr, f->have_last, st);
+                                    mfs, d_ones ? d_ones + c0 : nullptr, f->have_last, d_homo ? d_homo + (size_t)c0 * 9 : nullptr,
+                                    d_use ? d_use + c0 : nullptr, st);
         if (s != ORBFE_OK) return s;
         f->have_last = true;
         f->last_w2 = w / 2;
@@ -889,7 +1006,27 @@ extern "C" orbfe_status orbfe_flow_compute_masks_device(orbfe_flow *f, const uin
         return ORBFE_ERR_ARG;
     FDeviceGuard dg(f->device);
     return flow_run(f, d_gray, nframes, w, h, stride, frame_stride, threshold, d_mask, mask_stride, mask_frame_stride, d_mask_ones,
-                    (hipStream_t)stream);
+                    nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" orbfe_status orbfe_flow_compute_masks_homo_device(orbfe_flow *f, const uint8_t *d_gray, int32_t nframes, int32_t w,
+                                                             int32_t h, int32_t stride, size_t frame_stride, const double *d_homo,
+                                                             const int32_t *d_use_homo, float threshold, uint8_t *d_mask,
+                                                             int32_t mask_stride, size_t mask_frame_stride, int32_t *d_mask_ones,
+                                                             void *stream)
+{
+    if (!f || !d_gray || !d_mask || !d_homo || nframes < 1) return ORBFE_ERR_ARG;
+    if (nframes > f->maxb) {
+        orbfe_set_error("%d frames exceed max_batch %d", nframes, f->maxb);
+        return ORBFE_ERR_SIZE;
+    }
+    orbfe_status s = flow_check(f, w, h, stride);
+    if (s != ORBFE_OK) return s;
+    if (mask_stride < w || (nframes > 1 && (frame_stride < (size_t)stride * h || mask_frame_stride < (size_t)mask_stride * h)))
+        return ORBFE_ERR_ARG;
+    FDeviceGuard dg(f->device);
+    return flow_run(f, d_gray, nframes, w, h, stride, frame_stride, threshold, d_mask, mask_stride, mask_frame_stride, d_mask_ones,
+                    d_homo, d_use_homo, (hipStream_t)stream);
 }
 
 extern "C" orbfe_status orbfe_flow_compute_mask(orbfe_flow *f, const uint8_t *gray, int32_t w, int32_t h, int32_t stride, float threshold,
@@ -901,7 +1038,24 @@ extern "C" orbfe_status orbfe_flow_compute_mask(orbfe_flow *f, const uint8_t *gr
     FDeviceGuard dg(f->device);
     hipStream_t st = f->stream;
     ORBFE_HIP(hipMemcpy2DAsync(f->d_gray, w, gray, stride, w, h, hipMemcpyHostToDevice, st));
-    s = flow_run(f, f->d_gray, 1, w, h, w, (size_t)w * h, threshold, f->d_mask_host, w, (size_t)w * h, nullptr, st);
+    s = flow_run(f, f->d_gray, 1, w, h, w, (size_t)w * h, threshold, f->d_mask_host, w, (size_t)w * h, nullptr, nullptr, nullptr, st);
+    if (s != ORBFE_OK) return s;
+    ORBFE_HIP(hipMemcpy2DAsync(mask, mask_stride, f->d_mask_host, w, w, h, hipMemcpyDeviceToHost, st));
+    ORBFE_HIP(hipStreamSynchronize(st));
+    return ORBFE_OK;
+}
+
+extern "C" orbfe_status orbfe_flow_compute_mask_homo(orbfe_flow *f, const uint8_t *gray, int32_t w, int32_t h, int32_t stride,
+                                                     const double *homo, float threshold, uint8_t *mask, int32_t mask_stride)
+{
+    if (!f || !gray || !homo || !mask || mask_stride < w) return ORBFE_ERR_ARG;
+    orbfe_status s = flow_check(f, w, h, stride);
+    if (s != ORBFE_OK) return s;
+    FDeviceGuard dg(f->device);
+    hipStream_t st = f->stream;
+    ORBFE_HIP(hipMemcpy2DAsync(f->d_gray, w, gray, stride, w, h, hipMemcpyHostToDevice, st));
+    ORBFE_HIP(hipMemcpyAsync(f->d_homo1, homo, 9 * sizeof(double), hipMemcpyHostToDevice, st));
+    s = flow_run(f, f->d_gray, 1, w, h, w, (size_t)w * h, threshold, f->d_mask_host, w, (size_t)w * h, nullptr, f->d_homo1, nullptr, st);
     if (s != ORBFE_OK) return s;
     ORBFE_HIP(hipMemcpy2DAsync(mask, mask_stride, f->d_mask_host, w, w, h, hipMemcpyDeviceToHost, st));
     ORBFE_HIP(hipStreamSynchronize(st));
@@ -962,12 +1116,21 @@ extern "C" orbfe_status orbfe_flow_tap(orbfe_flow *f, int32_t frame, int32_t sta
         if (p < 0 && b == 0) return ORBFE_ERR_STATE;
         ow = P.lv[level].w, oh = P.lv[level].h, bytes = (size_t)ow * oh * 20, src = f->d_R + (size_t)(b + 1) * P.rtotal + P.lv[level].roff;
         break;
+    case ORBFE_FLOW_TAP_WARP:
+        if (!f->tap_homo) return ORBFE_ERR_STATE;
+        ow = W, oh = H, bytes = (size_t)W * H, src = f->d_warp + (size_t)b * W * H;
+        break;
     default:
         return ORBFE_ERR_ARG;
     }
     if (cap < bytes) return ORBFE_ERR_CAP;
     FDeviceGuard dg(f->device);
     ORBFE_HIP(hipStreamSynchronize(f->last_stream));
+    if (stage == ORBFE_FLOW_TAP_WARP) {
+        int32_t warped = 0;
+        ORBFE_HIP(hipMemcpy(&warped, f->d_warped + b, sizeof(warped), hipMemcpyDeviceToHost));
+        if (!warped) return ORBFE_ERR_STATE;
+    }
     ORBFE_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     if (w) *w = ow;
     if (h) *h = oh;

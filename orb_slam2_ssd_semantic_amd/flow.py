@@ -1,12 +1,13 @@
-"""FlowSLAM::Flow on the GPU: the fork's optical-flow dynamic-point mask (perfect/src/Flow.cc:15-52) and the masked-Frame
-keypoint rule (perfect/src/Frame.cc:360-377), through the C-ABI of csrc/orbfe_flow.hip.  No CPU fallback."""
+"""FlowSLAM::Flow on the GPU: the fork's optical-flow dynamic-point mask (perfect/src/Flow.cc:15-52), its homography-compensated
+form (:73-80, warpPerspective first) and the masked-Frame keypoint rule (perfect/src/Frame.cc:360-377), through the C-ABI of
+csrc/orbfe_flow.hip.  No CPU fallback."""
 import ctypes as C
 
 import numpy as np
 
 from . import _ffi
 
-TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY = range(6)
+TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY, TAP_WARP = range(7)
 
 
 def _ptr(t):
@@ -60,19 +61,29 @@ class Flow:
     def reset(self):
         _ffi.check(self._L.orbfe_flow_reset(self.h), "orbfe_flow_reset")
 
-    def compute_mask(self, gray, threshold):
-        """Flow::ComputeMask(GrayImg, mask, threshold): uint8 [h, w] of 0 / 1."""
+    def compute_mask(self, gray, threshold, homography=None):
+        """Flow::ComputeMask(GrayImg, mask, threshold): uint8 [h, w] of 0 / 1.  With a 3x3 homography (float32 or float64, as
+        findHomography returns it, not inverted): Flow::ComputeMask(GrayImg, Homo, mask, threshold), the frame warped first."""
         gray = np.ascontiguousarray(gray, np.uint8)
         h, w = gray.shape
         mask = np.empty((h, w), np.uint8)
-        _ffi.check(self._L.orbfe_flow_compute_mask(self.h, _ffi.ptr(gray), w, h, w, float(threshold), _ffi.ptr(mask), w),
-                   "orbfe_flow_compute_mask")
+        if homography is None:
+            _ffi.check(self._L.orbfe_flow_compute_mask(self.h, _ffi.ptr(gray), w, h, w, float(threshold), _ffi.ptr(mask), w),
+                       "orbfe_flow_compute_mask")
+            return mask
+        H = np.asarray(homography)
+        if H.shape != (3, 3) or H.dtype not in (np.float32, np.float64):
+            raise ValueError("homography must be a 3x3 float32 / float64 matrix")
+        H = np.ascontiguousarray(H, np.float64)   # Mat::convertTo(CV_64F): exact for float32
+        _ffi.check(self._L.orbfe_flow_compute_mask_homo(self.h, _ffi.ptr(gray), w, h, w, _ffi.ptr(H), float(threshold), _ffi.ptr(mask),
+                                                        w), "orbfe_flow_compute_mask_homo")
         return mask
 
-    def compute_masks(self, frames, threshold, masks=None, ones=None, stream=None):
+    def compute_masks(self, frames, threshold, masks=None, ones=None, stream=None, homographies=None, use=None):
         """frames: torch uint8 [n, h, w] on the device.  Returns (masks uint8 [n, h, w], ones int32 [n]) on the device; mask i
         comes from frames i-1 and i (mask 0 from the previous call's last frame).  Enqueued on `stream` (default: torch's
-        current stream), no synchronisation."""
+        current stream), no synchronisation.  homographies: torch float64 [n, 3, 3] on the device; frame i is warped by
+        homographies[i] first when use is None or use[i] != 0 (use: torch int32 [n] on the device)."""
         import torch
         n, h, w = frames.shape
         assert frames.dtype == torch.uint8 and frames.is_cuda and frames.stride(2) == 1 and frames.stride(1) == w
@@ -81,15 +92,28 @@ class Flow:
         if ones is None:
             ones = torch.empty(n, dtype=torch.int32, device=frames.device)
         st = torch.cuda.current_stream(frames.device).cuda_stream if stream is None else stream
-        _ffi.check(self._L.orbfe_flow_compute_masks_device(self.h, _ptr(frames), n, w, h, w, frames.stride(0), float(threshold),
-                                                           _ptr(masks), w, masks.stride(0), _ptr(ones), C.c_void_p(st)),
-                   "orbfe_flow_compute_masks_device")
+        if homographies is None:
+            if use is not None:
+                raise ValueError("use without homographies")
+            _ffi.check(self._L.orbfe_flow_compute_masks_device(self.h, _ptr(frames), n, w, h, w, frames.stride(0), float(threshold),
+                                                               _ptr(masks), w, masks.stride(0), _ptr(ones), C.c_void_p(st)),
+                       "orbfe_flow_compute_masks_device")
+            return masks, ones
+        H = homographies
+        if H.dtype != torch.float64 or tuple(H.shape) != (n, 3, 3) or not H.is_cuda or not H.is_contiguous():
+            raise ValueError("homographies must be a contiguous torch float64 [n, 3, 3] on the device")
+        if use is not None and (use.dtype != torch.int32 or tuple(use.shape) != (n,) or not use.is_cuda or not use.is_contiguous()):
+            raise ValueError("use must be a contiguous torch int32 [n] on the device")
+        _ffi.check(self._L.orbfe_flow_compute_masks_homo_device(self.h, _ptr(frames), n, w, h, w, frames.stride(0), _ptr(H),
+                                                                None if use is None else _ptr(use), float(threshold), _ptr(masks), w,
+                                                                masks.stride(0), _ptr(ones), C.c_void_p(st)),
+                   "orbfe_flow_compute_masks_homo_device")
         return masks, ones
 
     def tap(self, frame, stage, level=0):
         """A stage of the last call (frame index within it): see orbfe_flow_tap."""
         per = {TAP_HALF: (np.uint8, 1), TAP_FLOW: (np.float32, 2), TAP_FLOW2: (np.float32, 2), TAP_PRE: (np.uint8, 1),
-               TAP_MASK: (np.uint8, 1), TAP_POLY: (np.float32, 5)}
+               TAP_MASK: (np.uint8, 1), TAP_POLY: (np.float32, 5), TAP_WARP: (np.uint8, 1)}
         dt, ch = per[stage]
         cap = 4096 * 4096 * 20
         buf = np.empty(cap, np.uint8)

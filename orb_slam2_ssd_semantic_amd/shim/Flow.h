@@ -1,6 +1,6 @@
 // Flow.h -- drop-in replacement for the fork's perfect/include/Flow.h: namespace FlowSLAM, class Flow, the two ComputeMask
-// overloads.  The plain overload runs on the GPU through the C-ABI (orbfe_flow_*, csrc/orbfe_flow.hip); the homography
-// overload warps on the host with cv::warpPerspective (built with ORBFE_WITH_OPENCV only) and then calls the plain one.
+// overloads.  Both run on the GPU through the C-ABI (orbfe_flow_*, csrc/orbfe_flow.hip); the homography overload warps the
+// frame there with OpenCV 3.2's warpPerspective arithmetic, in every build.
 #pragma once
 
 #ifdef ORBFE_WITH_OPENCV

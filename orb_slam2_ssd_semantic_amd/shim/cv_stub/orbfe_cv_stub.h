@@ -10,6 +10,8 @@
 
 #define CV_8U 0
 #define CV_8UC1 0
+#define CV_32F 5
+#define CV_64F 6
 
 namespace cv {
 struct Point2f {
@@ -22,6 +24,7 @@ struct KeyPoint {  // field order of cv::KeyPoint (28 bytes)
     float size = 0, angle = -1, response = 0;
     int octave = 0, class_id = -1;
 };
+// single-channel matrices of CV_8U (the default), CV_32F or CV_64F elements
 class Mat {
 public:
     int rows = 0, cols = 0;
@@ -29,25 +32,30 @@ public:
     uint8_t *data = nullptr;
     Mat() {}
     Mat(int r, int c, int type) { create(r, c, type); }
-    Mat(int r, int c, int /*type*/, void *ext, size_t stp) : rows(r), cols(c), step(stp), data((uint8_t *)ext) {}
-    void create(int r, int c, int /*type*/)
+    Mat(int r, int c, int type, void *ext, size_t stp) : rows(r), cols(c), step(stp), data((uint8_t *)ext), type_(type) {}
+    void create(int r, int c, int type)
     {
-        if (r == rows && c == cols && own_) return;
-        own_.reset(new std::vector<uint8_t>((size_t)r * c));
-        rows = r; cols = c; step = (size_t)c; data = own_->data();
+        if (r == rows && c == cols && type == type_ && own_) return;
+        type_ = type;
+        own_.reset(new std::vector<uint8_t>((size_t)r * c * elemSize()));
+        rows = r; cols = c; step = (size_t)c * elemSize(); data = own_->data();
     }
     void release() { own_.reset(); rows = cols = 0; step = 0; data = nullptr; }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
-    int type() const { return CV_8UC1; }
-    bool isContinuous() const { return step == (size_t)cols; }
+    int type() const { return type_; }
+    size_t elemSize() const { return type_ == CV_64F ? 8 : type_ == CV_32F ? 4 : 1; }
+    bool isContinuous() const { return step == (size_t)cols * elemSize(); }
+    template <typename T> T &at(int r, int c) { return ((T *)(data + (size_t)r * step))[c]; }
+    template <typename T> const T &at(int r, int c) const { return ((const T *)(data + (size_t)r * step))[c]; }
     template <typename T> T *ptr(int r = 0) { return (T *)(data + (size_t)r * step); }
     template <typename T> const T *ptr(int r = 0) const { return (const T *)(data + (size_t)r * step); }
     uint8_t *ptr(int r = 0) { return data + (size_t)r * step; }
     const uint8_t *ptr(int r = 0) const { return data + (size_t)r * step; }
-    Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.step = step; m.data = data + (size_t)r * step; m.own_ = own_; return m; }
-    Mat roi(int x, int y, int w, int h) const { Mat m; m.rows = h; m.cols = w; m.step = step; m.data = data + (size_t)y * step + x; m.own_ = own_; return m; }
+    Mat row(int r) const { Mat m; m.rows = 1; m.cols = cols; m.step = step; m.data = data + (size_t)r * step; m.type_ = type_; m.own_ = own_; return m; }
+    Mat roi(int x, int y, int w, int h) const { Mat m; m.rows = h; m.cols = w; m.step = step; m.data = data + (size_t)y * step + x * elemSize(); m.type_ = type_; m.own_ = own_; return m; }
     Mat getMat() const { return *this; }
 private:
+    int type_ = CV_8UC1;
     std::shared_ptr<std::vector<uint8_t>> own_;
 };
 typedef const Mat &InputArray;
