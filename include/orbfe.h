@@ -829,6 +829,51 @@ orbfe_status orbfe_flow_tap(orbfe_flow *f, int32_t frame, int32_t stage, int32_t
 orbfe_status orbfe_flow_plan(int32_t w, int32_t h, int32_t *nlevels, int32_t *lw, int32_t *lh, int32_t *ksize, float *taps);
 orbfe_status orbfe_flow_poly_constants(float *g, double *ig);
 
+/* ---- the fork's homography estimate (csrc/orbfe_homography.hip) ---------------------------------------
+ * cv::findHomography(src, dst, method, threshold, mask, max_iters, confidence) of OpenCV 3.2 for method RANSAC (8) and 0 (least
+ * squares over all points), as Tracking::TrackHomo (perfect/src/Tracking.cc:1331-1399) calls it: src = points_current,
+ * dst = points_last, dst ~ H * src.  RANSAC: RNG((uint64)-1), getSubset, runKernel (normalised DLT, JacobiImpl_ eigen),
+ * float computeError, acceptance goodCount > max(maxGoodCount, 3), RANSACUpdateNumIters; then (n > 4) the refit over the
+ * inliers and the 10-iteration Levenberg-Marquardt refinement.  Bit-exact against tests/homography_oracle.py (an unpinned
+ * restatement).  Points are (x, y) float pairs.  threshold <= 0 means 3.  Output H: 9 doubles, row-major (H22 from runKernel's
+ * 1./H22 scaling), all zeros with ok = 0 when there is no model (n < 4, no subset, no model with more than 3 inliers, a failed
+ * method-0 fit); the mask (1 = inlier) is then all zeros.  An unknown method, a RANSAC confidence outside (0, 1), n > max_pairs
+ * or nsets > max_sets return ORBFE_ERR_ARG. */
+#define ORBFE_HOMOGRAPHY_RANSAC 8
+typedef struct orbfe_homography orbfe_homography;   /* device scratch for one host call, test taps, own stream */
+orbfe_status orbfe_homography_create(int32_t device, int32_t max_pairs, int32_t max_sets, orbfe_homography **out);
+void orbfe_homography_destroy(orbfe_homography *h);
+void *orbfe_homography_get_stream(orbfe_homography *h);
+/* HOST points in, HOST H / mask out, synchronous.  mask (n bytes) may be NULL.  *ok = the result (!H.empty()). */
+orbfe_status orbfe_find_homography(orbfe_homography *h, const float *src_xy, const float *dst_xy, int32_t n, int32_t method,
+                                   double threshold, int32_t max_iters, double confidence, double *H, uint8_t *mask, int32_t *ok);
+/* Batched form, DEVICE buffers: set i holds pairs [d_offsets[i], d_offsets[i+1]) of d_src_xy / d_dst_xy (CSR); its mask goes to
+ * the same range of d_mask (required).  d_H [nsets][9], d_ok [nsets]: ok = result && n_i > min_pairs, so min_pairs = 50 gives
+ * TrackHomo's `points_current.size() > 50 && !homo.empty()`, and (d_H, d_ok) are exactly the (d_homo, d_use_homo) of
+ * orbfe_flow_compute_masks_homo_device.  A set with n_i > max_pairs gets ok = 0 and a zero H; its mask is not written.
+ * Enqueued on `stream` (NULL = HIP's default stream), no synchronisation; the taps of the handle are overwritten. */
+orbfe_status orbfe_find_homographies_device(orbfe_homography *h, const int32_t *d_offsets, const float *d_src_xy,
+                                            const float *d_dst_xy, int32_t nsets, int32_t method, double threshold,
+                                            int32_t max_iters, double confidence, int32_t min_pairs, double *d_H, int32_t *d_ok,
+                                            uint8_t *d_mask, void *stream);
+/* Test taps of set `set` of the last call (synchronises the handle's last stream):
+ *   0 ORBFE_HOMO_TAP_RANSAC  the best RANSAC model (zeros unless RANSAC found one)                       double [9]
+ *   1 ORBFE_HOMO_TAP_INFO    RANSAC result, iterations run (the loop counter at exit), final niters,
+ *                            refit accepted (runKernel over the inliers succeeded)                        int32 [4]
+ *   2 ORBFE_HOMO_TAP_REFIT   the refit model before Levenberg-Marquardt (zeros when not refitted)         double [9]
+ * The RANSAC mask is the call's mask output.  ORBFE_ERR_STATE for a set the last call did not have. */
+enum { ORBFE_HOMO_TAP_RANSAC = 0, ORBFE_HOMO_TAP_INFO = 1, ORBFE_HOMO_TAP_REFIT = 2 };
+orbfe_status orbfe_homography_tap(orbfe_homography *h, int32_t set, int32_t stage, void *dst, size_t cap);
+/* Known-answer runs of the device primitives on HOST arrays (synchronous, current device):
+ *   0 ORBFE_HOMO_KAT_RNG       in: uint64 initial state; out: n uint32 of cv::RNG::next()
+ *   1 ORBFE_HOMO_KAT_HYPOT     in: n (a, b) doubles; out: n doubles of lapack.cpp's hypot
+ *   2 ORBFE_HOMO_KAT_NUMITERS  in: n (p, ep, max_iters) doubles; out: n int32 RANSACUpdateNumIters(p, ep, 4, max_iters)
+ *   3 ORBFE_HOMO_KAT_JACOBI9   in: n 9x9 doubles; out: n x (9 eigenvalues, 9x9 eigenvector rows) of JacobiImpl_
+ *   4 ORBFE_HOMO_KAT_JACOBI8   in: n 8x8 doubles; out: n x (8, 8x8) */
+enum { ORBFE_HOMO_KAT_RNG = 0, ORBFE_HOMO_KAT_HYPOT = 1, ORBFE_HOMO_KAT_NUMITERS = 2, ORBFE_HOMO_KAT_JACOBI9 = 3,
+       ORBFE_HOMO_KAT_JACOBI8 = 4 };
+orbfe_status orbfe_homography_kat(int32_t what, int32_t n, const void *in, void *out);
+
 #ifdef __cplusplus
 }
 #endif

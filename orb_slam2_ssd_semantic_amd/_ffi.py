@@ -47,6 +47,8 @@ SYMBOLS = (
     "orbfe_flow_create", "orbfe_flow_destroy", "orbfe_flow_reset", "orbfe_flow_get_stream", "orbfe_flow_compute_mask",
     "orbfe_flow_compute_masks_device", "orbfe_mask_keypoints_device", "orbfe_flow_tap", "orbfe_flow_plan", "orbfe_flow_poly_constants",
     "orbfe_flow_compute_mask_homo", "orbfe_flow_compute_masks_homo_device",
+    "orbfe_homography_create", "orbfe_homography_destroy", "orbfe_homography_get_stream", "orbfe_find_homography",
+    "orbfe_find_homographies_device", "orbfe_homography_tap", "orbfe_homography_kat",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -243,6 +245,16 @@ def _configure(L):
     L.orbfe_flow_tap.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp]
     L.orbfe_flow_plan.argtypes = [i32, i32, vp, vp, vp, vp, vp]
     L.orbfe_flow_poly_constants.argtypes = [vp, vp]
+    f64 = C.c_double
+    L.orbfe_homography_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.orbfe_homography_destroy.argtypes = [vp]
+    L.orbfe_homography_destroy.restype = None
+    L.orbfe_homography_get_stream.argtypes = [vp]
+    L.orbfe_homography_get_stream.restype = vp
+    L.orbfe_find_homography.argtypes = [vp, vp, vp, i32, i32, f64, i32, f64, vp, vp, vp]
+    L.orbfe_find_homographies_device.argtypes = [vp, vp, vp, vp, i32, i32, f64, i32, f64, i32, vp, vp, vp, vp]
+    L.orbfe_homography_tap.argtypes = [vp, i32, i32, vp, sz]
+    L.orbfe_homography_kat.argtypes = [i32, i32, vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default -> orbfe_status / int32

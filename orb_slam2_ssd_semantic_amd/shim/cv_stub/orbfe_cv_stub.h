@@ -60,4 +60,11 @@ private:
 };
 typedef const Mat &InputArray;
 typedef Mat &OutputArray;
+// calib3d's findHomography for Point2f vectors, methods 0 and RANSAC (shim/findHomography_orbfe.cc: on the GPU): a 3x3 CV_64F
+// matrix, or an empty one when there is no model; mask: n x 1 CV_8U, 1 = inlier
+enum { RANSAC = 8 };
+Mat findHomography(const std::vector<Point2f> &srcPoints, const std::vector<Point2f> &dstPoints, int method = 0,
+                   double ransacReprojThreshold = 3);
+Mat findHomography(const std::vector<Point2f> &srcPoints, const std::vector<Point2f> &dstPoints, int method,
+                   double ransacReprojThreshold, Mat &mask, const int maxIters = 2000, const double confidence = 0.995);
 }  // namespace cv
