@@ -11,19 +11,23 @@ Frames are independent, so ranks shard by construction (weak scaling: every rank
 collective on the data path itself.
 
 `value` is the HBM-resident rate (inputs in HBM when the timed region starts); the brute-force matcher of sub-batch j runs on a
-second stream behind an event, so it overlaps the pyramid of sub-batch j + 1 (+1.6 %).  The same JSON line also carries
+second stream behind an event, so it overlaps the pyramid of sub-batch j + 1 (+1.6 %).
+
+A plain run does only what `value` needs: set up, warm up, time the K steps, write --dump-outputs, print the line.  With
+`--full` the same JSON line also carries the timed output checked against the oracle (exact_checked), the exchange's
+no-gather steps (N > 1) and
   pcie_inclusive        the contract's config 3 as SURVEY 8(d) words it: pinned host frames -> H2D -> kernels -> D2H of
                         counts / keypoints / descriptors / matches, double-buffered on three streams (never `value`)
   workloads             S(seed) (corner-saturated) and S_tum(seed) (camera-like corner statistics), both FAST variants
   config4               the batched-keyframe configuration: 2000 features, a 1024-frame batch sharded over the ranks,
                         all-gather bytes and bus bandwidth, strong and weak figures
-  roofline / cpu_baseline / cpu_baseline_all_cores
+  roofline / stages / other modes / config5 / bow_chain / stereo_chain / host_api / cpu_baseline / cpu_baseline_all_cores
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1 re-executes itself under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1 re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
-Rank 0 prints ONE JSON line.  oracle/ is used only for the cpu_baseline legs (rank 0, N = 1).
+Rank 0 prints ONE JSON line.  oracle/ is used only by --full (the exactness checks and the CPU baselines).
 `--fake` replaces the extractor by a CPU stand-in over gloo: it exists so that tests/ can drive the spawn /
 rendezvous / gather / reporting path on a box without GPUs; its line is marked "fake": true.
 """
@@ -413,9 +417,13 @@ def main():
     ap.add_argument("--fast-mode", type=int, default=3, help="FAST variant of the timed region (3 auto = the library's default: dense or "
                     "lane-compacting per launch by the pass rate the kernel reports; 0 dense, 1 sparse shortcuts, 2 lane-compacting)")
     ap.add_argument("--no-match", action="store_true", help="extract only (BASELINE config 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines and the latency probe")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (rocprof runs): no PCIe leg, no "
-                    "S_tum leg, no config 4, no CPU baselines")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure as well: the timed output "
+                    "against the oracle, the stage table and roofline, the other modes and workloads, the PCIe leg, configs 4 "
+                    "and 5, the BoW / stereo / host-API / projection chains, the CPU baselines; with N > 1 the gathered frames "
+                    "against the oracle and the steps without the exchange.  A plain run times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the latency probe")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the timed region and the stage table (rocprof "
+                    "runs): no PCIe leg, no S_tum leg, no config 4, no CPU baselines")
     ap.add_argument("--path", choices=["extract_match", "bow", "config5"], default="extract_match",
                     help="bow: print the line of the device-resident ComputeBoW -> SearchByBoW chain instead; config5: the "
                          "line of BASELINE config 5 (512 resident 1920x1080 frames, 4000 features, one batched call)")
@@ -560,28 +568,30 @@ def main():
         for k in range(len(eng.outs)):
             gather.acquire(k)
         # the exchange in numbers: HIP events on the gather stream around the collectives of every timed step, the bytes one rank
-        # contributes, the bus bandwidth an all-gather of that size reached ((N - 1) x bytes per rank leave and enter every GPU), and
-        # the same K steps WITHOUT the exchange: what of the gather the kernels did not hide is the difference
+        # contributes, the bus bandwidth an all-gather of that size reached ((N - 1) x bytes per rank leave and enter every GPU)
         tm = gather.timing(last=args.steps)
         trunc = 0 if fake else sum(gather.truncated(k) for k in range(len(eng.outs)))
-        use_gather[0] = False
-        el_ng = timed(args.steps)
-        use_gather[0] = True
-        step()      # the last output set gathered again (the checks below read the gathered blocks of the last step)
-        fence()
-        for k in range(len(eng.outs)):
-            gather.acquire(k)
-        ms_g, ms_ng = elapsed / args.steps * 1e3, el_ng / args.steps * 1e3
+        ms_g = elapsed / args.steps * 1e3
         exch = {"gather_ms": round(tm["mean_ms"], 4) if tm else None, "gather_ms_max": round(tm["max_ms"], 4) if tm else None,
                 "gather_timed_by": ("wall clock of the host-staged worker (D2H + gloo + H2D)" if same else
                                     "HIP events on the gather stream around the three collectives (RCCL)") if not fake else "not timed (CPU stand-in)",
                 "gather_bytes_per_rank": int(gather.bytes_per_rank), "gather_slots_per_frame": int(gcap or eng.cap),
                 "gather_slots_full": int(eng.cap), "gather_truncated_frames": int(trunc),
                 "gather_bus_GBps": round(gather.bytes_per_rank * (world - 1) / (tm["mean_ms"] * 1e-3) / 1e9, 2) if tm and tm["mean_ms"] > 0 else None,
-                "ms_per_step_no_gather": round(ms_ng, 4), "ms_per_step_with_gather": round(ms_g, 4),
-                "value_no_gather": round(B * world * args.steps / el_ng, 2),
-                "gather_hidden_frac": (round(max(0.0, min(1.0, 1.0 - max(0.0, ms_g - ms_ng) / tm["mean_ms"])), 4) if tm and tm["mean_ms"] > 0 else None),
-                "rccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS")}
+                "ms_per_step_with_gather": round(ms_g, 4), "rccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS")}
+        if args.full:
+            # the same K steps WITHOUT the exchange: what of the gather the kernels did not hide is the difference
+            use_gather[0] = False
+            el_ng = timed(args.steps)
+            use_gather[0] = True
+            step()      # the last output set gathered again (the checks below read the gathered blocks of the last step)
+            fence()
+            for k in range(len(eng.outs)):
+                gather.acquire(k)
+            ms_ng = el_ng / args.steps * 1e3
+            exch.update({"ms_per_step_no_gather": round(ms_ng, 4), "value_no_gather": round(B * world * args.steps / el_ng, 2),
+                         "gather_hidden_frac": (round(max(0.0, min(1.0, 1.0 - max(0.0, ms_g - ms_ng) / tm["mean_ms"])), 4)
+                                                if tm and tm["mean_ms"] > 0 else None)})
     total_frames = B * world * args.steps
     value = total_frames / elapsed
 
@@ -597,7 +607,7 @@ def main():
                                     "features, 8 levels, %s; a step = ONE call of the library's sequence pipeline "
                                     "(orbfe_pipeline_extract_match_device) over %d resident frames per GPU = %d sub-batches of %d on %d "
                                     "pipes, frame k matched against frame k - 1 across sub-batches and steps%s; exactness is "
-                                    "checked against the in-repo oracle, which is pinned to the compiled reference "
+                                    "checked by --full runs against the in-repo oracle, which is pinned to the compiled reference "
                                     "(tests/test_ref_pin.py)") %
                                    (w, h, args.workload, nf, "extract only" if args.no_match else
                                     "extract + brute-force Hamming match to the previous frame (nnratio 0.9, TH_HIGH 100, rot. hist.)",
@@ -626,7 +636,8 @@ def main():
             result["exchange"] = exch if exch is not None else {"gather": "disabled (--no-gather): compute only"}
             if exch:
                 for k in ("gather_ms", "gather_bytes_per_rank", "gather_bus_GBps", "gather_hidden_frac", "ms_per_step_no_gather", "value_no_gather"):
-                    result[k] = exch[k]
+                    if k in exch:
+                        result[k] = exch[k]
         if same:
             result["same_device"] = True
             result["config"]["workload"] = ("SAME-DEVICE TEST MODE -- %d ranks share ONE GPU, host-staged gloo exchange: exercises the N > 1 "
@@ -637,15 +648,15 @@ def main():
             result["gathered_frames"] = int(gather.result(0)[0].shape[0]) if gather else B
 
     if not fake and rank == 0:
-        if args.no_extras:
-            result["exact_checked"] = False   # profiling runs: no oracle in the process
+        if args.no_extras or not args.full:
+            result["exact_checked"] = False   # a plain run / profiling runs: no oracle in the process
         else:
             result.update(self_check(eng, d_gray, (counter[0] - 1) % len(eng.outs), nf))
-    if not fake and world > 1 and not args.no_extras and gather:
+    if not fake and world > 1 and args.full and not args.no_extras and gather:
         chk = gathered_check(eng, gather, d_gray, (counter[0] - 1) % len(eng.outs), nf, rank, world)
         if rank == 0:
             result.update(chk)
-    if not fake:
+    if not fake and args.full:
         extras(args, eng, d_gray, value, result, rank, local_rank, world, fence, step, timed)
     if gather:
         gather.close()

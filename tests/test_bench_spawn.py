@@ -20,7 +20,7 @@ def _env():
 
 
 def test_bench_spawns_its_own_ranks():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + ARGS, env=_env(), capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full"] + ARGS, env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout          # rank 0 prints ONE line
@@ -31,6 +31,22 @@ def test_bench_spawns_its_own_ranks():
     ex = j["exchange"]                        # the exchange step's figures travel in the line (times are the GPU run's)
     assert ex["gather_bytes_per_rank"] == 16 * 4 + 16 * 64 * (28 + 32) and ex["ms_per_step_no_gather"] > 0 and ex["value_no_gather"] > 0
     assert j["scaling"] == "weak" and j["higher_is_better"] is True
+
+
+def test_a_plain_run_leaves_the_other_legs_to_full():
+    """without --full the line carries the headline figure of the timed steps: the exchange is timed inside them, the same
+    steps without it are not run again"""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + ARGS, env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == 2 and j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert j["unit"] == "frames/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+    ex = j["exchange"]
+    assert ex["gather_bytes_per_rank"] == 16 * 4 + 16 * 64 * (28 + 32) and ex["ms_per_step_with_gather"] > 0
+    for k in ("ms_per_step_no_gather", "value_no_gather", "gather_hidden_frac"):
+        assert k not in ex and k not in j, k
 
 
 def test_bench_refuses_a_wrong_world_size():

@@ -25,7 +25,7 @@ def _env():
 
 @pytest.mark.gpu
 def test_two_ranks_on_one_device_run_every_multi_gpu_path():
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--same-device", "--steps", "3", "--warmup", "1", "--frames", "128", "--launches", "4",
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--same-device", "--full", "--steps", "3", "--warmup", "1", "--frames", "128", "--launches", "4",
            "--seeds", "128", "--config4-batch", "1023"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

@@ -14,7 +14,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out")
 tag = sys.argv[1]
-bench_args = ["--no-extras", "--launches", "2", "--steps", "4", "--warmup", "2"] + sys.argv[2:]   # e.g. --workload S_tum --seeds 32
+bench_args = ["--full", "--no-extras", "--launches", "2", "--steps", "4", "--warmup", "2"] + sys.argv[2:]   # e.g. --workload S_tum --seeds 32
 cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + bench_args
 env = dict(os.environ, TMPDIR="/tmp")
 GROUPS = [["LDSBankConflict"], ["MemUnitStalled"], ["OccupancyPercent"], ["SQ_WAIT_INST_LDS", "SQ_WAVE_CYCLES"],
