@@ -292,7 +292,8 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
             const int second = m2 > (BM_NEG >> 8) ? 128 - m2 : 256;
             const bool valid = qi < nq;
             int m = -1;
-            if (valid && idx >= 0 && best <= th && (float)best < __fmul_rn(nnratio, (float)second)) m = idx;
+            // best < 256: with the reference's initial bestDist = 256 a row at distance 256 never becomes the best
+            if (valid && idx >= 0 && best < 256 && best <= th && (float)best < __fmul_rn(nnratio, (float)second)) m = idx;
             match[out0 + qi] = m;
             if (best_o) best_o[out0 + qi] = valid ? best : 256;
             if (second_o) second_o[out0 + qi] = valid ? second : 256;
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(256) void k_match_popc(const uint8_t *__restrict__ 
         const int second = k2 != 0xFFFFFFFFu ? (int)(k2 >> 22) : 256;
         const int idx = k1 != 0xFFFFFFFFu ? (int)(k1 & 0x3FFFFFu) : -1;
         int m = -1;
-        if (valid && idx >= 0 && best <= th && (float)best < __fmul_rn(nnratio, (float)second)) m = idx;
+        if (valid && idx >= 0 && best < 256 && best <= th && (float)best < __fmul_rn(nnratio, (float)second)) m = idx;  // as k_match_bf
         match[out0 + qi] = m;
         if (best_o) best_o[out0 + qi] = valid ? best : 256;
         if (second_o) second_o[out0 + qi] = valid ? second : 256;

@@ -323,6 +323,45 @@ def test_search_by_bow_kf_kf_equals_reference(ref, oracle, seed):
         assert rn == on and np.array_equal(r12, o12), (seed, it, n1, n2)
 
 
+def test_planted_matcher_edges_equal_reference(ref, oracle):
+    """The planted cases of tests/test_gpu_matcher_edges.py (tests/hamming_cases.py) against the compiled reference:
+    ComputeThreeMaxima on the 0.1f * max1 edges (10, 1), (20, 2), ... and on equal counts; SearchByBoW x2 on ties at the
+    16-feature chunk edges, ties whose earlier feature is already claimed, best == TH_LOW, the float ratio edges at 0.6 and
+    0.8, invalid map points, and 1000 one-feature nodes with half-bin rotations."""
+    import hamming_cases as H
+    import test_gpu_matcher_edges as E
+    for m1, m2 in H.MAXIMA_EDGES:
+        for m3 in (0, m2 - 1, m2):
+            for at in ((0, 1, 2), (12, 3, 0), (5, 11, 7)):
+                c = np.zeros(30, np.int32)
+                c[at[0]], c[at[1]], c[at[2]] = m1, m2, m3
+                assert ref.three_maxima(c) == oracle.three_maxima(c) == H.three_maxima(c), c.tolist()
+        c = np.zeros(30, np.int32)
+        c[[3, 7, 9]] = m1, m1 // 2, m2                    # the third maximum on the edge
+        assert ref.three_maxima(c) == oracle.three_maxima(c) == (3, 7, 9)
+    for eq in ((7, 7, 7, 7), (9, 5, 9, 9, 9), (3, 3)):
+        c = np.zeros(30, np.int32)
+        c[[12, 1, 4, 8, 11][:len(eq)]] = eq
+        assert ref.three_maxima(c) == oracle.three_maxima(c), c.tolist()
+    rng = np.random.default_rng(17)
+    pairs = E._chunk_tie_pairs(rng) + E._claim_pairs(rng) + E._th_ratio_pairs(rng, 0.6) + E._th_ratio_pairs(rng, 0.8)
+    pairs += E._invalid_pairs(rng) + [E._many_nodes_pair(rng, 1000), E._many_nodes_pair(rng, 150, E.ROTATION_CASES["half15"])]
+    matched = 0
+    for nnratio in (0.6, 0.8, 1.5):
+        for ori in (False, True):
+            for (d1, v1, a1, fv1), (d2, v2, a2, fv2) in pairs:
+                rm, rn = ref.search_by_bow_kf_f(d1, v1, a1, fv1, d2, a2, fv2, nnratio, ori)
+                om, on = oracle.search_by_bow(d1, v1, a1, fv1, d2, None, a2, fv2, nnratio, 50, False, ori)
+                assert rn == on and np.array_equal(rm, om), (nnratio, ori)
+                r12, rn = ref.search_by_bow_kf_kf(d1, v1, a1, fv1, d2, v2, a2, fv2, nnratio, ori)
+                o21, on = oracle.search_by_bow(d1, v1, a1, fv1, d2, v2, a2, fv2, nnratio, 50, True, ori)
+                o12 = np.full(len(d1), -1, np.int32)
+                o12[o21[o21 >= 0]] = np.flatnonzero(o21 >= 0)
+                assert rn == on and np.array_equal(r12, o12), (nnratio, ori)
+                matched += on
+    assert matched > 3000
+
+
 # ---------------------------------------------------------------------------------------------- (f) rows: sliced reference bodies
 def test_frame_grid_equals_sliced_reference(ref, oracle):
     """8(f).2: oracle assign_grid / features_in_area == Frame::AssignFeaturesToGrid / PosInGrid / GetFeaturesInArea cut
