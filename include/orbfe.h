@@ -348,8 +348,9 @@ orbfe_status orbfe_assign_grid(orbfe_matcher *m, const float *xy, int32_t n, flo
 orbfe_status orbfe_assign_grid_host(const float *xy, int32_t n, float minx, float miny, float gw_inv, float gh_inv,
                                     uint32_t *cell_off, uint32_t *cell_idx, int32_t *n_in_grid);
 /* AssignFeaturesToGrid for every frame of an extractor output block, device-resident: frame f's keypoints are
- * d_kps[f * cap .. f * cap + d_n[f]) as orbfe_extract_batch_device wrote them (mvKeysUn == mvKeys: no lens distortion, as
- * for TUM fr3); d_cell_off [nframes][ORBFE_GRID_COLS * ORBFE_GRID_ROWS + 1], d_cell_idx [nframes][cap], d_n_in_grid
+ * d_kps[f * cap .. f * cap + d_n[f]) -- mvKeysUn, so for a camera with lens distortion pass the undistorted block of
+ * orbfe_frame_geometry_batch_device, and without distortion (k1 = 0, as for TUM fr3) the block orbfe_extract_batch_device
+ * wrote; d_cell_off [nframes][ORBFE_GRID_COLS * ORBFE_GRID_ROWS + 1], d_cell_idx [nframes][cap], d_n_in_grid
  * [nframes].  Enqueued on `stream`, no host synchronisation. */
 orbfe_status orbfe_assign_grid_batch_device(orbfe_matcher *m, const orbfe_keypoint *d_kps, const int32_t *d_n, int32_t cap,
                                             int32_t nframes, float minx, float miny, float gw_inv, float gh_inv,
@@ -873,6 +874,52 @@ orbfe_status orbfe_homography_tap(orbfe_homography *h, int32_t set, int32_t stag
 enum { ORBFE_HOMO_KAT_RNG = 0, ORBFE_HOMO_KAT_HYPOT = 1, ORBFE_HOMO_KAT_NUMITERS = 2, ORBFE_HOMO_KAT_JACOBI9 = 3,
        ORBFE_HOMO_KAT_JACOBI8 = 4 };
 orbfe_status orbfe_homography_kat(int32_t what, int32_t n, const void *in, void *out);
+
+/* ---- the per-frame geometry of the RGB-D Frame (csrc/orbfe_frame.hip) ----------------------------------
+ * cv::undistortPoints(src, dst, K, D, noArray(), P) of OpenCV 3.2 (cvUndistortPoints: double arithmetic, 5 fixed iterations when
+ * there are coefficients), Frame::UndistortKeyPoints (perfect/src/Frame.cc:750-781), Frame::ComputeImageBounds (:784-815),
+ * Frame::ComputeStereoFromRGBD (:1041-1062) and Tracking's depth convertTo (perfect/src/Tracking.cc:681-682).  One __host__
+ * __device__ function (csrc/orbfe_undistort.h) serves the kernels and the host bounds helper.  Bit-exact against
+ * tests/undistort_oracle.py (an unpinned restatement).  The tilted model (14 coefficients) and a rectification R are not built. */
+typedef struct orbfe_camera {
+    float K[9];       /* mK, row-major 3x3 (CV_32F): fx = K[0], cx = K[2], fy = K[4], cy = K[5]; the skew K[1] is not read */
+    float P[9];       /* new camera matrix of undistortPoints (row-major 3x3), read when has_P != 0; the Frame passes P = K */
+    int32_t has_P;    /* 0: P absent -- identity, the results are normalised coordinates */
+    float dist[12];   /* mDistCoef: k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4]]] */
+    int32_t ndist;    /* 0, 4, 5, 8 or 12 (ORB-SLAM passes 4, or 5 when k3 != 0: perfect/src/Tracking.cc:154-165); else ORBFE_ERR_ARG */
+    float bf;         /* mbf = baseline * fx (uRight = x_un - bf / depth) */
+} orbfe_camera;
+#define ORBFE_DEPTH_U16 0 /* depth plane of uint16: d = (float)u * scale (convertTo(CV_32F, scale)) */
+#define ORBFE_DEPTH_F32 1 /* depth plane of float: d = v * scale when fabs(scale - 1.0f) > 1e-5 (Tracking's condition), else v */
+/* cv::undistortPoints on n HOST points (x, y) float pairs -> out_xy (may alias xy), on the matcher's stream, synchronous.  No k1
+ * shortcut: every point goes through the iterations (what the Frame skips when k1 == 0 is the caller's business). */
+orbfe_status orbfe_undistort_points(orbfe_matcher *m, const float *xy, int32_t n, const orbfe_camera *cam, float *out_xy);
+/* Frame::ComputeImageBounds(imLeft) for a w x ht image, host only: out = {minX, maxX, minY, maxY, gw_inv, gh_inv}.  dist[0] == 0
+ * (or ndist == 0): {0, w, 0, ht}; else the corners (0, 0), (w, 0), (0, ht), (w, ht) undistorted as orbfe_undistort_points does
+ * (with cam's P) and minX = min(x0, x2), maxX = max(x1, x3), minY = min(y0, y1), maxY = max(y2, y3).  gw_inv = 64.f / (maxX - minX)
+ * and gh_inv = 48.f / (maxY - minY) in float (src/Frame.cc:401-402): the arguments orbfe_assign_grid* take. */
+orbfe_status orbfe_image_bounds(const orbfe_camera *cam, int32_t w, int32_t ht, float out[6]);
+/* UndistortKeyPoints + ComputeStereoFromRGBD for every frame of an extractor output block (d_kps [nframes][cap], d_n [nframes]
+ * as orbfe_extract_batch_device or orbfe_mask_keypoints_device left them), device-resident:
+ *   d_kps_un [nframes][cap]   mvKeysUn: a copy of the keypoint with x, y undistorted; dist[0] == 0 (or ndist == 0): the copy is
+ *                             untouched -- the reference's k1-only test (Frame.cc:752), so k1 = 0 with k2 != 0 is NOT undistorted
+ *   d_depth / d_uright [nframes][cap]   mvDepth / mvuRight: d = the depth plane at ((int)y, (int)x) of the DISTORTED keypoint;
+ *                             d > 0: depth = d, uRight = x_un - bf / d (float), else -1 / -1.  A keypoint outside the plane has no
+ *                             depth (-1 / -1; undefined in the reference).  d_depth_plane == NULL (monocular and stereo Frames):
+ *                             -1 / -1 for all.  d_depth / d_uright may be NULL together (keypoints only).
+ * Slots >= d_n[f] of all three outputs are zero-filled (the all-gather invariant).  The depth plane of frame f starts at
+ * d_depth_plane + f * depth_frame_stride, rows depth_stride bytes apart, depth_w x depth_h elements of depth_format
+ * (ORBFE_DEPTH_*); scale = the float 1.0f / DepthMapFactor.  Enqueued on `stream`, no synchronisation. */
+orbfe_status orbfe_frame_geometry_batch_device(orbfe_matcher *m, const orbfe_keypoint *d_kps, const int32_t *d_n, int32_t cap,
+                                               int32_t nframes, const orbfe_camera *cam, const void *d_depth_plane, int32_t depth_w,
+                                               int32_t depth_h, int32_t depth_format, size_t depth_stride, size_t depth_frame_stride,
+                                               float scale, orbfe_keypoint *d_kps_un, float *d_depth, float *d_uright, void *stream);
+/* mImDepth.convertTo(mImDepth, CV_32F, scale) for nframes w x ht planes (Tracking.cc:681-682), DEVICE buffers: u16 planes always,
+ * f32 planes scaled under Tracking's condition (else copied); dst = (float)src * scale + 0.0f, as cvtScale_ computes it.  Strides
+ * in bytes.  Enqueued on `stream`, no synchronisation. */
+orbfe_status orbfe_depth_to_float_device(const void *d_src, int32_t depth_format, int32_t nframes, int32_t w, int32_t ht,
+                                         size_t src_stride, size_t src_frame_stride, float scale, float *d_dst, size_t dst_stride,
+                                         size_t dst_frame_stride, void *stream);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@ SYMBOLS = (
     "orbfe_flow_compute_mask_homo", "orbfe_flow_compute_masks_homo_device",
     "orbfe_homography_create", "orbfe_homography_destroy", "orbfe_homography_get_stream", "orbfe_find_homography",
     "orbfe_find_homographies_device", "orbfe_homography_tap", "orbfe_homography_kat",
+    "orbfe_undistort_points", "orbfe_image_bounds", "orbfe_frame_geometry_batch_device", "orbfe_depth_to_float_device",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -68,6 +69,15 @@ class OrbfeParams(C.Structure):
                 ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32), ("max_width", C.c_int32),
                 ("max_height", C.c_int32), ("max_batch", C.c_int32), ("device", C.c_int32),
                 ("blur_rounding", C.c_int32)]
+
+
+class OrbfeCamera(C.Structure):
+    """orbfe_camera: K, optional P (has_P), distortion coefficients, bf"""
+    _fields_ = [("K", C.c_float * 9), ("P", C.c_float * 9), ("has_P", C.c_int32), ("dist", C.c_float * 12), ("ndist", C.c_int32),
+                ("bf", C.c_float)]
+
+
+DEPTH_U16, DEPTH_F32 = 0, 1   # ORBFE_DEPTH_*
 
 
 class OrbfeError(RuntimeError):
@@ -255,6 +265,11 @@ def _configure(L):
     L.orbfe_find_homographies_device.argtypes = [vp, vp, vp, vp, i32, i32, f64, i32, f64, i32, vp, vp, vp, vp]
     L.orbfe_homography_tap.argtypes = [vp, i32, i32, vp, sz]
     L.orbfe_homography_kat.argtypes = [i32, i32, vp, vp]
+    cam = C.POINTER(OrbfeCamera)
+    L.orbfe_undistort_points.argtypes = [vp, vp, i32, cam, vp]
+    L.orbfe_image_bounds.argtypes = [cam, i32, i32, vp]
+    L.orbfe_frame_geometry_batch_device.argtypes = [vp, vp, vp, i32, i32, cam, vp, i32, i32, i32, sz, sz, f32, vp, vp, vp, vp]
+    L.orbfe_depth_to_float_device.argtypes = [vp, i32, i32, i32, i32, sz, sz, f32, vp, sz, sz, vp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default -> orbfe_status / int32

@@ -745,6 +745,30 @@ static orbfe_status matcher_create_impl(int32_t device, hipStream_t borrowed, bo
 
 extern "C" void *orbfe_matcher_get_stream(orbfe_matcher *m) { return m ? (void *)m->stream : nullptr; }
 
+// For the entry points of other translation units (orbfe_frame.hip): the matcher's device and own stream; scratch block `idx`
+// grown to `bytes` for a host-buffer call on the own stream (ordered behind the blocks' last user on another stream), and the
+// end of that call.  The caller has made the matcher's device current.
+orbfe_status orbfe_internal_matcher_info(orbfe_matcher *m, int *device, void **stream)
+{
+    if (!m) return ORBFE_ERR_ARG;
+    *device = m->device;
+    *stream = (void *)m->stream;
+    return ORBFE_OK;
+}
+orbfe_status orbfe_internal_matcher_scratch(orbfe_matcher *m, int idx, size_t bytes, void **p)
+{
+    if (!m || idx < 0 || idx >= 16) return ORBFE_ERR_ARG;
+    ORBFE_HIP(scratch_acquire(m, m->stream));
+    ORBFE_HIP(m->b[idx].ensure(bytes));
+    *p = m->b[idx].p;
+    return ORBFE_OK;
+}
+orbfe_status orbfe_internal_matcher_scratch_done(orbfe_matcher *m)
+{
+    ORBFE_HIP(scratch_release(m, m->stream));
+    return ORBFE_OK;
+}
+
 extern "C" orbfe_status orbfe_matcher_set_bf_kernel(orbfe_matcher *m, int32_t kernel)
 {
     if (!m || kernel < 0 || kernel > 1) return ORBFE_ERR_ARG;

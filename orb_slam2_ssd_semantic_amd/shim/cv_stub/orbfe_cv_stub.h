@@ -67,4 +67,9 @@ Mat findHomography(const std::vector<Point2f> &srcPoints, const std::vector<Poin
                    double ransacReprojThreshold = 3);
 Mat findHomography(const std::vector<Point2f> &srcPoints, const std::vector<Point2f> &dstPoints, int method,
                    double ransacReprojThreshold, Mat &mask, const int maxIters = 2000, const double confidence = 0.995);
+// imgproc's undistortPoints as Frame::UndistortKeyPoints / ComputeImageBounds call it (shim/undistortPoints_orbfe.cc: on the GPU):
+// src N x 2 CV_32F points, dst N x 2 CV_32F (may be src), K 3x3 CV_32F, D 4 / 5 / 8 / 12 CV_32F coefficients or empty, R empty,
+// P empty (normalised coordinates) or 3x3 CV_32F
+void undistortPoints(InputArray src, OutputArray dst, InputArray cameraMatrix, InputArray distCoeffs, InputArray R = Mat(),
+                     InputArray P = Mat());
 }  // namespace cv
