@@ -3,6 +3,7 @@
 `python -m orb_slam2_ssd_semantic_amd._build` or `_build.build()`.  hipcc cross-compiles without a
 GPU; the resulting .so travels to the GPU box with the repo snapshot (it is git-ignored only).
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -12,9 +13,10 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB = os.path.join(_PKG, "liborbfe.so")
-SOURCES = ["orbfe_kernels.hip", "orbfe_api.hip", "orbfe_match.hip", "orbfe_io.hip", "orbfe_group.hip", "orbfe_hostgeom.hip",
-           "orbfe_pipeline.hip", "orbfe_flow.hip", "orbfe_homography.hip", "orbfe_frame.hip"]
-HEADERS = ["orbfe_common.h", "orbfe_kernels.h", "orbfe_undistort.h","orbfe_pattern.inc", "orbfe_fast_body.inc", "orbfe_fast_body_u.inc", "orbfe_fast_body_c.inc", "orbfe_pyr_body.inc", os.path.join(_ROOT, "include", "orbfe.h")]
+# every csrc/*.hip is a translation unit of the library and every header a dependency of all of them: nothing to keep by hand
+SOURCES = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hip")))
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [os.path.join(_ROOT, "include", "orbfe.h")]
+MAX_COMPILES = 16   # hipcc processes in flight at once
 ARCH = "gfx950"
 # -ffp-contract=off: no FMA contraction anywhere (outputs must be bit-exact)
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall",
@@ -44,8 +46,7 @@ def _stale():
     except OSError:
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [h if os.path.isabs(h) else os.path.join(CSRC, h)
-                                                       for h in HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -70,19 +71,30 @@ def build(force=False, verbose=False, out_path=None, extra=None, bdir=None):
     bdir = bdir or os.path.join(_PKG, "build")
     os.makedirs(bdir, exist_ok=True)
     procs = []
+
+    def reap():
+        s, p = procs.pop(0)
+        out, _ = p.communicate()
+        if p.returncode != 0:
+            for _, q in procs:
+                q.kill()
+            for _, q in procs:
+                q.communicate()
+            raise RuntimeError(f"hipcc failed on {s}:\n{out}")
+        if verbose and out.strip():
+            print(out, file=sys.stderr)
+
     for s in SOURCES:
         o = os.path.join(bdir, s.replace(".hip", ".o"))
         cmd = [cc, *FLAGS, *extra, "-I", os.path.join(_ROOT, "include"), "-I", CSRC, "-c", os.path.join(CSRC, s), "-o", o]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
+        if len(procs) >= MAX_COMPILES:
+            reap()
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         objs.append(o)
-    for s, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed on {s}:\n{out}")
-        if verbose and out.strip():
-            print(out, file=sys.stderr)
+    while procs:
+        reap()
     cmd = [cc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out_path or LIB, *objs, "-ldl"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

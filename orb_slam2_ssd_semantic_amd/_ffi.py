@@ -80,6 +80,48 @@ class OrbfeCamera(C.Structure):
 DEPTH_U16, DEPTH_F32 = 0, 1   # ORBFE_DEPTH_*
 
 
+def tensor_ptr(t):
+    """the device (or host) address of a torch tensor's first element"""
+    return C.c_void_p(t.data_ptr())
+
+
+def stream_arg(device, stream):
+    """the `void *stream` argument of a *_device entry point: `stream` (a raw hipStream_t value), or torch's current stream on `device`"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(device).cuda_stream
+    return C.c_void_p(stream)
+
+
+class Handle:
+    """Base of the wrappers that own one C handle.  A subclass names the attribute that holds the handle (they differ for
+    historical reasons and are part of what callers reach into), the attribute that holds the library and the destroy entry
+    point; close(), __del__ and the context manager come from here.  `_owned = False` marks a handle someone else destroys."""
+    _HANDLE = "_h"
+    _LIB = "_L"
+    _DESTROY = None
+    _owned = True
+
+    def close(self):
+        h = getattr(self, self._HANDLE, None)
+        if h:
+            if self._owned:
+                getattr(getattr(self, self._LIB), self._DESTROY)(h)
+            setattr(self, self._HANDLE, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class OrbfeError(RuntimeError):
     def __init__(self, status, what):
         self.status = status

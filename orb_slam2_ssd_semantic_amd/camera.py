@@ -7,10 +7,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import DEPTH_F32, DEPTH_U16  # noqa: F401
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+from ._ffi import Handle, stream_arg, tensor_ptr
 
 
 def _depth_format(d):
@@ -33,10 +30,12 @@ def _mat3(a, name):
     return a
 
 
-class Camera:
+class Camera(Handle):
     """mK, mDistCoef and mbf of a Frame.  K: 3x3 (converted to float32, as the settings file's CV_32F mK); dist: 0, 4, 5, 8 or 12
     coefficients k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4]]]; P: the new camera matrix of undistortPoints -- "K" (the Frame's
     call, the default), None (normalised coordinates) or a 3x3 matrix."""
+
+    _HANDLE, _DESTROY = "_m", "orbfe_matcher_destroy"   # the matcher whose stream and scratch the calls use, made on first use
 
     def __init__(self, K, dist=(), bf=0.0, P="K", device=0):
         self._L = _ffi.lib()
@@ -67,17 +66,6 @@ class Camera:
             _ffi.check(self._L.orbfe_matcher_create(self.device, C.byref(m)), "orbfe_matcher_create")
             self._m = m
         return self._m
-
-    def close(self):
-        if self._m:
-            self._L.orbfe_matcher_destroy(self._m)
-            self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def undistort_points(self, xy):
         """cv::undistortPoints(src, dst, K, D, noArray(), P) on host points: float32 [n, 2] (no k1 shortcut)."""
@@ -115,11 +103,11 @@ class Camera:
                 depth = depth.unsqueeze(0)
             fmt = _depth_format(depth)
             es = depth.element_size()
-            dp, dh, dw, ds, dfs = _ptr(depth), depth.shape[1], depth.shape[2], depth.stride(1) * es, depth.stride(0) * es
-        st = torch.cuda.current_stream(kps.device).cuda_stream if stream is None else stream
-        _ffi.check(self._L.orbfe_frame_geometry_batch_device(self._matcher(), _ptr(kps), _ptr(n), int(cap), nframes, C.byref(self.cam), dp,
-                                                             dw, dh, fmt, ds, dfs, float(scale), _ptr(kps_un), _ptr(depth_out),
-                                                             _ptr(uright), C.c_void_p(st)), "orbfe_frame_geometry_batch_device")
+            dp, dh, dw, ds, dfs = tensor_ptr(depth), depth.shape[1], depth.shape[2], depth.stride(1) * es, depth.stride(0) * es
+        st = stream_arg(kps.device, stream)
+        _ffi.check(self._L.orbfe_frame_geometry_batch_device(self._matcher(), tensor_ptr(kps), tensor_ptr(n), int(cap), nframes, C.byref(self.cam), dp,
+                                                             dw, dh, fmt, ds, dfs, float(scale), tensor_ptr(kps_un), tensor_ptr(depth_out),
+                                                             tensor_ptr(uright), st), "orbfe_frame_geometry_batch_device")
         return kps_un, depth_out, uright
 
     @staticmethod
@@ -134,7 +122,7 @@ class Camera:
             out = torch.empty(depth.shape, dtype=torch.float32, device=depth.device)
         o = out.unsqueeze(0) if out.dim() == 2 else out
         es = d.element_size()
-        st = torch.cuda.current_stream(depth.device).cuda_stream if stream is None else stream
-        _ffi.check(_ffi.lib().orbfe_depth_to_float_device(_ptr(d), fmt, nf, w, h, d.stride(1) * es, d.stride(0) * es, float(scale), _ptr(o),
-                                                          o.stride(1) * 4, o.stride(0) * 4, C.c_void_p(st)), "orbfe_depth_to_float_device")
+        st = stream_arg(depth.device, stream)
+        _ffi.check(_ffi.lib().orbfe_depth_to_float_device(tensor_ptr(d), fmt, nf, w, h, d.stride(1) * es, d.stride(0) * es, float(scale), tensor_ptr(o),
+                                                          o.stride(1) * 4, o.stride(0) * 4, st), "orbfe_depth_to_float_device")
         return out

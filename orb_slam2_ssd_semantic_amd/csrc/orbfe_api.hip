@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "orbfe_common.h"
+#include "orbfe_host.h"
 #include "orbfe_kernels.h"
 
 // ---------------------------------------------------------------------------------------------------
@@ -56,68 +57,6 @@ extern "C" int32_t orbfe_device_count(void)
     }
     return n;
 }
-
-struct DeviceGuard {
-    int prev = -1, dev = -1;
-    explicit DeviceGuard(int d) : dev(d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-// ---------------------------------------------------------------------------------------------------
-// device buffer that only grows
-// ---------------------------------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t need)
-    {
-        if (need <= bytes) return hipSuccess;
-        if (p) {
-            hipError_t e = hipFree(p);
-            p = nullptr;
-            bytes = 0;
-            if (e != hipSuccess) return e;
-        }
-        need = (need + 255) & ~(size_t)255;
-        hipError_t e = hipMalloc(&p, need);
-        if (e == hipSuccess) bytes = need;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-struct PinBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t need)
-    {
-        if (need <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = need;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
 
 // ---------------------------------------------------------------------------------------------------
 // handle
@@ -915,17 +854,9 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
         orbfe_set_error("bad orbfe_params (nlevels 1..16, scale_factor > 1, max size <= 4096, max_batch >= 1)");
         return ORBFE_ERR_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        orbfe_set_error("no HIP device visible; liborbfe has no CPU fallback");
-        return ORBFE_ERR_NODEVICE;
-    }
     int dev = p->device;
-    if (dev < 0) {
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    }
-    if (dev >= ndev) { orbfe_set_error("device %d out of range (%d visible)", dev, ndev); return ORBFE_ERR_ARG; }
+    const orbfe_status rs = orb_resolve_device(&dev);
+    if (rs != ORBFE_OK) return rs;
 
     orbfe_handle *h = new (std::nothrow) orbfe_handle();
     if (!h) return ORBFE_ERR_NOMEM;

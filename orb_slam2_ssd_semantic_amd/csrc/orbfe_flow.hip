@@ -9,6 +9,7 @@
 #include <new>
 
 #include "orbfe_common.h"
+#include "orbfe_host.h"
 
 namespace {
 
@@ -702,19 +703,6 @@ __global__ __launch_bounds__(MK_T) void k_mask_keypoints(const uint8_t *mask, in
     if (threadIdx.x == 0) nn[b] = m;
 }
 
-struct FDeviceGuard {
-    int prev = -1, dev = -1;
-    explicit FDeviceGuard(int d) : dev(d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~FDeviceGuard()
-    {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
 inline unsigned nblk(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
 }  // namespace
@@ -746,11 +734,8 @@ struct orbfe_flow {
 
 static void flow_free(orbfe_flow *f)
 {
-    void *ptrs[] = {f->d_last, f->d_half, f->d_gray, f->d_mask_host, f->d_m0, f->d_m1, f->d_mfinal, f->d_T, f->d_B, f->d_I, f->d_R,
-                    f->d_FL, f->d_M, f->d_F2, f->d_V, f->d_ones, f->d_warp, f->d_hinv, f->d_homo1, f->d_warped};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
+    orb_free_all(f->stream, {f->d_last, f->d_half, f->d_gray, f->d_mask_host, f->d_m0, f->d_m1, f->d_mfinal, f->d_T, f->d_B, f->d_I, f->d_R,
+                             f->d_FL, f->d_M, f->d_F2, f->d_V, f->d_ones, f->d_warp, f->d_hinv, f->d_homo1, f->d_warped});
 }
 
 extern "C" orbfe_status orbfe_flow_plan(int32_t w, int32_t h, int32_t *nlevels, int32_t *lw, int32_t *lh, int32_t *ksize, float *taps)
@@ -789,17 +774,11 @@ extern "C" orbfe_status orbfe_flow_create(int32_t device, int32_t max_width, int
     *out = nullptr;
     if (max_width < FL_MIN_SIDE || max_height < FL_MIN_SIDE || max_batch < 1 || (int64_t)max_width * max_height > (1 << 26))
         return ORBFE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        orbfe_set_error("no HIP device visible; liborbfe has no CPU fallback");
-        return ORBFE_ERR_NODEVICE;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= ndev) { orbfe_set_error("device out of range"); return ORBFE_ERR_ARG; }
+    const orbfe_status rs = orb_resolve_device(&device);
+    if (rs != ORBFE_OK) return rs;
     orbfe_flow *f = new (std::nothrow) orbfe_flow();
     if (!f) return ORBFE_ERR_NOMEM;
-    FDeviceGuard dg(device);
+    DeviceGuard dg(device);
     f->device = device;
     f->maxw = max_width;
     f->maxh = max_height;
@@ -810,22 +789,16 @@ extern "C" orbfe_status orbfe_flow_create(int32_t device, int32_t max_width, int
     make_plan(w2, h2, f->maxplan);
     size_t hw2 = (size_t)w2 * h2, hw = (size_t)max_width * max_height, slots = f->chunk + 1, pairs = f->chunk;
     size_t f2 = (size_t)(2 * w2) * (2 * h2) * 2;
-    bool ok = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc(&f->d_last, hw2) == hipSuccess && hipMalloc(&f->d_half, slots * hw2) == hipSuccess &&
-              hipMalloc(&f->d_gray, hw) == hipSuccess && hipMalloc(&f->d_mask_host, hw) == hipSuccess &&
-              hipMalloc(&f->d_m0, pairs * hw) == hipSuccess && hipMalloc(&f->d_m1, pairs * hw) == hipSuccess &&
-              hipMalloc(&f->d_mfinal, pairs * hw) == hipSuccess &&
-              hipMalloc(&f->d_T, slots * hw2 * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_B, slots * hw2 * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_I, slots * hw2 * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_R, slots * f->maxplan.rtotal * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_FL, pairs * f->maxplan.ftotal * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_M, pairs * hw2 * 5 * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_V, pairs * hw2 * 5 * sizeof(double)) == hipSuccess &&
-              hipMalloc(&f->d_F2, pairs * f2 * sizeof(float)) == hipSuccess &&
-              hipMalloc(&f->d_ones, pairs * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&f->d_warp, pairs * hw) == hipSuccess && hipMalloc(&f->d_hinv, pairs * 9 * sizeof(double)) == hipSuccess &&
-              hipMalloc(&f->d_homo1, 9 * sizeof(double)) == hipSuccess && hipMalloc(&f->d_warped, pairs * sizeof(int32_t)) == hipSuccess;
+    auto blk = [](auto **p, size_t bytes) { return OrbAlloc{(void **)p, bytes}; };
+    const bool ok = orb_alloc_all(
+        &f->stream,
+        {blk(&f->d_last, hw2), blk(&f->d_half, slots * hw2), blk(&f->d_gray, hw), blk(&f->d_mask_host, hw), blk(&f->d_m0, pairs * hw),
+         blk(&f->d_m1, pairs * hw), blk(&f->d_mfinal, pairs * hw), blk(&f->d_T, slots * hw2 * sizeof(float)),
+         blk(&f->d_B, slots * hw2 * sizeof(float)), blk(&f->d_I, slots * hw2 * sizeof(float)),
+         blk(&f->d_R, slots * f->maxplan.rtotal * sizeof(float)), blk(&f->d_FL, pairs * f->maxplan.ftotal * sizeof(float)),
+         blk(&f->d_M, pairs * hw2 * 5 * sizeof(float)), blk(&f->d_V, pairs * hw2 * 5 * sizeof(double)),
+         blk(&f->d_F2, pairs * f2 * sizeof(float)), blk(&f->d_ones, pairs * sizeof(int32_t)), blk(&f->d_warp, pairs * hw),
+         blk(&f->d_hinv, pairs * 9 * sizeof(double)), blk(&f->d_homo1, 9 * sizeof(double)), blk(&f->d_warped, pairs * sizeof(int32_t))});
     if (!ok) {
         (void)hipGetLastError();
         orbfe_set_error("orbfe_flow_create: device allocation failed");
@@ -841,7 +814,7 @@ extern "C" orbfe_status orbfe_flow_create(int32_t device, int32_t max_width, int
 extern "C" void orbfe_flow_destroy(orbfe_flow *f)
 {
     if (!f) return;
-    FDeviceGuard dg(f->device);
+    DeviceGuard dg(f->device);
     (void)hipStreamSynchronize(f->last_stream);
     (void)hipStreamSynchronize(f->stream);
     flow_free(f);
@@ -1004,7 +977,7 @@ extern "C" orbfe_status orbfe_flow_compute_masks_device(orbfe_flow *f, const uin
     if (s != ORBFE_OK) return s;
     if (mask_stride < w || (nframes > 1 && (frame_stride < (size_t)stride * h || mask_frame_stride < (size_t)mask_stride * h)))
         return ORBFE_ERR_ARG;
-    FDeviceGuard dg(f->device);
+    DeviceGuard dg(f->device);
     return flow_run(f, d_gray, nframes, w, h, stride, frame_stride, threshold, d_mask, mask_stride, mask_frame_stride, d_mask_ones,
                     nullptr, nullptr, (hipStream_t)stream);
 }
@@ -1024,7 +997,7 @@ extern "C" orbfe_status orbfe_flow_compute_masks_homo_device(orbfe_flow *f, cons
     if (s != ORBFE_OK) return s;
     if (mask_stride < w || (nframes > 1 && (frame_stride < (size_t)stride * h || mask_frame_stride < (size_t)mask_stride * h)))
         return ORBFE_ERR_ARG;
-    FDeviceGuard dg(f->device);
+    DeviceGuard dg(f->device);
     return flow_run(f, d_gray, nframes, w, h, stride, frame_stride, threshold, d_mask, mask_stride, mask_frame_stride, d_mask_ones,
                     d_homo, d_use_homo, (hipStream_t)stream);
 }
@@ -1035,7 +1008,7 @@ extern "C" orbfe_status orbfe_flow_compute_mask(orbfe_flow *f, const uint8_t *gr
     if (!f || !gray || !mask || mask_stride < w) return ORBFE_ERR_ARG;
     orbfe_status s = flow_check(f, w, h, stride);
     if (s != ORBFE_OK) return s;
-    FDeviceGuard dg(f->device);
+    DeviceGuard dg(f->device);
     hipStream_t st = f->stream;
     ORBFE_HIP(hipMemcpy2DAsync(f->d_gray, w, gray, stride, w, h, hipMemcpyHostToDevice, st));
     s = flow_run(f, f->d_gray, 1, w, h, w, (size_t)w * h, threshold, f->d_mask_host, w, (size_t)w * h, nullptr, nullptr, nullptr, st);
@@ -1051,7 +1024,7 @@ extern "C" orbfe_status orbfe_flow_compute_mask_homo(orbfe_flow *f, const uint8_
     if (!f || !gray || !homo || !mask || mask_stride < w) return ORBFE_ERR_ARG;
     orbfe_status s = flow_check(f, w, h, stride);
     if (s != ORBFE_OK) return s;
-    FDeviceGuard dg(f->device);
+    DeviceGuard dg(f->device);
     hipStream_t st = f->stream;
     ORBFE_HIP(hipMemcpy2DAsync(f->d_gray, w, gray, stride, w, h, hipMemcpyHostToDevice, st));
     ORBFE_HIP(hipMemcpyAsync(f->d_homo1, homo, 9 * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1069,11 +1042,9 @@ extern "C" orbfe_status orbfe_mask_keypoints_device(const uint8_t *d_mask, int32
     if (!d_mask || !d_mask_ones || !d_kps || !d_desc || !d_n || nframes < 1 || cap < 1 || w < 1 || h < 1 || mask_stride < w ||
         (nframes > 1 && mask_frame_stride < (size_t)mask_stride * h))
         return ORBFE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return ORBFE_ERR_NODEVICE;
-    }
+    int32_t device = -1;   // the caller's current device: the buffers are theirs
+    const orbfe_status rs = orb_resolve_device(&device);
+    if (rs != ORBFE_OK) return rs;
     k_mask_keypoints<<<nframes, MK_T, 0, (hipStream_t)stream>>>(d_mask, w, h, mask_stride, mask_frame_stride, d_mask_ones, d_kps, d_desc,
                                                                 d_n, cap);
     ORBFE_HIP(hipGetLastError());
@@ -1124,7 +1095,7 @@ extern "C" orbfe_status orbfe_flow_tap(orbfe_flow *f, int32_t frame, int32_t sta
         return ORBFE_ERR_ARG;
     }
     if (cap < bytes) return ORBFE_ERR_CAP;
-    FDeviceGuard dg(f->device);
+    DeviceGuard dg(f->device);
     ORBFE_HIP(hipStreamSynchronize(f->last_stream));
     if (stage == ORBFE_FLOW_TAP_WARP) {
         int32_t warped = 0;

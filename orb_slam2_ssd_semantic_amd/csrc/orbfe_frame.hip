@@ -9,27 +9,10 @@
 #include <algorithm>
 
 #include "orbfe_common.h"
+#include "orbfe_matcher.h"
 #include "orbfe_undistort.h"
 
-// orbfe_match.hip: a matcher's device and own stream, and its scratch blocks for host-buffer entry points of this file
-orbfe_status orbfe_internal_matcher_info(orbfe_matcher *m, int *device, void **stream);
-orbfe_status orbfe_internal_matcher_scratch(orbfe_matcher *m, int idx, size_t bytes, void **p);
-orbfe_status orbfe_internal_matcher_scratch_done(orbfe_matcher *m);
-
 namespace {
-
-struct GuardDev {
-    int prev = -1, dev = -1;
-    explicit GuardDev(int d) : dev(d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~GuardDev()
-    {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
 
 bool cam_ok(const orbfe_camera *cam) { return cam && orb_undistort_ndist_ok(cam->ndist); }
 
@@ -140,24 +123,20 @@ extern "C" orbfe_status orbfe_undistort_points(orbfe_matcher *m, const float *xy
         return ORBFE_ERR_ARG;
     }
     if (n == 0) return ORBFE_OK;
-    int device = 0;
-    void *stv = nullptr;
-    orbfe_status s = orbfe_internal_matcher_info(m, &device, &stv);
-    if (s != ORBFE_OK) return s;
-    GuardDev g(device);
-    hipStream_t st = (hipStream_t)stv;
-    void *buf = nullptr;
+    DeviceGuard g(m->device);
+    hipStream_t st = m->stream;
     const size_t bytes = (size_t)n * 8;
-    s = orbfe_internal_matcher_scratch(m, 0, 2 * bytes, &buf);
-    if (s != ORBFE_OK) return s;
-    float *d_in = (float *)buf, *d_out = (float *)((uint8_t *)buf + bytes);
+    ORBFE_HIP(scratch_acquire(m, st));  // a device-buffer call on another stream may still be using the scratch blocks
+    ORBFE_HIP(m->b[0].ensure(2 * bytes));
+    float *d_in = m->b[0].as<float>(), *d_out = d_in + 2 * (size_t)n;
     ORBFE_HIP(hipMemcpyAsync(d_in, xy, bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, st, (const float *)d_in, n, orb_undistort_prepare(*cam),
                        d_out);
     ORBFE_HIP(hipGetLastError());
     ORBFE_HIP(hipMemcpyAsync(out_xy, d_out, bytes, hipMemcpyDeviceToHost, st));
     ORBFE_HIP(hipStreamSynchronize(st));
-    return orbfe_internal_matcher_scratch_done(m);
+    ORBFE_HIP(scratch_release(m, st));
+    return ORBFE_OK;
 }
 
 extern "C" orbfe_status orbfe_image_bounds(const orbfe_camera *cam, int32_t w, int32_t ht, float out[6])
@@ -208,11 +187,7 @@ extern "C" orbfe_status orbfe_frame_geometry_batch_device(orbfe_matcher *m, cons
     }
     const int64_t nslots = (int64_t)nframes * cap;
     if (nslots == 0) return ORBFE_OK;
-    int device = 0;
-    void *stv = nullptr;
-    orbfe_status s = orbfe_internal_matcher_info(m, &device, &stv);
-    if (s != ORBFE_OK) return s;
-    GuardDev g(device);
+    DeviceGuard g(m->device);
     const bool undistort = !orb_undistort_k1_zero(*cam);
     hipLaunchKernelGGL(k_frame_geometry, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_kps, d_n, cap,
                        nslots, orb_undistort_prepare(*cam), undistort ? 1 : 0, cam->bf, (const uint8_t *)d_depth_plane, depth_w,
@@ -233,11 +208,9 @@ extern "C" orbfe_status orbfe_depth_to_float_device(const void *d_src, int32_t d
         return ORBFE_ERR_ARG;
     }
     if (nframes == 0) return ORBFE_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return ORBFE_ERR_NODEVICE;
-    }
+    int32_t device = -1;   // the caller's current device: the buffers are theirs
+    const orbfe_status rs = orb_resolve_device(&device);
+    if (rs != ORBFE_OK) return rs;
     const int64_t ngroups = (int64_t)nframes * ht * ((w + 3) / 4);
     // 4-pixel groups: whole vectors when every row starts on a 16-byte boundary of dst and an 8- / 16-byte one of src
     const size_t sa = 4 * esz;

@@ -27,6 +27,7 @@
 #include <rccl/rccl.h>
 
 #include "orbfe_common.h"
+#include "orbfe_host.h"
 
 // ---------------------------------------------------------------------------------------------------
 // RCCL entry points, resolved once
@@ -83,13 +84,6 @@ Rccl &rccl()
             return ORBFE_ERR_HIP;                                                                           \
         }                                                                                                   \
     } while (0)
-
-// the calling thread's device, restored on every exit path
-struct GDeviceGuard {
-    int prev = -1;
-    GDeviceGuard() { (void)hipGetDevice(&prev); }
-    ~GDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 struct Member {  // one device of the group that THIS process drives
     int device = 0, rank = 0;
@@ -192,7 +186,7 @@ static void destroy_member(Member &m)
 extern "C" void orbfe_group_destroy(orbfe_group *g)
 {
     if (!g) return;
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     // under the copy transport every member pulls the OTHER members' slices on its own communication stream: all streams of
     // all members are drained before the first block is freed
     drain_members(g);
@@ -250,7 +244,7 @@ extern "C" orbfe_status orbfe_group_create_local_ex(const orbfe_params *p, const
     orbfe_group *g = nullptr;
     orbfe_status s = group_alloc(p, ndevices, transport, &g);
     if (s != ORBFE_OK) return s;
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     g->mem.resize((size_t)ndevices);
     std::vector<ncclComm_t> comms((size_t)ndevices, nullptr);
     std::vector<int> devs(devices, devices + ndevices);
@@ -298,7 +292,7 @@ extern "C" orbfe_status orbfe_group_create_rank(const orbfe_params *p, int32_t d
     orbfe_group *g = nullptr;
     orbfe_status s = group_alloc(p, world, ORBFE_GROUP_RCCL, &g);
     if (s != ORBFE_OK) return s;
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     if (device < 0) device = guard.prev >= 0 ? guard.prev : 0;
     g->mem.resize(1);
     Member &m = g->mem[0];
@@ -374,7 +368,7 @@ extern "C" orbfe_status orbfe_group_extract_batch(orbfe_group *g, const uint8_t 
         orbfe_set_error("bad argument to orbfe_group_extract_batch (at most %d frames)", g ? g->world * g->shard : 0);
         return ORBFE_ERR_ARG;
     }
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     orbfe_status rs = ORBFE_OK;
     for (Member &m : g->mem) {
         int lo, hi;
@@ -414,7 +408,7 @@ extern "C" orbfe_status orbfe_group_extract_shard_device(orbfe_group *g, int32_t
     int lo, hi;
     orbfe_group_shard_range(nframes_global, m.rank, g->world, &lo, &hi);
     if (hi > lo && !d_gray) { orbfe_set_error("orbfe_group_extract_shard_device: null frames"); return ORBFE_ERR_ARG; }
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     ORBFE_HIP(hipSetDevice(m.device));
     const orbfe_status s = extract_member(g, m, d_gray, hi - lo, w, ht, stride, frame_stride);
     if (s == ORBFE_OK) g->last_nframes = nframes_global;
@@ -463,7 +457,7 @@ static orbfe_status allgather_copy_enqueue(orbfe_group *g)
 extern "C" orbfe_status orbfe_group_allgather(orbfe_group *g)
 {
     if (!g) return ORBFE_ERR_ARG;
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     orbfe_status s;
     if (g->transport == ORBFE_GROUP_COPY) {
         s = allgather_copy_enqueue(g);
@@ -489,7 +483,7 @@ extern "C" orbfe_status orbfe_group_allgather(orbfe_group *g)
 extern "C" orbfe_status orbfe_group_synchronize(orbfe_group *g)
 {
     if (!g) return ORBFE_ERR_ARG;
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     for (Member &m : g->mem) {
         ORBFE_HIP(hipSetDevice(m.device));
         ORBFE_HIP(hipStreamSynchronize(m.s_cmp));
@@ -519,7 +513,7 @@ extern "C" orbfe_status orbfe_group_get_frame_from(orbfe_group *g, int32_t membe
     }
     Member &m = g->mem[(size_t)member];
     const size_t bi = (size_t)block_index(g, g->last_nframes, frame);
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     ORBFE_HIP(hipSetDevice(m.device));
     ORBFE_HIP(hipStreamSynchronize(m.s_cmp));
     ORBFE_HIP(hipStreamSynchronize(m.s_comm));
@@ -539,7 +533,7 @@ extern "C" orbfe_status orbfe_group_get_counts(orbfe_group *g, int32_t member, i
 {
     if (!g || member < 0 || member >= (int)g->mem.size() || !n_out) { orbfe_set_error("bad argument to orbfe_group_get_counts"); return ORBFE_ERR_ARG; }
     Member &m = g->mem[(size_t)member];
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     ORBFE_HIP(hipSetDevice(m.device));
     ORBFE_HIP(hipStreamSynchronize(m.s_cmp));
     ORBFE_HIP(hipStreamSynchronize(m.s_comm));
@@ -565,7 +559,7 @@ extern "C" orbfe_status orbfe_group_match(orbfe_group *g, const int32_t *qframe,
     const int nf = g->last_nframes;
     for (int p = 0; p < npairs; ++p)
         if (qframe[p] < 0 || qframe[p] >= nf || tframe[p] < 0 || tframe[p] >= nf) { orbfe_set_error("pair %d: frame out of range", p); return ORBFE_ERR_ARG; }
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     std::vector<int> owner_of((size_t)npairs, -1);
     std::vector<std::vector<int>> mine(g->mem.size());
     for (int p = 0; p < npairs; ++p) {
@@ -621,7 +615,7 @@ extern "C" orbfe_status orbfe_group_match_device(orbfe_group *g, int32_t member,
 {
     if (!g || member < 0 || member >= (int)g->mem.size()) return ORBFE_ERR_ARG;
     Member &m = g->mem[(size_t)member];
-    GDeviceGuard guard;
+    DeviceGuard guard;   // restores the calling thread's device on every exit path
     ORBFE_HIP(hipSetDevice(m.device));
     return orbfe_match_bf_frames_device(m.mat, m.d_kps, m.d_desc, m.d_n, g->cap, d_qblock, d_tblock, npairs, nnratio, th, check_ori,
                                         d_match, d_nmatches, (void *)m.s_cmp);

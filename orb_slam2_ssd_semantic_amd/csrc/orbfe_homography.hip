@@ -15,6 +15,7 @@
 #include <new>
 
 #include "orbfe_common.h"
+#include "orbfe_host.h"
 
 namespace {
 
@@ -688,19 +689,6 @@ __global__ void k_homo_kat_jacobi(int n, double *A, double *out)
     if (i < n) jacobi<N>(A + (size_t)i * N * N, out + (size_t)i * (N + N * N), out + (size_t)i * (N + N * N) + N, 1);
 }
 
-struct HDeviceGuard {
-    int prev = -1, dev = -1;
-    explicit HDeviceGuard(int d) : dev(d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~HDeviceGuard()
-    {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 
 struct orbfe_homography {
@@ -717,10 +705,7 @@ struct orbfe_homography {
 
 static void homo_free(orbfe_homography *h)
 {
-    void *ptrs[] = {h->d_src, h->d_dst, h->d_mask, h->d_off, h->d_ok, h->d_state, h->d_tap_info, h->d_H, h->d_tap_ransac, h->d_tap_refit};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    orb_free_all(h->stream, {h->d_src, h->d_dst, h->d_mask, h->d_off, h->d_ok, h->d_state, h->d_tap_info, h->d_H, h->d_tap_ransac, h->d_tap_refit});
 }
 
 extern "C" orbfe_status orbfe_homography_create(int32_t device, int32_t max_pairs, int32_t max_sets, orbfe_homography **out)
@@ -728,29 +713,21 @@ extern "C" orbfe_status orbfe_homography_create(int32_t device, int32_t max_pair
     if (!out) return ORBFE_ERR_ARG;
     *out = nullptr;
     if (max_pairs < 1 || max_sets < 1 || max_pairs > (1 << 24) || max_sets > (1 << 20)) return ORBFE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        orbfe_set_error("no HIP device visible; liborbfe has no CPU fallback");
-        return ORBFE_ERR_NODEVICE;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= ndev) { orbfe_set_error("device out of range"); return ORBFE_ERR_ARG; }
+    const orbfe_status rs = orb_resolve_device(&device);
+    if (rs != ORBFE_OK) return rs;
     orbfe_homography *h = new (std::nothrow) orbfe_homography();
     if (!h) return ORBFE_ERR_NOMEM;
-    HDeviceGuard dg(device);
+    DeviceGuard dg(device);
     h->device = device;
     h->max_pairs = max_pairs;
     h->max_sets = max_sets;
     size_t np = (size_t)max_pairs, ns = (size_t)max_sets;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc(&h->d_src, np * sizeof(float2)) == hipSuccess && hipMalloc(&h->d_dst, np * sizeof(float2)) == hipSuccess &&
-              hipMalloc(&h->d_mask, np) == hipSuccess && hipMalloc(&h->d_off, 2 * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&h->d_ok, sizeof(int32_t)) == hipSuccess && hipMalloc(&h->d_H, 9 * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->d_state, ns * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&h->d_tap_info, ns * 4 * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&h->d_tap_ransac, ns * 9 * sizeof(double)) == hipSuccess &&
-              hipMalloc(&h->d_tap_refit, ns * 9 * sizeof(double)) == hipSuccess;
+    auto blk = [](auto **p, size_t bytes) { return OrbAlloc{(void **)p, bytes}; };
+    const bool ok = orb_alloc_all(
+        &h->stream, {blk(&h->d_src, np * sizeof(float2)), blk(&h->d_dst, np * sizeof(float2)), blk(&h->d_mask, np),
+                     blk(&h->d_off, 2 * sizeof(int32_t)), blk(&h->d_ok, sizeof(int32_t)), blk(&h->d_H, 9 * sizeof(double)),
+                     blk(&h->d_state, ns * sizeof(int32_t)), blk(&h->d_tap_info, ns * 4 * sizeof(int32_t)),
+                     blk(&h->d_tap_ransac, ns * 9 * sizeof(double)), blk(&h->d_tap_refit, ns * 9 * sizeof(double))});
     if (!ok) {
         (void)hipGetLastError();
         orbfe_set_error("orbfe_homography_create: device allocation failed");
@@ -766,7 +743,7 @@ extern "C" orbfe_status orbfe_homography_create(int32_t device, int32_t max_pair
 extern "C" void orbfe_homography_destroy(orbfe_homography *h)
 {
     if (!h) return;
-    HDeviceGuard dg(h->device);
+    DeviceGuard dg(h->device);
     (void)hipStreamSynchronize(h->last_stream);
     (void)hipStreamSynchronize(h->stream);
     homo_free(h);
@@ -823,7 +800,7 @@ extern "C" orbfe_status orbfe_find_homography(orbfe_homography *h, const float *
     HoArgs a;
     orbfe_status s = homo_args(h, method, threshold, max_iters, confidence, a);
     if (s != ORBFE_OK) return s;
-    HDeviceGuard dg(h->device);
+    DeviceGuard dg(h->device);
     hipStream_t st = h->stream;
     const int32_t off[2] = {0, n};
     ORBFE_HIP(hipMemcpyAsync(h->d_off, off, sizeof(off), hipMemcpyHostToDevice, st));
@@ -860,7 +837,7 @@ extern "C" orbfe_status orbfe_find_homographies_device(orbfe_homography *h, cons
     HoArgs a;
     orbfe_status s = homo_args(h, method, threshold, max_iters, confidence, a);
     if (s != ORBFE_OK) return s;
-    HDeviceGuard dg(h->device);
+    DeviceGuard dg(h->device);
     a.off = d_offsets;
     a.src = (const float2 *)d_src_xy;
     a.dst = (const float2 *)d_dst_xy;
@@ -878,7 +855,7 @@ extern "C" orbfe_status orbfe_homography_tap(orbfe_homography *h, int32_t set, i
     size_t need = stage == ORBFE_HOMO_TAP_INFO ? 4 * sizeof(int32_t) : 9 * sizeof(double);
     if (stage < ORBFE_HOMO_TAP_RANSAC || stage > ORBFE_HOMO_TAP_REFIT) return ORBFE_ERR_ARG;
     if (cap < need) return ORBFE_ERR_CAP;
-    HDeviceGuard dg(h->device);
+    DeviceGuard dg(h->device);
     ORBFE_HIP(hipStreamSynchronize(h->last_stream));
     const void *srcp = stage == ORBFE_HOMO_TAP_RANSAC ? (const void *)(h->d_tap_ransac + (size_t)set * 9)
                      : stage == ORBFE_HOMO_TAP_INFO   ? (const void *)(h->d_tap_info + (size_t)set * 4)
@@ -891,12 +868,9 @@ extern "C" orbfe_status orbfe_homography_kat(int32_t what, int32_t n, const void
 {
     if (n < 0 || !out || (!in && n > 0) || what < ORBFE_HOMO_KAT_RNG || what > ORBFE_HOMO_KAT_JACOBI8) return ORBFE_ERR_ARG;
     if (n == 0) return ORBFE_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        orbfe_set_error("no HIP device visible; liborbfe has no CPU fallback");
-        return ORBFE_ERR_NODEVICE;
-    }
+    int32_t device = -1;   // runs on the caller's current device
+    const orbfe_status rs = orb_resolve_device(&device);
+    if (rs != ORBFE_OK) return rs;
     size_t in_b = 0, out_b = 0;
     switch (what) {
     case ORBFE_HOMO_KAT_RNG: in_b = sizeof(uint64_t); out_b = (size_t)n * 4; break;

@@ -1,0 +1,47 @@
+// orbfe_matcher.h -- the matcher handle, shared by the translation units that implement its entry points (orbfe_match.hip,
+// orbfe_grid.hip, orbfe_projection.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip.  Host only.
+#pragma once
+
+#include "orbfe_common.h"
+#include "orbfe_host.h"
+
+struct orbfe_matcher {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevBuf b[16];
+    bool own_stream = true;  // false: the stream belongs to a pipeline (orbfe_internal_matcher_create_on_stream)
+    int bf_kernel = 0;  // 0 = k_match_bf (int8 dot product on the matrix cores), 1 = k_match_popc (xor / popcount)
+    // Device entry points that use the scratch blocks b[] run on the CALLER's stream: one that arrives on another stream
+    // than its predecessor waits (at stream level) for the event recorded behind that predecessor's last launch.
+    hipStream_t scratch_stream = nullptr;
+    bool scratch_used = false;
+    hipEvent_t ev_scratch = nullptr;
+    PinBuf pin_in, pin_out;  // page-locked staging of the latency-bound per-frame calls (orbfe_search_by_projection)
+    bool proj_fused = true;   // orbfe_search_by_projection: the one-launch form (k_proj_fused); false = the four-kernel path (tests)
+    DevBuf proj_done;        // k_proj_fused's arrival counter / overflow word (zero between calls)
+    orbfe_matcher()
+    {
+        for (DevBuf &x : b) x.min_bytes = 4;
+        proj_done.min_bytes = pin_in.min_bytes = pin_out.min_bytes = 4;
+        pin_in.slack = pin_out.slack = true;
+    }
+};
+
+static inline hipError_t scratch_acquire(orbfe_matcher *m, hipStream_t st)
+{
+    if (m->scratch_used && m->scratch_stream != st) return hipStreamWaitEvent(st, m->ev_scratch, 0);
+    return hipSuccess;
+}
+static inline hipError_t scratch_release(orbfe_matcher *m, hipStream_t st)
+{
+    m->scratch_stream = st;
+    m->scratch_used = true;
+    return hipEventRecord(m->ev_scratch, st);
+}
+
+// a matcher for a pipe of orbfe_pipeline: `st` (the pipe's stream) is its own stream and stays the pipeline's
+orbfe_status orbfe_internal_matcher_create_on_stream(int32_t device, void *st, orbfe_matcher **out);
+
+// single-workgroup exclusive scan cnt[0..nq) -> off[0..nq] on `st`: k_scan_u32 lives in orbfe_grid.hip and this is its one launch
+// site, for the grid's own entry points and for orbfe_projection.hip (not exported)
+__attribute__((visibility("hidden"))) void orbfe_internal_launch_scan_u32(const uint32_t *cnt, int nq, uint32_t *off, hipStream_t st);

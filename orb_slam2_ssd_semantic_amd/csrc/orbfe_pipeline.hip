@@ -12,27 +12,12 @@
 #include <vector>
 
 #include "orbfe_common.h"
-
-// csrc/orbfe_api.hip / orbfe_match.hip: handles that live on a stream of the pipeline instead of creating their own
-orbfe_status orbfe_internal_create_on_stream(const orbfe_params *p, void *st, void *side, orbfe_handle **out);
-orbfe_status orbfe_internal_matcher_create_on_stream(int32_t device, void *st, orbfe_matcher **out);
+#include "orbfe_kernels.h"
+#include "orbfe_matcher.h"
 
 #ifndef ORBFE_PIPE_SIDE_STREAMS
 #define ORBFE_PIPE_SIDE_STREAMS 1   // side streams of a pipeline, shared by its pipes (A/B -DORBFE_PIPE_SIDE_STREAMS=n, 12 pipes: 1: 314-315 k frames/s resident and 0.91 of the PCIe link through the host entry point; 2: 312-313 k / 0.87; 4: 299-301 k; one per pipe: 310 k / 0.90)
 #endif
-
-struct PipeGuard {
-    int prev = -1, dev = -1;
-    explicit PipeGuard(int d) : dev(d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~PipeGuard()
-    {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
 
 struct orbfe_pipeline {
     orbfe_params prm;
@@ -121,7 +106,7 @@ static orbfe_status ensure_seq(orbfe_pipeline *pl, int nframes)
 extern "C" void orbfe_pipeline_destroy(orbfe_pipeline *pl)
 {
     if (!pl) return;
-    PipeGuard g(pl->device);
+    DeviceGuard g(pl->device);
     for (hipStream_t s : pl->st)
         if (s) (void)hipStreamSynchronize(s);
     for (orbfe_handle *h : pl->ext) orbfe_destroy(h);
@@ -174,22 +159,14 @@ extern "C" orbfe_status orbfe_pipeline_create(const orbfe_params *p, int32_t npi
         orbfe_pipeline_destroy(pl);
         return s;
     };
-    {   // the device the handles will resolve (p->device may be -1 = current); without a device the first create fails below
+    {   // the device the handles will use (p->device may be -1 = current)
         int dev = p->device;
-        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+        const orbfe_status rs = orb_resolve_device(&dev);
+        if (rs != ORBFE_OK) return fail(rs);
         pl->device = dev;
         pl->prm.device = dev;
     }
-    {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-            (void)hipGetLastError();
-            orbfe_set_error("no HIP device visible; liborbfe has no CPU fallback");
-            return fail(ORBFE_ERR_NODEVICE);
-        }
-        if (pl->device >= ndev) { orbfe_set_error("device %d out of range (%d visible)", pl->device, ndev); return fail(ORBFE_ERR_ARG); }
-    }
-    PipeGuard g(pl->device);
+    DeviceGuard g(pl->device);
     // One stream per pipe, shared by the pipe's extractor and matcher handles (which then create none of their own but the
     // extractor's side stream): the runtime multiplexes all streams of a process onto a few hardware queues, and every idle
     // stream less is a copy stream that does not have to share its queue with a kernel stream.
@@ -273,7 +250,7 @@ extern "C" orbfe_status orbfe_pipeline_reset_sequence(orbfe_pipeline *pl)
 extern "C" orbfe_status orbfe_pipeline_join(orbfe_pipeline *pl, void *stream)
 {
     if (!pl) return ORBFE_ERR_ARG;
-    PipeGuard g(pl->device);
+    DeviceGuard g(pl->device);
     for (int p = 0; p < pl->P; ++p) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, pl->ev_end[(size_t)p], 0));
     pl->joined = true;
     return ORBFE_OK;
@@ -282,7 +259,7 @@ extern "C" orbfe_status orbfe_pipeline_join(orbfe_pipeline *pl, void *stream)
 extern "C" orbfe_status orbfe_pipeline_synchronize(orbfe_pipeline *pl)
 {
     if (!pl) return ORBFE_ERR_ARG;
-    PipeGuard g(pl->device);
+    DeviceGuard g(pl->device);
     for (hipStream_t s : pl->st) ORBFE_HIP(hipStreamSynchronize(s));
     return ORBFE_OK;
 }
@@ -310,7 +287,7 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
         orbfe_set_error("bad argument to orbfe_pipeline_extract_match_device");
         return ORBFE_ERR_ARG;
     }
-    PipeGuard g(pl->device);
+    DeviceGuard g(pl->device);
     const int F = pl->F, P = pl->P;
     const int nsub = (nframes + F - 1) / F;
     orbfe_status s = ensure_events(pl, nsub + 1);
@@ -496,7 +473,7 @@ extern "C" orbfe_status orbfe_pipeline_extract_match(orbfe_pipeline *pl, const u
         orbfe_set_error("orbfe_pipeline_extract_match: cap %d below orbfe_pipeline_capacity() = %d", cap, pl->cap);
         return ORBFE_ERR_CAP;
     }
-    PipeGuard g(pl->device);
+    DeviceGuard g(pl->device);
     orbfe_status s = ensure_host_sets(pl, w, ht);
     if (s != ORBFE_OK) return s;
     const int F = pl->F, pc = pl->cap;

@@ -9,6 +9,8 @@ torch.distributed is plumbing: backend "nccl" is RCCL over xGMI on ROCm, "gloo" 
 import torch
 import torch.distributed as dist
 
+from ._ffi import Handle
+
 
 def shard_range(nframes, rank, world):
     """Contiguous block of frames owned by `rank`: [lo, hi). Remainder frames go to the lowest ranks."""
@@ -246,12 +248,13 @@ class OverlappedKeyframeGather:
             self.thread = None
 
 
-class KeyframeGroup:
+class KeyframeGroup(Handle):
     """ctypes mirror of the C-ABI's multi-device layer (include/orbfe.h, orbfe_group_*): the batched keyframe mode for
     C / C++ hosts -- contiguous shards, one in-place ncclAllGather (RCCL) of the padded count / keypoint / descriptor blocks,
     and the consumer of the gather (own frames against candidate frames anywhere in the batch).  `devices` = the devices
     ONE process drives (ncclCommInitAll); `rank_of_world=(rank, world, id_bytes)` = one process per device."""
 
+    _HANDLE, _LIB, _DESTROY = "handle", "L", "orbfe_group_destroy"
     RCCL, COPY = 0, 1   # transports of the exchange step (include/orbfe.h ORBFE_GROUP_RCCL / ORBFE_GROUP_COPY)
 
     def __init__(self, nfeatures, scale_factor, nlevels, ini_th, min_th, max_width, max_height, max_batch, devices=(0,),
@@ -297,17 +300,6 @@ class KeyframeGroup:
         lo, hi = C.c_int32(), C.c_int32()
         _ffi.lib().orbfe_group_shard_range(nframes, rank, world, C.byref(lo), C.byref(hi))
         return lo.value, hi.value
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.orbfe_group_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def extract_batch(self, frames):
         """frames: uint8 [n, h, w] numpy (host).  Every member extracts its shard."""

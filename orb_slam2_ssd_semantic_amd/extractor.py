@@ -10,10 +10,11 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import KP_DTYPE, OrbfeParams, check, ptr
+from ._ffi import KP_DTYPE, Handle, OrbfeParams, check, ptr
 
 
-class ORBextractor:
+class ORBextractor(Handle):
+    _DESTROY = "orbfe_destroy"
     HARRIS_SCORE, FAST_SCORE = 0, 1  # declared, unused by the reference too (include/ORBextractor.h:39)
 
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, *,
@@ -40,12 +41,6 @@ class ORBextractor:
         self.mnFeaturesPerLevel = np.zeros(nlevels, np.int32)
         check(self._L.orbfe_get_features_per_level(self._h, ptr(self.mnFeaturesPerLevel)), "features_per_level")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if self._owned:
-                self._L.orbfe_destroy(self._h)
-            self._h = None
-
     def set_option(self, name, value):
         """orbfe_set_option by name (overlap, rows, rows_fast, rows_blur, blur_pieces, blur_updown, pyr_rows, qt_threads_0..2,
         debug, and -- developer builds only -- pyr_fuse, fuse_blur_pyr, fuse_fast_pyr, fuse_fast_pyr_levels)"""
@@ -54,9 +49,6 @@ class ORBextractor:
     def last_call_reused(self):
         """True when the last __call__ was answered from the previous call's results (option reuse_identical_input)"""
         return bool(self._L.orbfe_last_call_reused(self._h))
-
-    def __del__(self):
-        self.close()
 
     # ---- getters of include/ORBextractor.h:58-78 ----
     def GetLevels(self):

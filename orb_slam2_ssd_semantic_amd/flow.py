@@ -6,12 +6,9 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from ._ffi import Handle, stream_arg, tensor_ptr
 
 TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY, TAP_WARP = range(7)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def plan(w, h):
@@ -32,27 +29,18 @@ def poly_constants():
     return g[:11], g[11:22], g[22:], tuple(float(v) for v in ig)
 
 
-class Flow:
+class Flow(Handle):
     """One FlowSLAM::Flow: its previous half-size frame lives on the device.  compute_mask() is Flow::ComputeMask on one host
     frame; compute_masks() the same over a device-resident sequence; mask_keypoints() the masked-Frame rule on the padded
     device blocks of ORBextractor.extract_batch_device-style outputs."""
+
+    _HANDLE, _DESTROY = "h", "orbfe_flow_destroy"
 
     def __init__(self, max_width=640, max_height=480, max_batch=1, device=0):
         self._L = _ffi.lib()
         self.h = C.c_void_p()
         _ffi.check(self._L.orbfe_flow_create(device, max_width, max_height, max_batch, C.byref(self.h)), "orbfe_flow_create")
         self.device = device
-
-    def close(self):
-        if self.h:
-            self._L.orbfe_flow_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def stream(self):
@@ -91,12 +79,12 @@ class Flow:
             masks = torch.empty((n, h, w), dtype=torch.uint8, device=frames.device)
         if ones is None:
             ones = torch.empty(n, dtype=torch.int32, device=frames.device)
-        st = torch.cuda.current_stream(frames.device).cuda_stream if stream is None else stream
+        st = stream_arg(frames.device, stream)
         if homographies is None:
             if use is not None:
                 raise ValueError("use without homographies")
-            _ffi.check(self._L.orbfe_flow_compute_masks_device(self.h, _ptr(frames), n, w, h, w, frames.stride(0), float(threshold),
-                                                               _ptr(masks), w, masks.stride(0), _ptr(ones), C.c_void_p(st)),
+            _ffi.check(self._L.orbfe_flow_compute_masks_device(self.h, tensor_ptr(frames), n, w, h, w, frames.stride(0), float(threshold),
+                                                               tensor_ptr(masks), w, masks.stride(0), tensor_ptr(ones), st),
                        "orbfe_flow_compute_masks_device")
             return masks, ones
         H = homographies
@@ -104,9 +92,9 @@ class Flow:
             raise ValueError("homographies must be a contiguous torch float64 [n, 3, 3] on the device")
         if use is not None and (use.dtype != torch.int32 or tuple(use.shape) != (n,) or not use.is_cuda or not use.is_contiguous()):
             raise ValueError("use must be a contiguous torch int32 [n] on the device")
-        _ffi.check(self._L.orbfe_flow_compute_masks_homo_device(self.h, _ptr(frames), n, w, h, w, frames.stride(0), _ptr(H),
-                                                                None if use is None else _ptr(use), float(threshold), _ptr(masks), w,
-                                                                masks.stride(0), _ptr(ones), C.c_void_p(st)),
+        _ffi.check(self._L.orbfe_flow_compute_masks_homo_device(self.h, tensor_ptr(frames), n, w, h, w, frames.stride(0), tensor_ptr(H),
+                                                                None if use is None else tensor_ptr(use), float(threshold), tensor_ptr(masks), w,
+                                                                masks.stride(0), tensor_ptr(ones), st),
                    "orbfe_flow_compute_masks_homo_device")
         return masks, ones
 
@@ -129,6 +117,6 @@ def mask_keypoints(masks, ones, kps, desc, n, cap, stream=None):
     (orbfe_keypoint), desc uint8 [b*cap*32], n int32 [b] -- all torch tensors on the device."""
     import torch
     b, h, w = masks.shape
-    st = torch.cuda.current_stream(masks.device).cuda_stream if stream is None else stream
-    _ffi.check(_ffi.lib().orbfe_mask_keypoints_device(_ptr(masks), w, h, w, masks.stride(0), _ptr(ones), b, _ptr(kps), _ptr(desc),
-                                                      _ptr(n), cap, C.c_void_p(st)), "orbfe_mask_keypoints_device")
+    st = stream_arg(masks.device, stream)
+    _ffi.check(_ffi.lib().orbfe_mask_keypoints_device(tensor_ptr(masks), w, h, w, masks.stride(0), tensor_ptr(ones), b, tensor_ptr(kps), tensor_ptr(desc),
+                                                      tensor_ptr(n), cap, st), "orbfe_mask_keypoints_device")

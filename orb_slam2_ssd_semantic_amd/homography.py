@@ -6,14 +6,11 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from ._ffi import Handle, stream_arg, tensor_ptr
 
 RANSAC = 8
 TAP_RANSAC, TAP_INFO, TAP_REFIT = range(3)
 KAT_RNG, KAT_HYPOT, KAT_NUMITERS, KAT_JACOBI9, KAT_JACOBI8 = range(5)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def _pairs(a, n=None):
@@ -23,9 +20,11 @@ def _pairs(a, n=None):
     return a
 
 
-class Homography:
+class Homography(Handle):
     """Device scratch for findHomography calls of at most max_pairs point pairs (host form) and batches of at most max_sets
     point sets (device form)."""
+
+    _HANDLE, _DESTROY = "h", "orbfe_homography_destroy"
 
     def __init__(self, max_pairs=4096, max_sets=64, device=0):
         self._L = _ffi.lib()
@@ -34,17 +33,6 @@ class Homography:
         self.device = device
         self.max_pairs = max_pairs
         self.max_sets = max_sets
-
-    def close(self):
-        if self.h:
-            self._L.orbfe_homography_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def stream(self):
@@ -81,10 +69,10 @@ class Homography:
             ok = torch.empty(nsets, dtype=torch.int32, device=dev)
         if mask is None:
             mask = torch.empty(max(src.shape[0], 1), dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        _ffi.check(self._L.orbfe_find_homographies_device(self.h, _ptr(offsets), _ptr(src), _ptr(dst), nsets, int(method),
+        st = stream_arg(dev, stream)
+        _ffi.check(self._L.orbfe_find_homographies_device(self.h, tensor_ptr(offsets), tensor_ptr(src), tensor_ptr(dst), nsets, int(method),
                                                           float(threshold), int(max_iters), float(confidence), int(min_pairs),
-                                                          _ptr(H), _ptr(ok), _ptr(mask), C.c_void_p(st)),
+                                                          tensor_ptr(H), tensor_ptr(ok), tensor_ptr(mask), st),
                    "orbfe_find_homographies_device")
         return H, ok, mask[:src.shape[0]]
 

@@ -12,7 +12,7 @@ import struct
 import numpy as np
 
 from . import _ffi
-from ._ffi import KP_DTYPE, check, ptr
+from ._ffi import KP_DTYPE, Handle, check, ptr
 
 ULONG_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -107,9 +107,11 @@ def load_map(path):
     return mps, kfs
 
 
-class VocabularyFile:
+class VocabularyFile(Handle):
     """ORBvoc.txt / ORBvoc.bin parsed by liborbfe.so (host only).  `arrays()` gives what ORBVocabulary(...) takes;
     `save_binary(path)` is tool/text2binary.cc's conversion."""
+
+    _HANDLE, _DESTROY = "_v", "orbfe_vocfile_free"
 
     def __init__(self, path):
         self._L = _ffi.lib()
@@ -118,14 +120,6 @@ class VocabularyFile:
         v = [C.c_int32() for _ in range(6)]
         check(self._L.orbfe_vocfile_info(self._v, *[C.byref(x) for x in v]), "orbfe_vocfile_info")
         self.k, self.L, self.nnodes, self.nwords, self.scoring, self.weighting = (x.value for x in v)
-
-    def close(self):
-        if getattr(self, "_v", None):
-            self._L.orbfe_vocfile_free(self._v)
-            self._v = None
-
-    def __del__(self):
-        self.close()
 
     @property
     def handle(self):

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import check, ptr
+from ._ffi import Handle, check, ptr
 
 
 def feature_vector_to_csr(fv):
@@ -25,7 +25,8 @@ def feature_vector_to_csr(fv):
     return node, off, np.asarray(idx, np.uint32)
 
 
-class ORBmatcher:
+class ORBmatcher(Handle):
+    _HANDLE, _DESTROY = "_m", "orbfe_matcher_destroy"
     TH_HIGH = 100      # src/ORBmatcher.cc:39
     TH_LOW = 50        # src/ORBmatcher.cc:40
     HISTO_LENGTH = 30  # src/ORBmatcher.cc:41
@@ -40,15 +41,6 @@ class ORBmatcher:
             check(self._L.orbfe_matcher_create(device, C.byref(self._m)), "orbfe_matcher_create")
         self.mfNNratio = float(nnratio)
         self.mbCheckOrientation = bool(checkOri)
-
-    def close(self):
-        if getattr(self, "_m", None):
-            if self._owned:
-                self._L.orbfe_matcher_destroy(self._m)
-            self._m = None
-
-    def __del__(self):
-        self.close()
 
     @property
     def handle(self):
@@ -343,12 +335,14 @@ class FrameGrid:
         return cand
 
 
-class ORBVocabulary:
+class ORBVocabulary(Handle):
     """DBoW2 vocabulary tree on the device (reference include/ORBVocabulary.h).
 
     `ORBVocabulary(matcher, child_off, child_idx, node_desc, word_id, weight, L)`; `transform(descriptors, levelsup=4)`
     mirrors `mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)` (src/Frame.cc:553) and returns
     (BowVector as (ids, values), FeatureVector as the (node, off, idx) CSR `ORBmatcher.SearchByBoW` takes)."""
+
+    _HANDLE, _DESTROY = "_v", "orbfe_vocabulary_destroy"
 
     def __init__(self, matcher, child_off, child_idx, node_desc, word_id, weight, L, device=-1):
         self._mt = matcher
@@ -361,14 +355,6 @@ class ORBVocabulary:
         ww = np.ascontiguousarray(weight, np.float64)
         check(self._L.orbfe_vocabulary_create(device, len(nd), ptr(co), ptr(ci), ptr(nd), ptr(wi), ptr(ww), int(L),
                                               C.byref(self._v)), "orbfe_vocabulary_create")
-
-    def close(self):
-        if getattr(self, "_v", None):
-            self._L.orbfe_vocabulary_destroy(self._v)
-            self._v = None
-
-    def __del__(self):
-        self.close()
 
     @property
     def handle(self):

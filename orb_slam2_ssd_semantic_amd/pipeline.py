@@ -5,12 +5,13 @@ plumbing only."""
 import ctypes as C
 
 from . import _ffi
-from ._ffi import OrbfeParams, check
+from ._ffi import Handle, OrbfeParams, check
 from .extractor import ORBextractor
 from .matcher import ORBmatcher
 
 
-class FramePipeline:
+class FramePipeline(Handle):
+    _HANDLE, _DESTROY = "_p", "orbfe_pipeline_destroy"
     CONTINUE, NO_JOIN = _ffi.PIPE_CONTINUE, _ffi.PIPE_NO_JOIN
 
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, *, max_width=640, max_height=480,
@@ -30,13 +31,9 @@ class FramePipeline:
 
     def close(self):
         if getattr(self, "_p", None):
-            for o in self.extractors + self.matchers:
+            for o in self.extractors + self.matchers:   # the wrappers of the pipes' handles, which the pipeline owns
                 o.close()
-            self._L.orbfe_pipeline_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        self.close()
+        super().close()
 
     @property
     def handle(self):

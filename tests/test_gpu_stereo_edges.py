@@ -1,6 +1,6 @@
 """Frame::ComputeStereoMatches (reference src/Frame.cc:642-846) at the shapes and branches the 640 x 480 suite never reaches.
 
-k_stereo_match + k_stereo_filter (csrc/orbfe_match.hip) against oracle.stereo_matches, uRight / depth bit patterns:
+k_stereo_match + k_stereo_filter (csrc/orbfe_stereo.hip) against oracle.stereo_matches, uRight / depth bit patterns:
   * more than 1024 left keypoints, so the one-workgroup filter runs its second stride and the median can sit past index 1023;
   * widths that are not multiples of 4, scale factors 1.1 / 1.5, 4 and 12 levels (both extractors share the settings);
   * maxD inside the disparity range (disparity >= maxD drops), a noise-free pair (most level-0 matches have SAD 0: over a
