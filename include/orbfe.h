@@ -921,6 +921,106 @@ orbfe_status orbfe_depth_to_float_device(const void *d_src, int32_t depth_format
                                          size_t src_stride, size_t src_frame_stride, float scale, float *d_dst, size_t dst_stride,
                                          size_t dst_frame_stride, void *stream);
 
+/* ---- Sim3Solver's RANSAC (csrc/orbfe_sim3.hip) ----------------------------------------------------------
+ * The reference's Sim3Solver (src/Sim3Solver.cc): Horn's closed form on three correspondences inside the RANSAC loop of
+ * `iterate`, the step of LoopClosing::ComputeSim3 between SearchByBoW and SearchBySim3.  The inputs are the constructor's
+ * quantities of the N correspondences: camera-frame points X1[i] = Rcw1 * Xw1 + tcw1 and X2[i] (orbfe_sim3_prepare_device
+ * computes them), the two level sigma^2 values (the threshold is (size_t)(9.210 * sigma2), truncated as in the reference) and
+ * the two cameras as K = (fx, fy, cx, cy).  The random draws are an INPUT: 3 * n_iterations raw values r in [0, 2^31 - 1] (bit 31
+ * is ignored), each used as DUtils' RandomInt(0, size - 1) = (int)(((double)r / 2147483648.0) * size); with r = rand() the
+ * stream is the reference's.  A call consumes three draws per iteration it ran (result.iterations_run); a caller that wants the
+ * reference's exact stream keeps the rest.  Bit-exact against the canonical mode of tests/sim3_oracle.py (an unpinned
+ * restatement); atan2 / sin / cos are fixed fp64 operation sequences, not a C library's. */
+typedef struct orbfe_sim3_model {
+    float T12[16];     /* row-major 4x4 [s*R t; 0 0 0 1] */
+    float R[9];        /* GetEstimatedRotation */
+    float t[3];        /* GetEstimatedTranslation */
+    float s;           /* GetEstimatedScale */
+    float reserved[3];
+} orbfe_sim3_model;
+typedef struct orbfe_sim3_state {   /* what a solver carries from one iterate call to the next; all zero = a new solver */
+    int32_t iterations;             /* mnIterations (SetRansacParameters sets it to 0) */
+    int32_t best_inliers;           /* mnBestInliers */
+    int32_t reserved[2];
+    orbfe_sim3_model best;          /* mBestT12 / mBestRotation / mBestTranslation / mBestScale */
+} orbfe_sim3_state;
+typedef struct orbfe_sim3_result {
+    int32_t found;                  /* iterate returned a model: n_inliers > min_inliers at an iteration whose count reached the best */
+    int32_t no_more;                /* bNoMore */
+    int32_t n_inliers;              /* nInliers (0 unless found) */
+    int32_t iterations_run;         /* iterations of this call */
+    orbfe_sim3_model model;         /* T12: the returned matrix, all zeros unless found; R, t, s: the getters (the best so far) */
+} orbfe_sim3_result;
+typedef struct orbfe_sim3_set {     /* one set of the batched form */
+    float K1[4], K2[4];             /* fx, fy, cx, cy of keyframe 1 and 2 */
+    int32_t fix_scale;              /* mbFixScale: scale 1 (stereo / RGB-D) */
+    int32_t min_inliers;            /* mRansacMinInliers */
+    int32_t max_its;                /* mRansacMaxIts, already clamped (orbfe_sim3_ransac_iterations) */
+    int32_t n_iterations;           /* iterate's nIterations */
+    int32_t draws_offset;           /* the set's 3 * n_iterations draws start here in d_draws */
+    int32_t key_offset, n_keys;     /* the set's slice of d_key_mask: mN1 bytes (d_idx1 form) */
+    int32_t reserved;
+} orbfe_sim3_set;
+typedef struct orbfe_sim3_iter {    /* tap record of one iteration run */
+    int32_t triple[3];
+    int32_t n_inliers;
+    float T12[16];
+} orbfe_sim3_iter;
+typedef struct orbfe_sim3 orbfe_sim3;   /* device scratch for one host call, test taps, own stream */
+orbfe_status orbfe_sim3_create(int32_t device, int32_t max_pairs, int32_t max_sets, orbfe_sim3 **out);
+void orbfe_sim3_destroy(orbfe_sim3 *h);
+void *orbfe_sim3_get_stream(orbfe_sim3 *h);
+/* SetRansacParameters' iteration clamp, host only (the host's libm): 1 when min_inliers == n, else
+ * ceil(log(1 - p) / log(1 - pow((float)min_inliers / n, 3))), then max(1, min(that, max_its)).  1 for n < min_inliers. */
+int32_t orbfe_sim3_ransac_iterations(double probability, int32_t min_inliers, int32_t max_its, int32_t n);
+/* One solver's iterate(n_iterations): HOST arrays in and out, synchronous.  X1 / X2 [n][3], sigma2_1 / sigma2_2 [n], draws
+ * [3 * n_iterations].  state and best_mask [n] (mvbBestInliers) are in / out: zeroed they are a new solver.  mask [n] (may be NULL):
+ * the inliers over the n correspondences when found, else zeros.  n < min_inliers (or n < 3, undefined in the reference): no
+ * model, no_more = 1.  n > max_pairs, n_iterations < 0 or past 2^20, negative counters: ORBFE_ERR_ARG, nothing is launched. */
+orbfe_status orbfe_sim3_iterate(orbfe_sim3 *h, const float *X1, const float *X2, const float *sigma2_1, const float *sigma2_2,
+                                int32_t n, const float *K1, const float *K2, int32_t fix_scale, int32_t min_inliers, int32_t max_its,
+                                int32_t n_iterations, const int32_t *draws, orbfe_sim3_state *state, uint8_t *best_mask,
+                                orbfe_sim3_result *result, uint8_t *mask);
+/* Batched form, DEVICE buffers: the solvers of one ComputeSim3 round in one launch.  Set i holds correspondences [d_offsets[i],
+ * d_offsets[i+1]) of d_X1 / d_X2 / d_sigma2_* (CSR); its masks go to the same range of d_best_mask (in / out) and d_mask; its
+ * parameters are d_sets[i], its state d_state[i] (in / out), its result d_result[i].  A set with n_i > max_pairs gets found = 0,
+ * no_more = 1, n_inliers = 0 and iterations_run = 0 in d_result[i] and nothing else of it is written (state, masks, model).
+ * d_idx1 (optional, together with d_key_mask; CSR like the points): mvnIndices1, the keypoint index in keyframe 1 of every
+ * correspondence.  The set's n_keys bytes of d_key_mask at key_offset are then iterate's vbInliers: zeroed, and on a return
+ * d_key_mask[key_offset + d_idx1[j]] = 1 for every inlier j (an index outside [0, n_keys) is skipped), which lines up with the
+ * vpMatched12 SearchBySim3 takes.  Enqueued on `stream` (NULL = HIP's default stream), no synchronisation; the handle's taps
+ * are overwritten. */
+orbfe_status orbfe_sim3_iterate_device(orbfe_sim3 *h, const int32_t *d_offsets, const float *d_X1, const float *d_X2,
+                                       const float *d_sigma2_1, const float *d_sigma2_2, const orbfe_sim3_set *d_sets,
+                                       const int32_t *d_draws, int32_t nsets, orbfe_sim3_state *d_state, uint8_t *d_best_mask,
+                                       orbfe_sim3_result *d_result, uint8_t *d_mask, const int32_t *d_idx1, uint8_t *d_key_mask,
+                                       void *stream);
+/* The constructor's mvX3Dc1 / mvX3Dc2 on DEVICE buffers: d_X1[i] = Rcw1 * d_world1[i] + tcw1 and likewise for keyframe 2, n map
+ * point pairs; the poses are HOST arrays (row-major 3x3, 3).  Enqueued on `stream`, no synchronisation. */
+orbfe_status orbfe_sim3_prepare_device(orbfe_sim3 *h, const float *d_world1, const float *d_world2, int32_t n, const float *Rcw1,
+                                       const float *tcw1, const float *Rcw2, const float *tcw2, float *d_X1, float *d_X2, void *stream);
+/* Test taps of set `set` of the last call (synchronises the handle's last stream).  A handle holds and writes no taps until
+ * orbfe_sim3_set_tap_iteration is first called on it (that call allocates them; ORBFE_ERR_NOMEM if it cannot); from then on every
+ * call records them for its first ORBFE_SIM3_TAP_SETS sets:
+ *   0 ORBFE_SIM3_TAP_ITERATIONS  one orbfe_sim3_iter per iteration run (the first ORBFE_SIM3_TAP_ITERS of them); *count = records
+ *   1 ORBFE_SIM3_TAP_ERRORS      err1 / err2 of CheckInliers, float [n][2], of the iteration (counted within the call) chosen
+ *                                with orbfe_sim3_set_tap_iteration BEFORE the call (default 0); *count = n.  ORBFE_ERR_STATE
+ *                                when the call did not run that iteration.
+ * ORBFE_ERR_STATE for a set the taps of the last call do not cover (every set, on a handle whose taps were never asked for). */
+#define ORBFE_SIM3_TAP_SETS 32
+#define ORBFE_SIM3_TAP_ITERS 512
+enum { ORBFE_SIM3_TAP_ITERATIONS = 0, ORBFE_SIM3_TAP_ERRORS = 1 };
+orbfe_status orbfe_sim3_set_tap_iteration(orbfe_sim3 *h, int32_t iteration);
+orbfe_status orbfe_sim3_tap(orbfe_sim3 *h, int32_t set, int32_t stage, void *dst, size_t cap, int32_t *count);
+/* Known-answer runs of the device primitives on HOST arrays (synchronous, current device):
+ *   0 ORBFE_SIM3_KAT_JACOBI4   in: n 4x4 floats; out: n x (4 eigenvalues, 4x4 eigenvector rows) of JacobiImpl_<float>
+ *   1 ORBFE_SIM3_KAT_ATAN2     in: n (y, x) doubles; out: n doubles of the canonical atan2
+ *   2 ORBFE_SIM3_KAT_SIN       in: n doubles; out: n doubles of the canonical sin
+ *   3 ORBFE_SIM3_KAT_COS       likewise, cos
+ *   4 ORBFE_SIM3_KAT_ROTATION  in: n 4x4 float N matrices; out: n 3x3 float rotations (eigen, angle-axis, Rodrigues) */
+enum { ORBFE_SIM3_KAT_JACOBI4 = 0, ORBFE_SIM3_KAT_ATAN2 = 1, ORBFE_SIM3_KAT_SIN = 2, ORBFE_SIM3_KAT_COS = 3, ORBFE_SIM3_KAT_ROTATION = 4 };
+orbfe_status orbfe_sim3_kat(int32_t what, int32_t n, const void *in, void *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,8 @@ SYMBOLS = (
     "orbfe_homography_create", "orbfe_homography_destroy", "orbfe_homography_get_stream", "orbfe_find_homography",
     "orbfe_find_homographies_device", "orbfe_homography_tap", "orbfe_homography_kat",
     "orbfe_undistort_points", "orbfe_image_bounds", "orbfe_frame_geometry_batch_device", "orbfe_depth_to_float_device",
+    "orbfe_sim3_create", "orbfe_sim3_destroy", "orbfe_sim3_get_stream", "orbfe_sim3_ransac_iterations", "orbfe_sim3_iterate",
+    "orbfe_sim3_iterate_device", "orbfe_sim3_prepare_device", "orbfe_sim3_set_tap_iteration", "orbfe_sim3_tap", "orbfe_sim3_kat",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -307,6 +309,19 @@ def _configure(L):
     L.orbfe_find_homographies_device.argtypes = [vp, vp, vp, vp, i32, i32, f64, i32, f64, i32, vp, vp, vp, vp]
     L.orbfe_homography_tap.argtypes = [vp, i32, i32, vp, sz]
     L.orbfe_homography_kat.argtypes = [i32, i32, vp, vp]
+    L.orbfe_sim3_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.orbfe_sim3_destroy.argtypes = [vp]
+    L.orbfe_sim3_destroy.restype = None
+    L.orbfe_sim3_get_stream.argtypes = [vp]
+    L.orbfe_sim3_get_stream.restype = vp
+    L.orbfe_sim3_ransac_iterations.argtypes = [f64, i32, i32, i32]
+    L.orbfe_sim3_ransac_iterations.restype = i32
+    L.orbfe_sim3_iterate.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.orbfe_sim3_iterate_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_sim3_prepare_device.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_sim3_set_tap_iteration.argtypes = [vp, i32]
+    L.orbfe_sim3_tap.argtypes = [vp, i32, i32, vp, sz, vp]
+    L.orbfe_sim3_kat.argtypes = [i32, i32, vp, vp]
     cam = C.POINTER(OrbfeCamera)
     L.orbfe_undistort_points.argtypes = [vp, vp, i32, cam, vp]
     L.orbfe_image_bounds.argtypes = [cam, i32, i32, vp]

@@ -16,6 +16,7 @@
 
 #include "orbfe_common.h"
 #include "orbfe_host.h"
+#include "orbfe_jacobi.h"
 
 namespace {
 
@@ -34,107 +35,7 @@ __host__ __device__ inline uint32_t rng_next(uint64_t &s)
     return (uint32_t)s;
 }
 
-// lapack.cpp's hypot template (oracle H3)
-__device__ inline double cv_hypot(double a, double b)
-{
-    a = fabs(a);
-    b = fabs(b);
-    if (a > b) {
-        b /= a;
-        return a * sqrt(1 + b * b);
-    }
-    if (b > 0) {
-        a /= b;
-        return b * sqrt(1 + a * a);
-    }
-    return 0;
-}
-
-// JacobiImpl_ on an N x N symmetric matrix whose element e lives at A[e * st] (V likewise); W[k * st] eigenvalues, descending
-template <int N>
-__device__ void jacobi(double *A, double *W, double *V, int st)
-{
-    int indR[N], indC[N];
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++) V[(i * N + j) * st] = i == j ? 1. : 0.;
-    auto row_max = [&](int k) {
-        int m = k + 1;
-        double mv = fabs(A[(N * k + m) * st]);
-        for (int i = k + 2; i < N; i++) {
-            double val = fabs(A[(N * k + i) * st]);
-            if (mv < val) mv = val, m = i;
-        }
-        indR[k] = m;
-    };
-    auto col_max = [&](int k) {
-        int m = 0;
-        double mv = fabs(A[k * st]);
-        for (int i = 1; i < k; i++) {
-            double val = fabs(A[(N * i + k) * st]);
-            if (mv < val) mv = val, m = i;
-        }
-        indC[k] = m;
-    };
-    for (int k = 0; k < N; k++) {
-        W[k * st] = A[(N + 1) * k * st];
-        if (k < N - 1) row_max(k);
-        if (k > 0) col_max(k);
-    }
-    for (int iters = 0; iters < N * N * 30; iters++) {
-        int k = 0;
-        double mv = fabs(A[indR[0] * st]);
-        for (int i = 1; i < N - 1; i++) {
-            double val = fabs(A[(N * i + indR[i]) * st]);
-            if (mv < val) mv = val, k = i;
-        }
-        int l = indR[k];
-        for (int i = 1; i < N; i++) {
-            double val = fabs(A[(N * indC[i] + i) * st]);
-            if (mv < val) mv = val, k = indC[i], l = i;
-        }
-        double p = A[(N * k + l) * st];
-        if (fabs(p) <= DBL_EPSILON) break;
-        double y = (W[l * st] - W[k * st]) * 0.5;
-        double t = fabs(y) + cv_hypot(p, y);
-        double s = cv_hypot(p, t);
-        double c = t / s;
-        s = p / s;
-        t = (p / t) * p;
-        if (y < 0) s = -s, t = -t;
-        A[(N * k + l) * st] = 0;
-        W[k * st] -= t;
-        W[l * st] += t;
-        auto rot = [&](double *M, int i0, int i1) {
-            double a0 = M[i0 * st], b0 = M[i1 * st];
-            M[i0 * st] = a0 * c - b0 * s;
-            M[i1 * st] = a0 * s + b0 * c;
-        };
-        for (int i = 0; i < k; i++) rot(A, N * i + k, N * i + l);
-        for (int i = k + 1; i < l; i++) rot(A, N * k + i, N * i + l);
-        for (int i = l + 1; i < N; i++) rot(A, N * k + i, N * l + i);
-        for (int i = 0; i < N; i++) rot(V, N * k + i, N * l + i);
-        for (int j = 0; j < 2; j++) {
-            int idx = j == 0 ? k : l;
-            if (idx < N - 1) row_max(idx);
-            if (idx > 0) col_max(idx);
-        }
-    }
-    for (int k = 0; k < N - 1; k++) {
-        int m = k;
-        for (int i = k + 1; i < N; i++)
-            if (W[m * st] < W[i * st]) m = i;
-        if (k != m) {
-            double tw = W[m * st];
-            W[m * st] = W[k * st];
-            W[k * st] = tw;
-            for (int i = 0; i < N; i++) {
-                double tv = V[(N * m + i) * st];
-                V[(N * m + i) * st] = V[(N * k + i) * st];
-                V[(N * k + i) * st] = tv;
-            }
-        }
-    }
-}
+// cv_hypot and jacobi<N> (lapack.cpp's hypot template and JacobiImpl_, oracle H3 / H8): orbfe_jacobi.h
 
 __device__ inline int update_num_iters(double p, double ep, int model_points, int max_iters)
 {
