@@ -1,5 +1,5 @@
 // orbfe_api.hip -- host side of the extractor C-ABI (include/orbfe.h): constructor tables, per-size plan,
-// device buffers, stream/event plumbing.  All pixel work happens in orbfe_kernels.hip; there is no CPU path.
+// device buffers, stream/event plumbing.  All pixel work happens in the kernel files (one per stage: orbfe_kernels.h); there is no CPU path.
 //
 // Reference behaviour restated here (paths relative to /root/reference):
 //   constructor tables            src/ORBextractor.cc:399-466

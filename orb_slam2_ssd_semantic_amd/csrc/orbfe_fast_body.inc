@@ -1,7 +1,21 @@
-// orbfe_fast_body.inc -- the body of the FAST pass of one wave (K2, see orbfe_kernels.hip), included TEXTUALLY by k_fast_map and
-// k_fast_pyr so that both compile it in their own context (a shared __device__ function changed k_fast_map's register allocation:
-// +1 % instructions).  Expects in scope: SPARSE, plan, fs, lanes, skeys, scount, cflags, cf_words, fstat, s_buf, s_cf and the
-// wave-uniform t (index of the wave in the lane list), b (frame), lane, wv.
+// orbfe_fast_body.inc -- the body of the dense FAST pass of one wave (K2, see orbfe_fast.hip), included TEXTUALLY by k_fast_map,
+// k_fast_map_u and k_fast_pyr so that each compiles it in its own context (a shared __device__ function changed k_fast_map's
+// register allocation: +1 % instructions).  Expects in scope: SPARSE, CELLROWS (constexpr bool, below), plan, fs, lanes, skeys,
+// scount, cflags, cf_words, fstat, s_buf, s_cf and the wave-uniform t (index of the wave in the lane list), b (frame), lane, wv.
+//
+// CELLROWS = false is the generic form: any run of rows per lane.  CELLROWS = true is the CELL-ROW form:
+// the reference runs cv::FAST once per 30-px cell (src/ORBextractor.cc:798-838): a corner's 3x3 suppression never looks across a
+// cell boundary.  A wave of this form walks whole CELL ROWS: every lane is a 4-pixel column of a run of rows [ys, ys + nrows) that
+// starts on a cell-row boundary and ends on one (or at the end of the detectable interior), and all runs of a wave have the same
+// length: the lanes are at the same position inside their runs in every step.  Consequences, against the generic form:
+//   * no strength row outside the run is ever needed (the row above its first row and the row below its last row count as zero):
+//     nrows strength rows instead of nrows + 2, nrows + 7 steps instead of nrows + 8;
+//   * everything that depends on the row only is the same in every lane and lives in SCALAR registers: the row's address (buffer
+//     addressing: resource = the level, the lane's first row and column as its offset, the step's row as the scalar offset), the row's position in its cell (up / down
+//     neighbours valid), the row part of the candidate order key `ord` and of the key's y coordinate, the loop bounds; every row
+//     of the run is a detectable row, so the threshold needs no per-row validity select.
+// Per row step that is ~20 vector instructions fewer of ~214, and 2 arc evaluations fewer per run.
+// Only the places that differ branch on CELLROWS; FM_LDS_CONSTS (orbfe_fast_colmask.inc) is an A/B path of the generic form.
     uint32_t *lflag = s_cf + wv * cf_words;
     for (int i = lane; i < cf_words; i += 64) lflag[i] = 0u;  // wave-private: its own DS operations execute in order
     // Work is described per LANE: a 4-pixel column, a run of rows, "halo" (contributes neighbour strengths only).
@@ -23,82 +37,46 @@
     const int ix0 = ORBFE_EDGE, iy0 = ORBFE_EDGE, ix1 = L.ix1, iy1 = L.iy1;
     const int wcell = L.wcell, hcell = L.hcell;
     const int x = ld.x;                 // first pixel of this lane (16 <= x < ix1: the 12-byte row window is in the image)
+    // the run of rows [ys, ys + nrows): every lane's run starts on a cell row and all runs of a wave have the same length (the host
+    // packs it so; dead and halo lanes carry copies), so the POSITION INSIDE THE RUN is the same in every lane -- the first row
+    // itself is a per-lane constant that only enters the lane's address, key and order constants
     const int ys = ld.ys;
-    int nsteps = ld.nrows;
+    int nrows = ld.nrows;               // rows the wave walks: the common run length / the longest run of its lanes
+    if (!CELLROWS) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nsteps = max(nsteps, __shfl_xor(nsteps, o, 64));
-    nsteps = __builtin_amdgcn_readfirstlane(nsteps) + 8;  // wave-uniform, and the compiler knows it
+        for (int o = 32; o > 0; o >>= 1) nrows = max(nrows, __shfl_xor(nrows, o, 64));
+    }
+    nrows = __builtin_amdgcn_readfirstlane(nrows);  // wave-uniform, and the compiler knows it
+    // generic: pixel rows ys - 4 .. , the last suppression in step nrows + 7
+    // cell rows: pixel rows ys - 3 .. ys + nrows + 2 in steps 0 .. nrows + 5, the last suppression in step nrows + 6
+    const int nsteps = nrows + (CELLROWS ? 7 : 8);
     const int tz = max(plan->min_th, 1);
 
-    // per-lane column masks: bit j = pixel j inside the interior / has a valid left / right neighbour in its cell
-    // (cell column, x in cell) of the lane's four pixels from ONE division: pixel j + 1 is one step to the right of pixel j
-    // (columns left of the interior count as its first column, as `ord` below wants them)
-    int ccj[4], mj[4];
-    {
-        const int r0 = max(x - ix0, 0);
-        int c = r0 / wcell, m = r0 - c * wcell;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j > 0 && x + j - ix0 >= 1) {
-                ++m;
-                if (m == wcell) { m = 0; ++c; }
-            }
-            ccj[j] = c;
-            mj[j] = m;
-        }
-    }
-    int inside = 0, lvalid = 0, rvalid = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int xx = x + j;
-        if (xx >= ix0 && xx < ix1) {
-            const int m = mj[j];
-            inside |= 1 << j;
-            if (m != 0) lvalid |= 1 << j;
-            if (m != wcell - 1 && xx + 1 < ix1) rvalid |= 1 << j;
-        }
-    }
-    auto halves = [](int bits, int j) -> uint32_t {
-        return (((bits >> j) & 1) ? 0xFFFFu : 0u) | (((bits >> (j + 1)) & 1) ? 0xFFFF0000u : 0u);
-    };
-#ifdef FM_LDS_CONSTS
-    s_lcm[wv][lane] = make_uint4(halves(inside, 0), halves(inside, 2), halves(lvalid, 0), halves(lvalid, 2));
-    s_lcr[wv][lane] = make_uint2(halves(rvalid, 0), halves(rvalid, 2));
-    // the address is laundered through an empty asm at every use, so the loads stay where they are written (a loop-invariant
-    // load would be hoisted back into registers)
-    uint32_t lc_m = (uint32_t)(uintptr_t)&s_lcm[wv][lane], lc_r = (uint32_t)(uintptr_t)&s_lcr[wv][lane], lc_o = (uint32_t)(uintptr_t)&s_lco[wv][lane];
-    typedef uint32_t fm_v4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t fm_v2 __attribute__((ext_vector_type(2)));
-#define FM_LC_LOAD(type, addr) ({ asm volatile("" : "+v"(addr)); *(const __attribute__((address_space(3))) type *)(uintptr_t)(addr); })
-#else
-    const uint32_t in01 = halves(inside, 0), in23 = halves(inside, 2);
-    const uint32_t lv01 = halves(lvalid, 0), lv23 = halves(lvalid, 2);
-    const uint32_t rv01 = halves(rvalid, 0), rv23 = halves(rvalid, 2);
-#endif
-    // a cell seam between the two pixels of a pair lets BOTH be NMS survivors; at most one pair of a lane has one
-    const bool split01 = (inside & 3) == 3 && !(lvalid & 2), split23 = (inside & 12) == 12 && !(lvalid & 8);
-    const bool wave_split = orb_ballot(split01 || split23) != 0ull;
-    const bool out_lane = !(ld.flags & 1) && inside != 0;
-    const int nrows_out = out_lane ? (int)ld.nrows : 0;
+#include "orbfe_fast_colmask.inc"
+    const int nrows_out = !CELLROWS && out_lane ? (int)ld.nrows : 0;   // generic: rows of the run the lane emits
+    const unsigned long long bout = CELLROWS ? orb_ballot(out_lane) : 0ull;   // cell rows: lanes that emit (halo and dead lanes compute, never output)
     // per-pixel part of `ord`, the rank key of the reference's candidate order (cell-row-major, raster inside a cell):
     // ord = (cell_row * ncc + cell_col) << 12 | y_in_cell << 6 | x_in_cell
+    // (cell rows: the cell row the lane's run starts in is part of the per-lane constant, what the rows walked add is scalar)
     uint32_t ordx[4];
+    {
+        const uint32_t row_part = CELLROWS ? (uint32_t)(((ys - iy0) / hcell) * L.ncc) << 12 : 0u;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        ordx[j] = ((uint32_t)ccj[j] << 12) | (uint32_t)mj[j];
+        for (int j = 0; j < 4; ++j) ordx[j] = row_part + (((uint32_t)ccj[j] << 12) | (uint32_t)mj[j]);
     }
 #ifdef FM_LDS_CONSTS
     s_lco[wv][lane] = make_uint4(ordx[0], ordx[1], ordx[2], ordx[3]);
 #endif
-    int rmod = (ys - iy0) % hcell;                                  // y_in_cell of the next NMS row (per lane)
-    uint32_t ordy = ((uint32_t)(((ys - iy0) / hcell) * L.ncc) << 12) | ((uint32_t)rmod << 6);
+    int rmod = CELLROWS ? 0 : (ys - iy0) % hcell;                   // y_in_cell of the next NMS row (per lane; cell rows: runs start on a cell row)
+    uint32_t ordy = CELLROWS ? 0u : ((uint32_t)(((ys - iy0) / hcell) * L.ncc) << 12) | ((uint32_t)rmod << 6);
     const uint32_t ord_wrap = ((uint32_t)L.ncc << 12) - ((uint32_t)hcell << 6);  // added when a new cell row starts
     const uint32_t tzz = (uint32_t)tz * 0x00010001u;
     const uint32_t resp0 = (uint32_t)(tz - 1);
     const int ysrel = ys - 7 - iy0;                                 // strength row of step s, relative to iy0, minus s
     const uint32_t hrange = (uint32_t)(iy1 - iy0);
-    // key of pixel 0 in the NMS row of step 0 (detection-window coordinates = level - 16, reference :831-832)
-    const uint32_t key00 = (uint32_t)(x - ORBFE_MINB) + ((uint32_t)(ys - 8 - ORBFE_MINB) << 12);
+    // key of pixel 0 in the NMS row of step 0 (detection-window coordinates = level - 16, reference :831-832): the row of step s
+    // is ys - 8 + s, cell rows ys - 7 + s
+    const uint32_t key00 = (uint32_t)(x - ORBFE_MINB) + ((uint32_t)(ys - (CELLROWS ? 7 : 8) - ORBFE_MINB) << 12);
 
     // 8-slot ring of unpacked rows (7 live), statically indexed under the 8-fold unroll; the raw row of the next step is
     // fetched one step ahead into one of two 12-byte buffers
@@ -110,12 +88,24 @@
 #pragma unroll
         for (int i = 0; i < FM_NE; ++i) R[k][i] = 0u;
     }
+    // generic: per-lane addresses (lanes past their run re-read a valid row).  Cell rows: buffer addressing, the step's row is a
+    // scalar offset; rows ys - 3 .. ys + nrows + 4 all lie inside the level.
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, -1, 0x00020000);
+    const int voff = (ys - 3) * pitch + x - 4;
+    typedef uint32_t fmu_v3 __attribute__((ext_vector_type(3)));
     auto fetch = [&](int s, uint32_t (&dst3)[3]) {
-        const int r = ys - 4 + s;  // image row of step s (lanes past their run re-read a valid row)
-        const uint8_t *row = src + (__umul24((uint32_t)min(r, H - 1), (uint32_t)pitch) + (uint32_t)x);
-        dst3[0] = *(const uint32_t *)(row - 4);
-        dst3[1] = *(const uint32_t *)(row);
-        dst3[2] = *(const uint32_t *)(row + 4);
+        if constexpr (CELLROWS) {   // (constexpr: the lambda captures what its live branch names, nothing of the other form)
+            const fmu_v3 w = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, s * pitch, 0);   // the step's row: a scalar offset
+            dst3[0] = w.x;
+            dst3[1] = w.y;
+            dst3[2] = w.z;
+        } else {
+            const int r = ys - 4 + s;  // image row of step s (lanes past their run re-read a valid row)
+            const uint8_t *row = src + (__umul24((uint32_t)min(r, H - 1), (uint32_t)pitch) + (uint32_t)x);
+            dst3[0] = *(const uint32_t *)(row - 4);
+            dst3[1] = *(const uint32_t *)(row);
+            dst3[2] = *(const uint32_t *)(row + 4);
+        }
     };
     fetch(0, Raw[0]);
 
@@ -124,11 +114,14 @@
         for (int k = 0; k < 8; ++k) {
             const int s = s0 + k;
             if (s >= nsteps) break;    // wave-uniform
+            const bool have_row = !CELLROWS || s < nrows + 6;   // cell rows, scalar: the last step only suppresses
+            // (fetch and unpack are unconditional -- a conditional load is waited for where the branches join, i.e. at once; the rows
+            // past the run that the last two steps read, ys + nrows + 3 and + 4, still lie inside the level: iy1 + 4 <= h - 15)
             fetch(s + 1, Raw[(k + 1) % 2]);
             fast_unpack_row(Raw[k % 2], R[k]);
             if (s < 6) continue;
             // ---- strength row rc = r - 3 (newest ring slot k is row rc+3, slot (k+2)%8 is row rc-3) ----
-            {
+            if (have_row) {
                 const uint32_t(&rm3)[FM_NE] = R[(k + 2) % 8];
                 const uint32_t(&rm2)[FM_NE] = R[(k + 3) % 8];
                 const uint32_t(&rm1)[FM_NE] = R[(k + 4) % 8];
@@ -136,8 +129,8 @@
                 const uint32_t(&rp1)[FM_NE] = R[(k + 6) % 8];
                 const uint32_t(&rp2)[FM_NE] = R[(k + 7) % 8];
                 const uint32_t(&rp3)[FM_NE] = R[k];
-                const bool rowok = (uint32_t)(ysrel + s) < hrange;  // iy0 <= rc < iy1
-                const uint32_t tt = rowok ? tzz : 0x03FF03FFu;
+                const bool rowok = (uint32_t)(ysrel + s) < hrange;  // iy0 <= rc < iy1 (every row of a cell-row run is a detectable row)
+                const uint32_t tt = CELLROWS || rowok ? tzz : 0x03FF03FFu;
                 bool arcs = true;
 #ifdef FM_LDS_CONSTS
                 const fm_v4 lcm = FM_LC_LOAD(fm_v4, lc_m);
@@ -159,11 +152,11 @@
                     S01[k] = S23[k] = 0u;
                 }
             }
-            if (s < 8) continue;
+            if (s < (CELLROWS ? 7 : 8)) continue;
             // ---- 3x3 strict NMS of row rn = rc - 1 on packed pairs: rows U = S[k-2], M = S[k-1], D = S[k] ----
             const int ku = (k + 6) % 8, km = (k + 7) % 8;
             const bool up_ok = rmod != 0;            // neighbours outside the own cell count as 0
-            const bool dn_ok = rmod != hcell - 1;    // (the row at iy1 is already all zero)
+            const bool dn_ok = rmod != hcell - 1 && have_row;    // (generic: the row at iy1 is already all zero; cell rows: the last row has no row below it in the run)
             const uint32_t ord_row = ordy;
             {
                 const bool wrap = rmod == hcell - 1;
@@ -195,10 +188,11 @@
             const uint32_t n01 = pk_max3(l01, x12 & rv01, v01);
             const uint32_t n23 = pk_max3(x12 & lv23, r23, v23);
             const uint32_t g01 = pk_subsat_u16(m01, n01), g23 = pk_subsat_u16(m23, n23);  // != 0 <=> survivor
-            const bool row_out = s - 8 < nrows_out;  // per lane
+            // generic: per lane; cell rows: the lanes that emit, every row of the run
+            const bool row_out = CELLROWS ? out_lane : s - 8 < nrows_out;
             // ballots of the plain compares, combined on the scalar side (a ballot of a combined predicate is lowered through a
             // VGPR: select 0 / 1, compare again)
-            const unsigned long long brow = orb_ballot(row_out);
+            const unsigned long long brow = CELLROWS ? bout : orb_ballot(row_out);
             const unsigned long long b01 = orb_ballot(g01 != 0u) & brow, b23 = orb_ballot(g23 != 0u) & brow;
             const bool has01 = row_out && g01 != 0u, has23 = row_out && g23 != 0u;
             if (b01 | b23) {
@@ -207,33 +201,8 @@
                 const uint32_t ordx[4] = {lco.x, lco.y, lco.z, lco.w};
 #endif
                 const uint32_t keyrow = key00 + ((uint32_t)s << 12);
-                const int p01 = __popcll(b01);
-                if (has01) {
-                    const bool hi = g01 > 0xFFFFu;
-                    const uint32_t a = hi ? m01 >> 16 : m01 & 0xFFFFu;
-                    sbuf[nbuf + lanes_below(b01)] = make_uint2(keyrow + (hi ? 1u : 0u) + ((a + resp0) << 24),
-                                                               ord_row + (hi ? ordx[1] : ordx[0]));
-                }
-                if (has23) {
-                    const bool hi = g23 > 0xFFFFu;
-                    const uint32_t a = hi ? m23 >> 16 : m23 & 0xFFFFu;
-                    sbuf[nbuf + p01 + lanes_below(b23)] = make_uint2(keyrow + (hi ? 3u : 2u) + ((a + resp0) << 24),
-                                                                     ord_row + (hi ? ordx[3] : ordx[2]));
-                }
-                nbuf += p01 + __popcll(b23);
-                if (wave_split) {  // both pixels of a seam pair survived: the low one is still to be written
-                    const uint32_t gs = split01 ? g01 : (split23 ? g23 : 0u);
-                    const bool dbl = row_out && (gs & 0xFFFFu) != 0u && gs > 0xFFFFu;
-                    const unsigned long long bd = orb_ballot(dbl);
-                    if (bd) {
-                        if (dbl) {
-                            const uint32_t a = (split23 ? m23 : m01) & 0xFFFFu;
-                            sbuf[nbuf + lanes_below(bd)] = make_uint2(keyrow + (split23 ? 2u : 0u) + ((a + resp0) << 24),
-                                                                      ord_row + (split23 ? ordx[2] : ordx[0]));
-                        }
-                        nbuf += __popcll(bd);
-                    }
-                }
+                const int p01n = __popcll(b01), p23n = __popcll(b23);
+#include "orbfe_fast_emit.inc"
                 if (nbuf > FM_BUF - FM_ROW_MAX) {
                     fm_flush(slist, scnt, sbuf, nbuf, key_cap, lane, lflag, ini_th);
                     nbuf = 0;

@@ -51,44 +51,7 @@
     nsteps = __builtin_amdgcn_readfirstlane(nsteps) + 8;  // wave-uniform, and the compiler knows it
     const int tz = max(plan->min_th, 1);
 
-    // per-lane column masks: bit j = pixel j inside the interior / has a valid left / right neighbour in its cell
-    // (cell column, x in cell) of the lane's four pixels from ONE division: pixel j + 1 is one step to the right of pixel j
-    // (columns left of the interior count as its first column, as `ord` below wants them)
-    int ccj[4], mj[4];
-    {
-        const int r0 = max(x - ix0, 0);
-        int c = r0 / wcell, m = r0 - c * wcell;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j > 0 && x + j - ix0 >= 1) {
-                ++m;
-                if (m == wcell) { m = 0; ++c; }
-            }
-            ccj[j] = c;
-            mj[j] = m;
-        }
-    }
-    int inside = 0, lvalid = 0, rvalid = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int xx = x + j;
-        if (xx >= ix0 && xx < ix1) {
-            const int m = mj[j];
-            inside |= 1 << j;
-            if (m != 0) lvalid |= 1 << j;
-            if (m != wcell - 1 && xx + 1 < ix1) rvalid |= 1 << j;
-        }
-    }
-    auto halves = [](int bits, int j) -> uint32_t {
-        return (((bits >> j) & 1) ? 0xFFFFu : 0u) | (((bits >> (j + 1)) & 1) ? 0xFFFF0000u : 0u);
-    };
-    const uint32_t in01 = halves(inside, 0), in23 = halves(inside, 2);
-    const uint32_t lv01 = halves(lvalid, 0), lv23 = halves(lvalid, 2);
-    const uint32_t rv01 = halves(rvalid, 0), rv23 = halves(rvalid, 2);
-    // a cell seam between the two pixels of a pair lets BOTH be NMS survivors; at most one pair of a lane has one
-    const bool split01 = (inside & 3) == 3 && !(lvalid & 2), split23 = (inside & 12) == 12 && !(lvalid & 8);
-    const bool wave_split = orb_ballot(split01 || split23) != 0ull;
-    const bool out_lane = !(ld.flags & 1) && inside != 0;
+#include "orbfe_fast_colmask.inc"
     const int nrows_out = out_lane ? (int)ld.nrows : 0;
     // per-pixel part of `ord`, the rank key of the reference's candidate order (cell-row-major, raster inside a cell):
     // ord = (cell_row * ncc + cell_col) << 12 | y_in_cell << 6 | x_in_cell
@@ -286,32 +249,7 @@
                     fm_flush(slist, scnt, sbuf, nbuf, key_cap, lane, lflag, ini_th);
                     nbuf = 0;
                 }
-                if (has01) {
-                    const bool hi = g01 > 0xFFFFu;
-                    const uint32_t a = hi ? m01 >> 16 : m01 & 0xFFFFu;
-                    sbuf[nbuf + lanes_below(b01)] = make_uint2(keyrow + (hi ? 1u : 0u) + ((a + resp0) << 24),
-                                                               ord_row + (hi ? ordx[1] : ordx[0]));
-                }
-                if (has23) {
-                    const bool hi = g23 > 0xFFFFu;
-                    const uint32_t a = hi ? m23 >> 16 : m23 & 0xFFFFu;
-                    sbuf[nbuf + p01n + lanes_below(b23)] = make_uint2(keyrow + (hi ? 3u : 2u) + ((a + resp0) << 24),
-                                                                      ord_row + (hi ? ordx[3] : ordx[2]));
-                }
-                nbuf += p01n + p23n;
-                if (wave_split) {  // both pixels of a seam pair survived: the low one is still to be written
-                    const uint32_t gs = split01 ? g01 : (split23 ? g23 : 0u);
-                    const bool dbl = row_out && (gs & 0xFFFFu) != 0u && gs > 0xFFFFu;
-                    const unsigned long long bd = orb_ballot(dbl);
-                    if (bd) {
-                        if (dbl) {
-                            const uint32_t a = (split23 ? m23 : m01) & 0xFFFFu;
-                            sbuf[nbuf + lanes_below(bd)] = make_uint2(keyrow + (split23 ? 2u : 0u) + ((a + resp0) << 24),
-                                                                      ord_row + (split23 ? ordx[2] : ordx[0]));
-                        }
-                        nbuf += __popcll(bd);
-                    }
-                }
+#include "orbfe_fast_emit.inc"
             }
         }
     }

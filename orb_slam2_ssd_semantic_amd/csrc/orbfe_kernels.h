@@ -1,4 +1,15 @@
-// orbfe_kernels.h -- launcher interface between the host API (orbfe_api.hip) and the kernels.
+// orbfe_kernels.h -- launcher interface between the host API (orbfe_api.hip) and the hand-written HIP kernels (gfx950 / CDNA4,
+// wave64) of the ORB extractor, one file per stage.
+//
+// Reference behaviour restated (paths relative to /root/reference):
+//   K1 k_pyr_walk        ComputePyramid + cv::resize INTER_LINEAR   src/ORBextractor.cc:1117-1145   orbfe_pyramid.hip
+//   K2 k_fast_map        per-cell cv::FAST + NMS + minTh fallback   src/ORBextractor.cc:798-838     orbfe_fast.hip
+//   K3 k_octree          DistributeOctTree / DivideNode             src/ORBextractor.cc:478-765     orbfe_octree.hip
+//   K4 k_blur7           GaussianBlur 7x7 sigma 2 REFLECT_101       src/ORBextractor.cc:1094-1095   orbfe_blur.hip
+//   K5 k_orient_describe IC_Angle + computeOrbDescriptor + rescale  src/ORBextractor.cc:59-131, 846-857, 1103-1110   orbfe_describe.hip
+//
+// Integer / byte work bounded by VALU issue (FAST), HBM (pyramid, blur) and LDS latency (quadtree); no MFMA.  Float steps
+// that decide an output bit use explicitly rounded single operations (__fmul_rn/__fadd_rn/__fdiv_rn, no FMA contraction).
 #pragma once
 #include "orbfe_common.h"
 
@@ -53,25 +64,27 @@ struct OrbLaunch {
     unsigned long long *d_fstat;
 };
 
-// FAST(l) + resize(l -> l + 1) in one launch per level for the levels below `nfused`, the remaining pyramid levels and one
-// FAST launch over the remaining waves after them (replaces orbk_launch_pyramid + orbk_launch_fast); spread: see k_fast_pyr
-hipError_t orbk_launch_fast_pyr(const OrbLaunch &a, int nfused, int spread, hipStream_t st);
-hipError_t orbk_launch_fast_levels(const OrbLaunch &a, int l0, int l1, int clear, hipStream_t st);
 hipError_t orbk_upload_constants(const int *umax16);
 size_t orbk_octree_lds_bytes(int node_cap, int max_nini, int w, int h, int ncells);
 size_t orbk_octree_box_bytes(int node_cap);
 size_t orbk_octree_node_bytes(int node_cap);  // global scratch per (frame, level) when the node arrays do not fit the LDS
 hipError_t orbk_prepare_octree(int node_cap, int max_nini, int w, int h, int ncells);
-size_t orbk_pyramid_lds_bytes(int dh);
-#define ORBFE_PW_ROWS 16  // destination rows per lane run of the pyramid kernels (= PW_ROWS)
-size_t orbk_pyramid2_lds_bytes(int gx, int gy);  // dynamic LDS of the two-level pyramid kernel for a tile of gx column groups x gy runs  // dynamic LDS of the pyramid kernel for a destination level of dh rows
+#define ORBFE_PW_ROWS 16  // destination rows per lane run of the pyramid kernels (8, 24, 32 measured slower)
+size_t orbk_pyramid_lds_bytes(int dh);  // dynamic LDS of the pyramid kernel for a destination level of dh rows
 hipError_t orbk_launch_pyramid(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_fast(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_octree(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_blur(const OrbLaunch &a, hipStream_t st);
+hipError_t orbk_launch_describe(const OrbLaunch &a, hipStream_t st);
+#ifdef ORBFE_DEVELOPER   // the measured-slower variants, compiled only into developer builds
+// FAST(l) + resize(l -> l + 1) in one launch per level for the levels below `nfused`, the remaining pyramid levels and one
+// FAST launch over the remaining waves after them (replaces orbk_launch_pyramid + orbk_launch_fast); spread: see k_fast_pyr
+hipError_t orbk_launch_fast_pyr(const OrbLaunch &a, int nfused, int spread, hipStream_t st);
+hipError_t orbk_launch_fast_levels(const OrbLaunch &a, int l0, int l1, int clear, hipStream_t st);
 // blur of every level and the pyramid in one chained pass (replaces orbk_launch_pyramid + orbk_launch_blur)
 hipError_t orbk_launch_blur_pyr(const OrbLaunch &a, hipStream_t st);
-hipError_t orbk_launch_describe(const OrbLaunch &a, hipStream_t st);
+size_t orbk_pyramid2_lds_bytes(int gx, int gy);  // dynamic LDS of the two-level pyramid kernel for a tile of gx column groups x gy runs
+#endif
 
 // device view of the pyramid the handle built in its last call (orbfe_api.hip), for kernels outside the extractor
 struct OrbPyrView {

@@ -1,4 +1,4 @@
-// orbfe_pyr_body.inc -- the row walk of one resize workgroup (K1, see orbfe_kernels.hip), included TEXTUALLY by k_pyr_walk and
+// orbfe_pyr_body.inc -- the row walk of one resize workgroup (K1, see orbfe_pyramid.hip) in its per-lane form, included TEXTUALLY by
 // k_fast_pyr.  Expects in scope: a (PyrArgs), bxi (index of the workgroup among the resize workgroups of its frame), b (frame).
     extern __shared__ uint2 s_dyn[];
     uint2 *s_yt = s_dyn;                                   // [dh + 8]: .x = b0 | b1 << 16, .y = sy (low half)

@@ -197,7 +197,7 @@ def test_shape_table_covers_the_run_boundaries(oracle):
         if r < 24:
             assert {0, 1, r - 1} <= {n % r for n in rows}, r
     # cell-row FAST runs: at least three run lengths put 2+ cell rows into one run on level 0 of every shape (interior cell
-    # seams inside a run: up_ok / dn_ok / ord_wrap of orbfe_fast_body_u.inc), and runs are cut short at the end of a level
+    # seams inside a run: up_ok / dn_ok / ord_wrap of orbfe_fast_body.inc with CELLROWS), and runs are cut short at the end of a level
     for s in SHAPES:
         L0 = level_geometry(s)[0]
         kcs = [max(1, (r + L0["hcell"] // 2) // L0["hcell"]) for r in ROWS_FAST if r >= 24]

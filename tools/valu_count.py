@@ -1,5 +1,5 @@
-"""Counts the instructions one steady-state row step of k_fast_map / k_blur7 issues (VALU ceiling of bench.py's roofline).
-usage: python tools/valu_count.py      (needs hipcc; compiles csrc/orbfe_kernels.hip to assembly for gfx950)
+"""Counts the instructions one steady-state row step of k_fast_map issues (VALU ceiling of bench.py's roofline).
+usage: python tools/valu_count.py      (needs hipcc; compiles csrc/orbfe_fast.hip to assembly for gfx950)
 
 k_fast_map's row loop is unrolled 8-fold; the instruction mix of the whole unrolled body (from the loop header to the
 back edge, emission slow paths included) divided by 8 is reported.  The numbers are pasted into bench.py (VALU_MODEL)."""
@@ -14,10 +14,10 @@ CSRC = os.path.join(ROOT, "orb_slam2_ssd_semantic_amd", "csrc")
 
 
 def assembly():
-    out = os.path.join(tempfile.gettempdir(), "orbfe_kernels.s")
+    out = os.path.join(tempfile.gettempdir(), "orbfe_fast.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950",
                            "--cuda-device-only", "-S", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                           os.path.join(CSRC, "orbfe_kernels.hip"), "-o", out], stderr=subprocess.DEVNULL)
+                           os.path.join(CSRC, "orbfe_fast.hip"), "-o", out], stderr=subprocess.DEVNULL)
     return open(out).read().splitlines()
 
 
