@@ -1021,6 +1021,71 @@ orbfe_status orbfe_sim3_tap(orbfe_sim3 *h, int32_t set, int32_t stage, void *dst
 enum { ORBFE_SIM3_KAT_JACOBI4 = 0, ORBFE_SIM3_KAT_ATAN2 = 1, ORBFE_SIM3_KAT_SIN = 2, ORBFE_SIM3_KAT_COS = 3, ORBFE_SIM3_KAT_ROTATION = 4 };
 orbfe_status orbfe_sim3_kat(int32_t what, int32_t n, const void *in, void *out);
 
+/* ---- The fork's dense point-cloud map (csrc/orbfe_cloud.hip) ---------------------------------------------
+ * PointCloudMapping::viewer() of the reference (src/pointcloudmapping.cc) without the detector, the outlier filter, the cluster
+ * database and the viewer: draw_rect_with_depth_threshold, generatePointCloud + pcl::transformPointCloud,
+ * removeNaNFromPointCloud, the append to globalMap and pcl::VoxelGrid.  Bit-exact against tests/cloud_oracle.py (an unpinned
+ * oracle: PCL is restated from knowledge, its assumptions are the list P1 .. P16 there).  Inside a voxel the points are summed in
+ * ascending input position (a stable sort); std::sort leaves that order open.
+ * A point is pcl::PointXYZRGBA without its padding: rgba = a << 24 | r << 16 | g << 8 | b.  Every record buffer is 16-byte
+ * aligned.  Strides are in bytes.  The *_device calls take DEVICE buffers, run on `stream` and return after it has drained: each
+ * of them reports sizes the host needs. */
+typedef struct orbfe_cloud_point {
+    float x, y, z;
+    uint32_t rgba;
+} orbfe_cloud_point;
+typedef struct orbfe_cloud orbfe_cloud;
+/* resolution: the voxel leaf (the float leaf is (float)resolution); max_points: records the map can hold, including the points of
+ * an insert before its filter pass, and the most orbfe_cloud_voxel_filter_device takes; max_frames: keyframes of one generate /
+ * insert call; w x ht: the keyframe size. */
+orbfe_status orbfe_cloud_create(int32_t device, double resolution, int32_t max_points, int32_t max_frames, int32_t w, int32_t ht,
+                                orbfe_cloud **out);
+void orbfe_cloud_destroy(orbfe_cloud *h);
+void *orbfe_cloud_get_stream(orbfe_cloud *h);
+/* draw_rect_with_depth_threshold for the boxes of ONE frame, in list order (the caller has dropped the detections with
+ * prob <= 0.54).  boxes [nboxes][4] = cv::Rect_<float> x, y, width, height and colors [nboxes][3] = the bytes stored at
+ * color[3 j + 0 .. 2] are HOST arrays.  The colour plane is painted in place; the flat pixel indices of box b (ascending) follow
+ * those of box b - 1 in d_indices, counts[b] (host) of them.  idx_cap < the sum of (height - 1) * (width - 2) over the boxes (the
+ * most they can record): ORBFE_ERR_CAP, *n_out = that sum.  A box for which an index the reference would read or write lies
+ * outside the plane (undefined there), whose numbers are not finite or reach 2^20, or whose painted width exceeds w:
+ * ORBFE_ERR_ARG, nothing is written.  *n_out = indices recorded. */
+orbfe_status orbfe_cloud_paint_boxes_device(orbfe_cloud *h, const float *d_depth, size_t depth_stride, uint8_t *d_bgr, size_t bgr_stride,
+                                            const float *boxes, const uint8_t *colors, int32_t nboxes, int32_t *d_indices,
+                                            int32_t idx_cap, int32_t *counts, int32_t *n_out, void *stream);
+/* generatePointCloud, transformPointCloud and removeNaNFromPointCloud for nframes keyframes: float depth planes, BGR planes,
+ * intrinsics [nframes][4] = fx, fy, cx, cy and T [nframes][16] = T.inverse().matrix() row-major in double (HOST arrays; see
+ * orbfe_cloud_pose_matrix).  d_out receives the finite points of frame 0 in pixel order, then frame 1's, ...; counts[f] (host) and
+ * *n_out tell how many.  More than cap: ORBFE_ERR_CAP, *n_out = the need, d_out untouched. */
+orbfe_status orbfe_cloud_generate_device(orbfe_cloud *h, const float *d_depth, size_t depth_stride, size_t depth_frame_stride,
+                                         const uint8_t *d_bgr, size_t bgr_stride, size_t bgr_frame_stride, int32_t nframes,
+                                         const float *intrinsics, const double *T, orbfe_cloud_point *d_out, int32_t cap,
+                                         int32_t *counts, int32_t *n_out, void *stream);
+/* What viewer() does when it wakes up to nframes new keyframes: generate each, append to the map, then one VoxelGrid pass over
+ * the map.  Map size + new points > max_points: ORBFE_ERR_CAP, *n_out = the need, the map unchanged.  *n_out = the map's size
+ * after the call; *overflow = 1 when PCL's grid-size check (more than INT_MAX cells) left the map unfiltered. */
+orbfe_status orbfe_cloud_insert_device(orbfe_cloud *h, const float *d_depth, size_t depth_stride, size_t depth_frame_stride,
+                                       const uint8_t *d_bgr, size_t bgr_stride, size_t bgr_frame_stride, int32_t nframes,
+                                       const float *intrinsics, const double *T, int32_t *counts, int32_t *n_out, int32_t *overflow,
+                                       void *stream);
+/* one keyframe from HOST planes (w floats / 3 w bytes per row, no padding), on the handle's stream */
+orbfe_status orbfe_cloud_insert(orbfe_cloud *h, const float *depth, const uint8_t *bgr, const float *intrinsics, const double *T,
+                                int32_t *n_out, int32_t *overflow);
+/* pcl::VoxelGrid (the handle's leaf) over n <= max_points records; d_out (cap records) may not overlap d_in.  n = 0 or no finite
+ * point: 0 voxels.  More than INT_MAX cells: ORBFE_OK, *overflow = 1 and the input copied through (cap < n: ORBFE_ERR_CAP).
+ * More voxels than cap: ORBFE_ERR_CAP, *n_out = the need. */
+orbfe_status orbfe_cloud_voxel_filter_device(orbfe_cloud *h, const orbfe_cloud_point *d_in, int32_t n, orbfe_cloud_point *d_out,
+                                             int32_t cap, int32_t *n_out, int32_t *overflow, void *stream);
+/* the map: its size, its records on the device (valid until the next insert / upload), a copy to the host (cap < size:
+ * ORBFE_ERR_CAP, *n_out = size), and its replacement by n device records (n = 0 empties it) */
+int32_t orbfe_cloud_size(const orbfe_cloud *h);
+const orbfe_cloud_point *orbfe_cloud_data_device(const orbfe_cloud *h);
+orbfe_status orbfe_cloud_download(orbfe_cloud *h, orbfe_cloud_point *dst, int32_t cap, int32_t *n_out);
+orbfe_status orbfe_cloud_upload_device(orbfe_cloud *h, const orbfe_cloud_point *d_points, int32_t n, void *stream);
+/* Host only: Converter::toSE3Quat(Tcw) followed by Isometry3d::inverse().matrix() -- the float pose widened to double, its
+ * rotation through g2o's normalised quaternion and back, then R^T and -(R^T) t; row-major in and out.  Restated from knowledge of
+ * Eigen 3.2 / g2o (oracle P15, P16); a caller that links Eigen passes its own matrix to the calls above. */
+orbfe_status orbfe_cloud_pose_matrix(const float Tcw[16], double out[16]);
+
 #ifdef __cplusplus
 }
 #endif

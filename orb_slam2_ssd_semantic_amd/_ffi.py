@@ -52,6 +52,9 @@ SYMBOLS = (
     "orbfe_undistort_points", "orbfe_image_bounds", "orbfe_frame_geometry_batch_device", "orbfe_depth_to_float_device",
     "orbfe_sim3_create", "orbfe_sim3_destroy", "orbfe_sim3_get_stream", "orbfe_sim3_ransac_iterations", "orbfe_sim3_iterate",
     "orbfe_sim3_iterate_device", "orbfe_sim3_prepare_device", "orbfe_sim3_set_tap_iteration", "orbfe_sim3_tap", "orbfe_sim3_kat",
+    "orbfe_cloud_create", "orbfe_cloud_destroy", "orbfe_cloud_get_stream", "orbfe_cloud_paint_boxes_device", "orbfe_cloud_generate_device",
+    "orbfe_cloud_insert_device", "orbfe_cloud_insert", "orbfe_cloud_voxel_filter_device", "orbfe_cloud_size", "orbfe_cloud_data_device",
+    "orbfe_cloud_download", "orbfe_cloud_upload_device", "orbfe_cloud_pose_matrix",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -322,6 +325,22 @@ def _configure(L):
     L.orbfe_sim3_set_tap_iteration.argtypes = [vp, i32]
     L.orbfe_sim3_tap.argtypes = [vp, i32, i32, vp, sz, vp]
     L.orbfe_sim3_kat.argtypes = [i32, i32, vp, vp]
+    L.orbfe_cloud_create.argtypes = [i32, f64, i32, i32, i32, i32, C.POINTER(vp)]
+    L.orbfe_cloud_destroy.argtypes = [vp]
+    L.orbfe_cloud_destroy.restype = None
+    L.orbfe_cloud_get_stream.argtypes = [vp]
+    L.orbfe_cloud_get_stream.restype = vp
+    L.orbfe_cloud_paint_boxes_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, i32, vp, i32, vp, vp, vp]
+    L.orbfe_cloud_generate_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.orbfe_cloud_insert_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i32, vp, vp, vp, vp, vp, vp]
+    L.orbfe_cloud_insert.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_cloud_voxel_filter_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
+    L.orbfe_cloud_size.argtypes = [vp]
+    L.orbfe_cloud_data_device.argtypes = [vp]
+    L.orbfe_cloud_data_device.restype = vp
+    L.orbfe_cloud_download.argtypes = [vp, vp, i32, vp]
+    L.orbfe_cloud_upload_device.argtypes = [vp, vp, i32, vp]
+    L.orbfe_cloud_pose_matrix.argtypes = [vp, vp]
     cam = C.POINTER(OrbfeCamera)
     L.orbfe_undistort_points.argtypes = [vp, vp, i32, cam, vp]
     L.orbfe_image_bounds.argtypes = [cam, i32, i32, vp]
