@@ -1022,8 +1022,8 @@ enum { ORBFE_SIM3_KAT_JACOBI4 = 0, ORBFE_SIM3_KAT_ATAN2 = 1, ORBFE_SIM3_KAT_SIN 
 orbfe_status orbfe_sim3_kat(int32_t what, int32_t n, const void *in, void *out);
 
 /* ---- The fork's dense point-cloud map (csrc/orbfe_cloud.hip) ---------------------------------------------
- * PointCloudMapping::viewer() of the reference (src/pointcloudmapping.cc) without the detector, the outlier filter, the cluster
- * database and the viewer: draw_rect_with_depth_threshold, generatePointCloud + pcl::transformPointCloud,
+ * PointCloudMapping::viewer() of the reference (src/pointcloudmapping.cc) without the detector and the viewer (the outlier filter
+ * and the cluster database follow in the next section): draw_rect_with_depth_threshold, generatePointCloud + pcl::transformPointCloud,
  * removeNaNFromPointCloud, the append to globalMap and pcl::VoxelGrid.  Bit-exact against tests/cloud_oracle.py (an unpinned
  * oracle: PCL is restated from knowledge, its assumptions are the list P1 .. P16 there).  Inside a voxel the points are summed in
  * ascending input position (a stable sort); std::sort leaves that order open.
@@ -1085,6 +1085,80 @@ orbfe_status orbfe_cloud_upload_device(orbfe_cloud *h, const orbfe_cloud_point *
  * rotation through g2o's normalised quaternion and back, then R^T and -(R^T) t; row-major in and out.  Restated from knowledge of
  * Eigen 3.2 / g2o (oracle P15, P16); a caller that links Eigen passes its own matrix to the calls above. */
 orbfe_status orbfe_cloud_pose_matrix(const float Tcw[16], double out[16]);
+
+/* ---- The fork's 3-D objects (csrc/orbfe_objects.hip) -------------------------------------------------------
+ * What viewer() does per keyframe and detected box (src/pointcloudmapping.cc:441-479): ExtractIndices with the indices
+ * orbfe_cloud_paint_boxes_device recorded, pcl::StatisticalOutlierRemoval, pcl::VoxelGrid, compute3DCentroid, getMinMax3D; and
+ * sem_merge with the `clusters` vector (:246-322).  Bit-exact against tests/objects_oracle.py (unpinned, assumptions O1 .. O12
+ * there).  Three decisions are the library's: sqrt(nn_dists[k]) is the DOUBLE square root of the widened float; an object with
+ * fewer than mean_k + 1 finite points is reported ORBFE_OBJECT_TOO_FEW, not filtered, and yields no cluster (the reference reads
+ * past the end of an array there); an object with no index or no voxel is reported ORBFE_OBJECT_EMPTY and yields no cluster.
+ * The calls hang off an orbfe_cloud handle; their scratch is allocated at their first use.  mean_k in [1, 63] (the reference: 50),
+ * stddev_mul a number (the reference: 1.0), mode = how the nearest neighbours are found (same result): anything else is
+ * ORBFE_ERR_ARG before any launch. */
+enum { ORBFE_OBJECT_OK = 0, ORBFE_OBJECT_TOO_FEW = 1, ORBFE_OBJECT_EMPTY = 2 };
+enum { ORBFE_KNN_AUTO = 0, ORBFE_KNN_BRUTE = 1, ORBFE_KNN_GRID = 2 };
+#define ORBFE_OBJECT_CLASSES 21 /* background + the 20 VOC classes */
+typedef struct orbfe_object {
+    int32_t status, n_in, n_kept, n_voxels; /* indices in, points the filter kept, voxels of the kept points */
+    float centroid[3], min[3], max[3];      /* over the voxels; zeros unless status is ORBFE_OBJECT_OK */
+    int32_t reserved_;
+    double threshold, mean, stddev;         /* of the filter's mean neighbour distances */
+} orbfe_object;
+typedef struct orbfe_filter_stat {
+    int32_t status, n_in, n_finite, n_kept;
+    double threshold, mean, stddev;
+} orbfe_filter_stat;
+/* how one point set's neighbours were found: used = ORBFE_KNN_BRUTE or ORBFE_KNN_GRID; for the grid its cells per axis, its
+ * origin and cells per metre: the cell of x is min(dims[0] - 1, (int)((x - origin[0]) * inv_cell)), in float.  The grid depends
+ * on the set's bounds and its number of finite points only. */
+typedef struct orbfe_knn_plan {
+    int32_t used, dims[3];
+    float origin[3], inv_cell;
+    int32_t n_finite, cells;
+} orbfe_knn_plan;
+/* pcl::StatisticalOutlierRemoval over nobj point sets at once: set o is d_points[offsets[o] .. offsets[o + 1]) (offsets: HOST,
+ * nobj + 1 entries from 0).  d_distances (one float per record) receives the mean distance to the mean_k nearest neighbours (0 for
+ * a record that is not finite and for the sets that are not filtered), d_keep (one byte per record) 1 for a point that stays;
+ * stats [nobj] and, unless NULL, plans [nobj] are HOST arrays. */
+orbfe_status orbfe_cloud_outlier_filter_device(orbfe_cloud *h, const orbfe_cloud_point *d_points, const int32_t *offsets, int32_t nobj,
+                                               int32_t mean_k, double stddev_mul, int32_t mode, float *d_distances, uint8_t *d_keep,
+                                               orbfe_filter_stat *stats, orbfe_knn_plan *plans, void *stream);
+/* The objects of ONE keyframe: the depth plane, the colour plane orbfe_cloud_paint_boxes_device painted, intrinsics [4] and T [16]
+ * as for orbfe_cloud_generate_device, and that call's d_indices (device) and counts [nboxes] (host).  objects [nboxes] (HOST) is
+ * filled.  Unless NULL, d_kept receives the flat indices the filter kept (box after box, objects[b].n_kept each) and d_voxels the
+ * voxel records (objects[b].n_voxels each, the objects that are not OK have none); *n_kept / *n_voxels = their totals.  More than
+ * kept_cap / voxel_cap: ORBFE_ERR_CAP, the totals report the need, nothing else is written.  An index outside the plane yields a
+ * point that is not finite. */
+orbfe_status orbfe_cloud_objects_device(orbfe_cloud *h, const float *d_depth, size_t depth_stride, const uint8_t *d_bgr, size_t bgr_stride,
+                                        const float *intrinsics, const double *T, const int32_t *d_indices, const int32_t *counts,
+                                        int32_t nboxes, int32_t mean_k, double stddev_mul, int32_t mode, orbfe_object *objects,
+                                        int32_t *d_kept, int32_t kept_cap, orbfe_cloud_point *d_voxels, int32_t voxel_cap, int32_t *n_kept,
+                                        int32_t *n_voxels, void *stream);
+/* one keyframe from HOST planes (no padding) and HOST boxes / colours as for orbfe_cloud_paint_boxes_device, on the handle's
+ * stream: the paint (bgr is painted in place), then the objects */
+orbfe_status orbfe_cloud_objects(orbfe_cloud *h, const float *depth, uint8_t *bgr, const float *intrinsics, const double *T,
+                                 const float *boxes, const uint8_t *colors, int32_t nboxes, int32_t mean_k, double stddev_mul, int32_t mode,
+                                 orbfe_object *objects);
+/* bytes of device scratch the calls of this section have allocated on the handle so far (0 until the first of them) */
+int64_t orbfe_cloud_objects_scratch_bytes(const orbfe_cloud *h);
+/* Host only: the reference's `clusters` vector and sem_merge.  obj_size [ORBFE_OBJECT_CLASSES] = the distance below which two
+ * centroids of a class are one object, NULL = the reference's table.  merge: the nearest same-class entry closer than 100 m and
+ * than obj_size[class_id] takes the cluster (prob and centroid averaged, min the smaller minimum, max the SMALLER maximum, as
+ * the reference has it), else it is appended; *index_out = the entry.  The caller applies the reference's prob > 0.54 gate and
+ * merges only objects whose status is ORBFE_OBJECT_OK. */
+typedef struct orbfe_cluster {
+    int32_t class_id;
+    float prob, centroid[3], min[3], max[3];
+} orbfe_cluster;
+typedef struct orbfe_objects orbfe_objects;
+orbfe_status orbfe_objects_create(const float *obj_size, orbfe_objects **out);
+void orbfe_objects_destroy(orbfe_objects *db);
+orbfe_status orbfe_objects_merge(orbfe_objects *db, int32_t class_id, float prob, const float *centroid, const float *min_pt,
+                                 const float *max_pt, int32_t *index_out);
+int32_t orbfe_objects_size(const orbfe_objects *db);
+orbfe_status orbfe_objects_get(const orbfe_objects *db, int32_t i, orbfe_cluster *out);
+void orbfe_objects_clear(orbfe_objects *db);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,8 @@ SYMBOLS = (
     "orbfe_cloud_create", "orbfe_cloud_destroy", "orbfe_cloud_get_stream", "orbfe_cloud_paint_boxes_device", "orbfe_cloud_generate_device",
     "orbfe_cloud_insert_device", "orbfe_cloud_insert", "orbfe_cloud_voxel_filter_device", "orbfe_cloud_size", "orbfe_cloud_data_device",
     "orbfe_cloud_download", "orbfe_cloud_upload_device", "orbfe_cloud_pose_matrix",
+    "orbfe_cloud_outlier_filter_device", "orbfe_cloud_objects_device", "orbfe_cloud_objects", "orbfe_cloud_objects_scratch_bytes",
+    "orbfe_objects_create", "orbfe_objects_destroy", "orbfe_objects_merge", "orbfe_objects_size", "orbfe_objects_get", "orbfe_objects_clear",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -341,6 +343,19 @@ def _configure(L):
     L.orbfe_cloud_download.argtypes = [vp, vp, i32, vp]
     L.orbfe_cloud_upload_device.argtypes = [vp, vp, i32, vp]
     L.orbfe_cloud_pose_matrix.argtypes = [vp, vp]
+    L.orbfe_cloud_outlier_filter_device.argtypes = [vp, vp, vp, i32, i32, f64, i32, vp, vp, vp, vp, vp]
+    L.orbfe_cloud_objects_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, i32, i32, f64, i32, vp, vp, i32, vp, i32, vp, vp, vp]
+    L.orbfe_cloud_objects.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, f64, i32, vp]
+    L.orbfe_cloud_objects_scratch_bytes.argtypes = [vp]
+    L.orbfe_cloud_objects_scratch_bytes.restype = C.c_int64
+    L.orbfe_objects_create.argtypes = [vp, C.POINTER(vp)]
+    L.orbfe_objects_destroy.argtypes = [vp]
+    L.orbfe_objects_destroy.restype = None
+    L.orbfe_objects_merge.argtypes = [vp, i32, C.c_float, vp, vp, vp, vp]
+    L.orbfe_objects_size.argtypes = [vp]
+    L.orbfe_objects_get.argtypes = [vp, i32, vp]
+    L.orbfe_objects_clear.argtypes = [vp]
+    L.orbfe_objects_clear.restype = None
     cam = C.POINTER(OrbfeCamera)
     L.orbfe_undistort_points.argtypes = [vp, vp, i32, cam, vp]
     L.orbfe_image_bounds.argtypes = [cam, i32, i32, vp]

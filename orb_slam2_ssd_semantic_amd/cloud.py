@@ -11,6 +11,16 @@ from ._ffi import Handle, stream_arg, tensor_ptr
 
 REC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("rgba", "<u4")])   # orbfe_cloud_point
 assert REC_DTYPE.itemsize == 16
+OBJECT_DTYPE = np.dtype([("status", "<i4"), ("n_in", "<i4"), ("n_kept", "<i4"), ("n_voxels", "<i4"), ("centroid", "<f4", 3), ("min", "<f4", 3),
+                         ("max", "<f4", 3), ("reserved_", "<i4"), ("threshold", "<f8"), ("mean", "<f8"), ("stddev", "<f8")])   # orbfe_object
+FILTER_DTYPE = np.dtype([("status", "<i4"), ("n_in", "<i4"), ("n_finite", "<i4"), ("n_kept", "<i4"), ("threshold", "<f8"), ("mean", "<f8"),
+                         ("stddev", "<f8")])   # orbfe_filter_stat
+PLAN_DTYPE = np.dtype([("used", "<i4"), ("dims", "<i4", 3), ("origin", "<f4", 3), ("inv_cell", "<f4"), ("n_finite", "<i4"), ("cells", "<i4")])
+CLUSTER_DTYPE = np.dtype([("class_id", "<i4"), ("prob", "<f4"), ("centroid", "<f4", 3), ("min", "<f4", 3), ("max", "<f4", 3)])   # orbfe_cluster
+assert (OBJECT_DTYPE.itemsize, FILTER_DTYPE.itemsize, PLAN_DTYPE.itemsize, CLUSTER_DTYPE.itemsize) == (80, 40, 40, 44)
+OBJECT_OK, OBJECT_TOO_FEW, OBJECT_EMPTY = 0, 1, 2
+KNN_AUTO, KNN_BRUTE, KNN_GRID = 0, 1, 2
+PROB_GATE = 0.54   # the reference merges a detection only when prob > 0.54
 
 
 def pose_matrix(Tcw):
@@ -170,6 +180,90 @@ class PointCloudMap(Handle):
             return n.value
         return out[:n.value], bool(ovf.value)
 
+    def outlier_filter(self, points, offsets=None, mean_k=50, stddev_mul=1.0, mode=KNN_AUTO, stream=None):
+        """pcl::StatisticalOutlierRemoval over one point set or several (offsets: CSR, len(sets) + 1 entries from 0): a device
+        cloud (int32 [n, 4]) or REC_DTYPE host records.  -> (distances float32 device tensor [n], keep uint8 device tensor [n],
+        FILTER_DTYPE stats [sets], PLAN_DTYPE plans [sets])"""
+        import torch
+        if isinstance(points, np.ndarray):
+            points = torch.from_numpy(np.ascontiguousarray(points, REC_DTYPE).view(np.int32).reshape(-1, 4))
+        src = points.to(self._dev()).contiguous()
+        if src.dtype != torch.int32 or src.ndim != 2 or src.shape[1] != 4:
+            raise ValueError("a cloud is an int32 [n, 4] tensor")
+        n = src.shape[0]
+        off = np.array([0, n], np.int32) if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        if off.ndim != 1 or len(off) < 1 or (len(off) > 0 and off[-1] != n):
+            raise ValueError("offsets run from 0 to the number of points")
+        nobj = len(off) - 1
+        dist = torch.zeros(max(n, 1), dtype=torch.float32, device=self._dev())
+        keep = torch.zeros(max(n, 1), dtype=torch.uint8, device=self._dev())
+        stats = np.zeros(max(nobj, 1), FILTER_DTYPE)
+        plans = np.zeros(max(nobj, 1), PLAN_DTYPE)
+        _ffi.check(self._L.orbfe_cloud_outlier_filter_device(self.h, tensor_ptr(src) if n else None, _ffi.ptr(off), nobj, int(mean_k),
+                                                             float(stddev_mul), int(mode), tensor_ptr(dist), tensor_ptr(keep), _ffi.ptr(stats),
+                                                             _ffi.ptr(plans), stream_arg(self._dev(), stream)),
+                   "orbfe_cloud_outlier_filter_device")
+        return dist[:n], keep[:n], stats[:nobj], plans[:nobj]
+
+    def build_objects(self, depth, bgr, pose, camera, indices, mean_k=50, stddev_mul=1.0, mode=KNN_AUTO, want_kept=False, want_voxels=False,
+                      stream=None):
+        """The objects of one keyframe from the index lists paint_boxes returned (bgr: the painted plane).  -> OBJECT_DTYPE [boxes],
+        and, when asked for, the list of kept-index arrays and the list of REC_DTYPE voxel arrays"""
+        import torch
+        d, c, B, K, T = self._frames(depth, bgr, pose, camera)
+        if B != 1:
+            raise ValueError("one keyframe at a time")
+        counts = np.array([len(ix) for ix in indices], np.int32)
+        nb, total = len(counts), int(counts.sum())
+        flat = np.concatenate([np.asarray(ix, np.int32) for ix in indices]) if total else np.zeros(0, np.int32)
+        idx = torch.from_numpy(np.ascontiguousarray(flat)).to(self._dev()) if total else None
+        objs = np.zeros(max(nb, 1), OBJECT_DTYPE)
+        kept = torch.zeros(max(total, 1), dtype=torch.int32, device=self._dev()) if want_kept else None
+        vox = torch.zeros((max(total, 1), 4), dtype=torch.int32, device=self._dev()) if want_voxels else None
+        nk, nv = C.c_int32(), C.c_int32()
+        _ffi.check(self._L.orbfe_cloud_objects_device(self.h, tensor_ptr(d), self.w * 4, tensor_ptr(c), self.w * 3, _ffi.ptr(K), _ffi.ptr(T),
+                                                      tensor_ptr(idx) if total else None, _ffi.ptr(counts) if nb else None, nb, int(mean_k),
+                                                      float(stddev_mul), int(mode), _ffi.ptr(objs), tensor_ptr(kept) if want_kept else None, total,
+                                                      tensor_ptr(vox) if want_voxels else None, total, C.byref(nk), C.byref(nv),
+                                                      stream_arg(self._dev(), stream)), "orbfe_cloud_objects_device")
+        objs = objs[:nb]
+        out = [objs]
+        if want_kept:
+            flatk = kept[:nk.value].cpu().numpy()
+            ends = np.cumsum(objs["n_kept"])
+            out.append([flatk[e - k:e].copy() for e, k in zip(ends, objs["n_kept"])])
+        if want_voxels:
+            flatv = to_records(vox[:nv.value])
+            nvs = np.where(objs["status"] == OBJECT_OK, objs["n_voxels"], 0)
+            ends = np.cumsum(nvs)
+            out.append([flatv[e - k:e].copy() for e, k in zip(ends, nvs)])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def objects(self, depth, bgr, pose, camera, boxes, colors, probs, class_ids, db=None, mean_k=50, stddev_mul=1.0, mode=KNN_AUTO, stream=None):
+        """What viewer() does with the detections of one keyframe: the reference's prob > 0.54 gate, the box paint, then per box
+        the outlier filter, the voxel grid, the centroid and the bounds; with `db` (an ObjectDatabase) every object whose status
+        is OBJECT_OK is merged into it.  -> (OBJECT_DTYPE records of the boxes that passed the gate, their positions in `boxes`,
+        the painted bgr device tensor)"""
+        bx = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
+        col = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        pr = np.ascontiguousarray(probs, np.float32).reshape(-1)
+        cid = np.ascontiguousarray(class_ids, np.int32).reshape(-1)
+        if not (len(bx) == len(col) == len(pr) == len(cid)):
+            raise ValueError("one colour, probability and class per box")
+        sel = np.nonzero(pr.astype(np.float64) > PROB_GATE)[0]
+        d, c = self._planes(depth, bgr)
+        painted, indices = self.paint_boxes(d, c, bx[sel], col[sel], stream)
+        objs = self.build_objects(d, c, pose, camera, indices, mean_k, stddev_mul, mode, stream=stream)
+        if db is not None:
+            for o, k in zip(objs, sel):
+                if o["status"] == OBJECT_OK:
+                    db.merge(int(cid[k]), pr[k], o["centroid"], o["min"], o["max"])
+        return objs, sel, painted
+
+    def objects_scratch_bytes(self):
+        """device bytes the outlier filter and the objects have allocated on this handle (0 until they are first used)"""
+        return int(self._L.orbfe_cloud_objects_scratch_bytes(self.h))
+
     def load(self, points, stream=None):
         """replace the map by a device cloud (int32 [n, 4]); an empty one clears it"""
         p = points.contiguous()
@@ -232,3 +326,50 @@ def paint_boxes(depth, bgr, boxes, colors, device=0):
     with PointCloudMap(1.0, int(d.shape[-1]), int(d.shape[-2]), max_points=1, max_frames=1, device=device) as m:
         img, idx = m.paint_boxes(depth, bgr, boxes, colors)
         return img.cpu().numpy(), idx
+
+
+class ObjectDatabase(Handle):
+    """The reference's `clusters` vector with sem_merge (host only, no device needed).  obj_size: 21 floats, the distance below
+    which two centroids of a class are one object; None = the reference's table."""
+
+    _HANDLE, _DESTROY = "h", "orbfe_objects_destroy"
+
+    def __init__(self, obj_size=None):
+        self._L = _ffi.lib()
+        self.h = C.c_void_p()
+        sizes = None if obj_size is None else np.ascontiguousarray(obj_size, np.float32).reshape(21)
+        _ffi.check(self._L.orbfe_objects_create(_ffi.ptr(sizes), C.byref(self.h)), "orbfe_objects_create")
+
+    def merge(self, class_id, prob, centroid, min_pt, max_pt):
+        """-> the index of the entry that took the cluster"""
+        v = [np.ascontiguousarray(a, np.float32).reshape(3) for a in (centroid, min_pt, max_pt)]
+        i = C.c_int32()
+        _ffi.check(self._L.orbfe_objects_merge(self.h, int(class_id), float(np.float32(prob)), _ffi.ptr(v[0]), _ffi.ptr(v[1]), _ffi.ptr(v[2]),
+                                               C.byref(i)), "orbfe_objects_merge")
+        return i.value
+
+    def __len__(self):
+        return int(self._L.orbfe_objects_size(self.h))
+
+    def records(self):
+        """CLUSTER_DTYPE [len(self)]"""
+        out = np.zeros(len(self), CLUSTER_DTYPE)
+        for i in range(len(out)):
+            _ffi.check(self._L.orbfe_objects_get(self.h, i, C.c_void_p(out[i:i + 1].ctypes.data)), "orbfe_objects_get")
+        return out
+
+    def clear(self):
+        self._L.orbfe_objects_clear(self.h)
+
+
+def statistical_outlier_removal(points, mean_k=50, stddev_mul=1.0, mode=KNN_AUTO, device=0):
+    """pcl::StatisticalOutlierRemoval over REC_DTYPE records, a float32 [n, 3] array or a device cloud -> (keep bool [n],
+    distances float32 [n], the FILTER_DTYPE record) on the host"""
+    if isinstance(points, np.ndarray) and points.dtype != REC_DTYPE:
+        xyz = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rec = np.zeros(len(xyz), REC_DTYPE)
+        rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+        points = rec
+    with PointCloudMap(1.0, 1, 1, max_points=1, max_frames=1, device=device) as m:
+        dist, keep, stats, _ = m.outlier_filter(points, None, mean_k, stddev_mul, mode)
+        return keep.cpu().numpy().astype(bool), dist.cpu().numpy(), stats[0]
