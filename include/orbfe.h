@@ -1160,6 +1160,116 @@ int32_t orbfe_objects_size(const orbfe_objects *db);
 orbfe_status orbfe_objects_get(const orbfe_objects *db, int32_t i, orbfe_cluster *out);
 void orbfe_objects_clear(orbfe_objects *db);
 
+/* ---- PnPsolver's EPnP RANSAC (csrc/orbfe_pnp.hip) ----------------------------------------------------------
+ * The reference's PnPsolver (src/PnPsolver.cc): EPnP on four correspondences inside the RANSAC loop of `iterate`, with Refine's
+ * EPnP over the best inliers, the step of Tracking::Relocalization between SearchByBoW and PoseOptimization.  The inputs are the
+ * constructor's vectors of the N correspondences: P3Dw [N][3] (map point positions), P2D [N][2] (undistorted keypoints), sigma2
+ * [N] (mvLevelSigma2 of the keypoint's octave), float; K = (fx, fy, cx, cy).  The random draws are an input: raw values in
+ * [0, 2^31 - 1], FOUR per iteration, index (int)(((double)r / 2147483648.0) * size) over the shrinking list; Refine consumes none.
+ * Everything is the reference's arithmetic, fp64 where it uses double and float where it uses float, bit-exact against
+ * tests/pnp_oracle.py (an unpinned restatement; its numbered assumptions P1.. are DESIGN 8h's). */
+typedef struct orbfe_pnp_params {
+    int32_t min_inliers;            /* mRansacMinInliers after SetRansacParameters */
+    int32_t max_its;                /* mRansacMaxIts, clamped */
+    float epsilon;                  /* mRansacEpsilon, possibly raised */
+    float th2;                      /* mvMaxError[i] = sigma2[i] * th2; orbfe_pnp_ransac_params sets the reference's default 5.991 */
+} orbfe_pnp_params;
+typedef struct orbfe_pnp_state {    /* what a solver carries from one iterate call to the next; all zero = a new solver */
+    int32_t iterations;             /* mnIterations */
+    int32_t best_inliers;           /* mnBestInliers */
+    int32_t reserved[2];
+    float best_Tcw[16];             /* mBestTcw */
+} orbfe_pnp_state;
+typedef struct orbfe_pnp_result {
+    int32_t found;                  /* a pose was returned: Refine's (refined = 1) or, at the clamp, the best one (refined = 0) */
+    int32_t no_more;                /* bNoMore */
+    int32_t n_inliers;              /* nInliers, 0 unless found */
+    int32_t iterations_run;         /* iterations this call ran = groups of four draws it consumed */
+    int32_t refined;
+    int32_t refine_runs;            /* EPnP runs of Refine in this call: one per best mask (a failed Refine is a function of the best
+                                       mask alone and is not repeated until the best changes), where the reference runs one per
+                                       iteration at or above min_inliers */
+    int32_t reserved[2];
+    float Tcw[16];                  /* the returned matrix, all zeros unless found */
+} orbfe_pnp_result;
+typedef struct orbfe_pnp_set {      /* one set of the batched form */
+    float K[4];
+    orbfe_pnp_params params;
+    int32_t n_iterations;           /* iterate's argument */
+    int32_t draws_offset;           /* first draw of the set in d_draws */
+    int32_t key_offset, n_keys;     /* the set's slice of d_key_mask (n_keys = 0: no scatter) */
+} orbfe_pnp_set;
+typedef struct orbfe_pnp_iter {     /* tap record of one iteration run */
+    int32_t quad[4];                /* the four correspondences drawn */
+    int32_t N;                      /* compute_pose's choice among the three beta approximations, 1 .. 3 */
+    int32_t n_inliers;              /* mnInliersi */
+    int32_t refine_ran;             /* this call ran Refine's EPnP at this iteration */
+    int32_t refine_inliers;         /* mnRefinedInliers of the best mask of this iteration, 0 when n_inliers < min_inliers */
+    double R[9], t[3];              /* mRi, mti */
+} orbfe_pnp_iter;
+typedef struct orbfe_pnp orbfe_pnp;   /* device scratch for one host call and for Refine, test taps, own stream */
+/* max_points: correspondences of one host call, and of all sets of one batched call together */
+orbfe_status orbfe_pnp_create(int32_t device, int32_t max_points, int32_t max_sets, orbfe_pnp **out);
+void orbfe_pnp_destroy(orbfe_pnp *h);
+void *orbfe_pnp_get_stream(orbfe_pnp *h);
+/* Host only: SetRansacParameters as written (the N * epsilon truncation, both clamps, the epsilon raise, pow(epsilon, 3) although
+ * the set is 4, the host's libm); out->th2 = 5.991. */
+orbfe_status orbfe_pnp_ransac_params(double probability, int32_t min_inliers, int32_t max_its, int32_t min_set, float epsilon, int32_t n,
+                                     orbfe_pnp_params *out);
+/* iterations one call can run: the reference's loop goes on while mnIterations < mRansacMaxIts OR nCurrentIterations <
+ * n_iterations, i.e. max(n_iterations, max_its - state->iterations) unless Refine returns first.  The call reads 4 draws for
+ * each of them. */
+int32_t orbfe_pnp_iterations(const orbfe_pnp_state *state, const orbfe_pnp_params *params, int32_t n_iterations);
+/* One solver's iterate(n_iterations) on HOST arrays, synchronous.  draws: 4 * orbfe_pnp_iterations(..) values.  state and
+ * best_mask (mvbBestInliers, uint8 [n]) are the solver's, in / out; mask (may be NULL) is vbInliers per correspondence.  n <
+ * min_inliers gives no_more = 1 and no model, and so does n < 4, where the reference is undefined: the library's decision.
+ * ORBFE_ERR_ARG: a NULL pointer, n < 0 or > max_points, negative counters, more iterations than 2^20. */
+orbfe_status orbfe_pnp_iterate(orbfe_pnp *h, const float *P3Dw, const float *P2D, const float *sigma2, int32_t n, const float *K,
+                               const orbfe_pnp_params *params, int32_t n_iterations, const int32_t *draws, orbfe_pnp_state *state,
+                               uint8_t *best_mask, orbfe_pnp_result *result, uint8_t *mask);
+/* Batched form, DEVICE buffers: the solvers of one Relocalization round in one launch, one workgroup per set.  Set i holds
+ * correspondences [d_offsets[i], d_offsets[i + 1]) of the flat arrays (at most max_points in all).  d_keypoint_index (with
+ * d_key_mask, both or neither): mvKeyPointIndices; on a return the set's inliers are scattered into its slice of d_key_mask,
+ * which lines up with the vpMapPointMatches the following SearchByProjection takes.  Enqueued on `stream` (NULL = HIP's default
+ * stream), no synchronisation. */
+orbfe_status orbfe_pnp_iterate_device(orbfe_pnp *h, const int32_t *d_offsets, const float *d_P3Dw, const float *d_P2D,
+                                      const float *d_sigma2, const orbfe_pnp_set *d_sets, const int32_t *d_draws, int32_t nsets,
+                                      orbfe_pnp_state *d_state, uint8_t *d_best_mask, orbfe_pnp_result *d_result, uint8_t *d_mask,
+                                      const int32_t *d_keypoint_index, uint8_t *d_key_mask, void *stream);
+/* The constructor on DEVICE data: d_keys the frame's undistorted keypoints (mvKeysUn, ORBFE keypoint records of 28 bytes, pt and
+ * octave are read), d_level_sigma2 [n_levels] (mvLevelSigma2), d_mappoint_index [n_keys] the map point of each keypoint (-1 =
+ * none or bad; an index >= n_mappoints or an octave outside the levels counts as none), d_mappoint_pos [n_mappoints][3]
+ * (GetWorldPos).  Writes mvP2D, mvSigma2, mvP3Dw and mvKeyPointIndices compacted in keypoint order, at most `capacity` of them,
+ * and *d_count.  One launch on `stream`, no synchronisation. */
+orbfe_status orbfe_pnp_prepare_device(orbfe_pnp *h, const void *d_keys, int32_t n_keys, const float *d_level_sigma2, int32_t n_levels,
+                                      const int32_t *d_mappoint_index, const float *d_mappoint_pos, int32_t n_mappoints, float *d_P2D,
+                                      float *d_sigma2, float *d_P3Dw, int32_t *d_keypoint_index, int32_t *d_count, int32_t capacity,
+                                      void *stream);
+/* Test taps, as orbfe_sim3_tap: allocated by the first orbfe_pnp_set_tap_iteration, then recorded for the first
+ * ORBFE_PNP_TAP_SETS sets of every call:
+ *   0 ORBFE_PNP_TAP_ITERATIONS  one orbfe_pnp_iter per iteration run (the first ORBFE_PNP_TAP_ITERS of them); *count = records
+ *   1 ORBFE_PNP_TAP_ERRORS      error2 of CheckInliers, float [n], of the iteration (counted within the call) chosen with
+ *                               orbfe_pnp_set_tap_iteration BEFORE the call (default 0); ORBFE_ERR_STATE if it was not run */
+#define ORBFE_PNP_TAP_SETS 32
+#define ORBFE_PNP_TAP_ITERS 512
+enum { ORBFE_PNP_TAP_ITERATIONS = 0, ORBFE_PNP_TAP_ERRORS = 1 };
+orbfe_status orbfe_pnp_set_tap_iteration(orbfe_pnp *h, int32_t iteration);
+orbfe_status orbfe_pnp_tap(orbfe_pnp *h, int32_t set, int32_t stage, void *dst, size_t cap, int32_t *count);
+/* Known-answer runs of the device primitives on the caller's current device, doubles in and out, n items:
+ *   0..4  SVD of a 3x3 / 12x12 / 6x3 / 6x4 / 6x5 matrix (row-major): out = w [k], the left vectors as rows [k][m], the right
+ *         vectors as rows [k][k] -- OpenCV 3.2's JacobiSVDImpl_<double>
+ *   5..7  cvSolve(A, b, CV_SVD) on 6x3 / 6x4 / 6x5: in = A, b [6]; out = x [k]
+ *   8     cvInvert(A, CV_SVD) on 3x3
+ *   9     qr_solve on 6x4: in = A, b [6]; out = x [4], left at zeros when a column is found all zero
+ *   10    compute_pose on n correspondences (ONE item): in = fu, fv, uc, vc, then n x (X, Y, Z, u, v); out = R [9], t [3], the
+ *         error returned, N, the three rep_errors */
+enum {
+    ORBFE_PNP_KAT_SVD3 = 0, ORBFE_PNP_KAT_SVD12 = 1, ORBFE_PNP_KAT_SVD6X3 = 2, ORBFE_PNP_KAT_SVD6X4 = 3, ORBFE_PNP_KAT_SVD6X5 = 4,
+    ORBFE_PNP_KAT_SOLVE6X3 = 5, ORBFE_PNP_KAT_SOLVE6X4 = 6, ORBFE_PNP_KAT_SOLVE6X5 = 7, ORBFE_PNP_KAT_INVERT3 = 8,
+    ORBFE_PNP_KAT_QR_SOLVE = 9, ORBFE_PNP_KAT_COMPUTE_POSE = 10
+};
+orbfe_status orbfe_pnp_kat(int32_t what, int32_t n, const double *in, double *out);
+
 #ifdef __cplusplus
 }
 #endif

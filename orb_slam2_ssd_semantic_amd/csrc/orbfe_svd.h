@@ -1,0 +1,201 @@
+// orbfe_svd.h -- OpenCV 3.2's one-sided Jacobi SVD (JacobiSVDImpl_<double>, core/src/lapack.cpp) and SVBkSb, which is what
+// cvSVD, cvInvert(.., CV_SVD) and cvSolve(.., CV_SVD) resolve to on small CV_64F matrices.  Plain C++ on doubles, one operation
+// at a time, for host and device alike; the files that include this are compiled with -ffp-contract=off.  Restated by
+// tests/pnp_oracle.py (P1-P3); sizes up to SVD_MAX columns.
+#pragma once
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define ORBFE_HD __host__ __device__
+#else
+#define ORBFE_HD
+#endif
+
+constexpr int SVD_MAX = 12;
+
+// lapack.cpp's hypot template (oracle H3 / P1): no libm
+ORBFE_HD inline double svd_hypot(double a, double b)
+{
+    a = fabs(a);
+    b = fabs(b);
+    if (a > b) {
+        b /= a;
+        return a * sqrt(1 + b * b);
+    }
+    if (b > 0) {
+        a /= b;
+        return b * sqrt(1 + a * a);
+    }
+    return 0;
+}
+
+// JacobiSVDImpl_ on At (n rows of length m: the matrix transposed, m >= n), Vt n x n, W n values, n1 = n.  Afterwards the rows of
+// At are the left singular vectors, the rows of Vt the right ones, W descending.
+ORBFE_HD inline void jacobi_svd(double *At, double *W, double *Vt, int m, int n)
+{
+    const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
+    const int max_iter = m > 30 ? m : 30;
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) {
+            const double t = At[i * m + k];
+            sd += t * t;
+        }
+        W[i] = sd;
+        for (int k = 0; k < n; k++) Vt[i * n + k] = 0;
+        Vt[i * n + i] = 1;
+    }
+    for (int iter = 0; iter < max_iter; iter++) {
+        bool changed = false;
+        for (int i = 0; i < n - 1; i++)
+            for (int j = i + 1; j < n; j++) {
+                double *Ai = At + i * m, *Aj = At + j * m;
+                double a = W[i], p = 0, b = W[j];
+                for (int k = 0; k < m; k++) p += Ai[k] * Aj[k];
+                if (fabs(p) <= eps * sqrt(a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = svd_hypot(p, beta);
+                double c, s;
+                if (beta < 0) {
+                    const double delta = (gamma - beta) * 0.5;
+                    s = sqrt(delta / gamma);
+                    c = p / (gamma * s * 2);
+                } else {
+                    c = sqrt((gamma + beta) / (gamma * 2));
+                    s = p / (gamma * c * 2);
+                }
+                a = b = 0;
+                for (int k = 0; k < m; k++) {
+                    const double t0 = c * Ai[k] + s * Aj[k];
+                    const double t1 = -s * Ai[k] + c * Aj[k];
+                    Ai[k] = t0;
+                    Aj[k] = t1;
+                    a += t0 * t0;
+                    b += t1 * t1;
+                }
+                W[i] = a;
+                W[j] = b;
+                changed = true;
+                double *Vi = Vt + i * n, *Vj = Vt + j * n;
+                for (int k = 0; k < n; k++) {
+                    const double t0 = c * Vi[k] + s * Vj[k];
+                    const double t1 = -s * Vi[k] + c * Vj[k];
+                    Vi[k] = t0;
+                    Vj[k] = t1;
+                }
+            }
+        if (!changed) break;
+    }
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) {
+            const double t = At[i * m + k];
+            sd += t * t;
+        }
+        W[i] = sqrt(sd);
+    }
+    for (int i = 0; i < n - 1; i++) {
+        int j = i;
+        for (int k = i + 1; k < n; k++)
+            if (W[j] < W[k]) j = k;
+        if (i != j) {
+            double t = W[i];
+            W[i] = W[j];
+            W[j] = t;
+            for (int k = 0; k < m; k++) {
+                t = At[i * m + k];
+                At[i * m + k] = At[j * m + k];
+                At[j * m + k] = t;
+            }
+            for (int k = 0; k < n; k++) {
+                t = Vt[i * n + k];
+                Vt[i * n + k] = Vt[j * n + k];
+                Vt[j * n + k] = t;
+            }
+        }
+    }
+    uint64_t rng = 0x12345678;   // cv::RNG, one per call
+    for (int i = 0; i < n; i++) {
+        double sd = W[i];
+        for (int ii = 0; ii < 100 && sd <= minval; ii++) {
+            // a null singular value: a random vector, orthogonalised against the rows before it
+            const double val0 = 1. / m;
+            for (int k = 0; k < m; k++) {
+                rng = (uint64_t)(uint32_t)rng * 4164903690U + (uint32_t)(rng >> 32);
+                At[i * m + k] = ((uint32_t)rng & 256) != 0 ? val0 : -val0;
+            }
+            for (int iter = 0; iter < 2; iter++)
+                for (int j = 0; j < i; j++) {
+                    sd = 0;
+                    for (int k = 0; k < m; k++) sd += At[i * m + k] * At[j * m + k];
+                    double asum = 0;
+                    for (int k = 0; k < m; k++) {
+                        const double t = At[i * m + k] - sd * At[j * m + k];
+                        At[i * m + k] = t;
+                        asum += fabs(t);
+                    }
+                    asum = asum > eps * 100 ? 1 / asum : 0;
+                    for (int k = 0; k < m; k++) At[i * m + k] *= asum;
+                }
+            sd = 0;
+            for (int k = 0; k < m; k++) {
+                const double t = At[i * m + k];
+                sd += t * t;
+            }
+            sd = sqrt(sd);
+        }
+        const double s = sd > minval ? 1 / sd : 0.;
+        for (int k = 0; k < m; k++) At[i * m + k] *= s;
+    }
+}
+
+// cv::SVD::compute on A (m x n row-major, m >= n): At takes the transpose
+ORBFE_HD inline void svd_compute(const double *A, int m, int n, double *At, double *W, double *Vt)
+{
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < m; k++) At[i * m + k] = A[k * n + i];
+    jacobi_svd(At, W, Vt, m, n);
+}
+
+ORBFE_HD inline double svbksb_threshold(const double *W, int n)
+{
+    double threshold = 0;
+    for (int i = 0; i < n; i++) threshold += W[i];
+    return threshold * (DBL_EPSILON * 2);
+}
+
+// SVBkSb with one right-hand side: x = V * inv(w) * Ut * b over the factors jacobi_svd left (m >= n)
+ORBFE_HD inline void svbksb_solve(const double *Ut, const double *W, const double *Vt, int m, int n, const double *b, double *x)
+{
+    const double threshold = svbksb_threshold(W, n);
+    for (int j = 0; j < n; j++) x[j] = 0;
+    for (int i = 0; i < n; i++) {
+        double wi = W[i];
+        if (fabs(wi) <= threshold) continue;
+        wi = 1 / wi;
+        double s = 0;
+        for (int j = 0; j < m; j++) s += Ut[i * m + j] * b[j];
+        s *= wi;
+        for (int j = 0; j < n; j++) x[j] = x[j] + s * Vt[i * n + j];
+    }
+}
+
+// SVBkSb without a right-hand side on a square matrix: the pseudo-inverse, n x n row-major
+ORBFE_HD inline void svbksb_invert(const double *Ut, const double *W, const double *Vt, int n, double *x)
+{
+    const double threshold = svbksb_threshold(W, n);
+    double buffer[SVD_MAX];
+    for (int j = 0; j < n * n; j++) x[j] = 0;
+    for (int i = 0; i < n; i++) {
+        double wi = W[i];
+        if (fabs(wi) <= threshold) continue;
+        wi = 1 / wi;
+        for (int j = 0; j < n; j++) buffer[j] = Ut[i * n + j] * wi;
+        for (int r = 0; r < n; r++) {
+            const double s = Vt[i * n + r];
+            for (int j = 0; j < n; j++) x[r * n + j] = x[r * n + j] + s * buffer[j];
+        }
+    }
+}

@@ -13,6 +13,8 @@
 #define CV_32F 5
 #define CV_64F 6
 
+struct CvMat;   // the C API's matrix: include/PnPsolver.h names it in private signatures; never defined or used here
+
 namespace cv {
 struct Point2f {
     float x = 0, y = 0;
