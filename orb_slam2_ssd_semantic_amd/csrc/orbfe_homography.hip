@@ -12,8 +12,6 @@
 #include <float.h>
 #include <math.h>
 
-#include <new>
-
 #include "orbfe_common.h"
 #include "orbfe_host.h"
 #include "orbfe_jacobi.h"
@@ -611,45 +609,21 @@ static void homo_free(orbfe_homography *h)
 
 extern "C" orbfe_status orbfe_homography_create(int32_t device, int32_t max_pairs, int32_t max_sets, orbfe_homography **out)
 {
-    if (!out) return ORBFE_ERR_ARG;
-    *out = nullptr;
-    if (max_pairs < 1 || max_sets < 1 || max_pairs > (1 << 24) || max_sets > (1 << 20)) return ORBFE_ERR_ARG;
-    const orbfe_status rs = orb_resolve_device(&device);
-    if (rs != ORBFE_OK) return rs;
-    orbfe_homography *h = new (std::nothrow) orbfe_homography();
-    if (!h) return ORBFE_ERR_NOMEM;
+    orbfe_homography *h = nullptr;
+    const orbfe_status s = orb_create_begin(&device, max_pairs, max_sets, out, &h);
+    if (s != ORBFE_OK) return s;
     DeviceGuard dg(device);
-    h->device = device;
     h->max_pairs = max_pairs;
-    h->max_sets = max_sets;
     size_t np = (size_t)max_pairs, ns = (size_t)max_sets;
-    auto blk = [](auto **p, size_t bytes) { return OrbAlloc{(void **)p, bytes}; };
     const bool ok = orb_alloc_all(
-        &h->stream, {blk(&h->d_src, np * sizeof(float2)), blk(&h->d_dst, np * sizeof(float2)), blk(&h->d_mask, np),
-                     blk(&h->d_off, 2 * sizeof(int32_t)), blk(&h->d_ok, sizeof(int32_t)), blk(&h->d_H, 9 * sizeof(double)),
-                     blk(&h->d_state, ns * sizeof(int32_t)), blk(&h->d_tap_info, ns * 4 * sizeof(int32_t)),
-                     blk(&h->d_tap_ransac, ns * 9 * sizeof(double)), blk(&h->d_tap_refit, ns * 9 * sizeof(double))});
-    if (!ok) {
-        (void)hipGetLastError();
-        orbfe_set_error("orbfe_homography_create: device allocation failed");
-        homo_free(h);
-        delete h;
-        return ORBFE_ERR_NOMEM;
-    }
-    h->last_stream = h->stream;
-    *out = h;
-    return ORBFE_OK;
+        &h->stream, {orb_blk(&h->d_src, np * sizeof(float2)), orb_blk(&h->d_dst, np * sizeof(float2)), orb_blk(&h->d_mask, np),
+                     orb_blk(&h->d_off, 2 * sizeof(int32_t)), orb_blk(&h->d_ok, sizeof(int32_t)), orb_blk(&h->d_H, 9 * sizeof(double)),
+                     orb_blk(&h->d_state, ns * sizeof(int32_t)), orb_blk(&h->d_tap_info, ns * 4 * sizeof(int32_t)),
+                     orb_blk(&h->d_tap_ransac, ns * 9 * sizeof(double)), orb_blk(&h->d_tap_refit, ns * 9 * sizeof(double))});
+    return orb_create_finish(ok, "orbfe_homography_create", h, homo_free, out);
 }
 
-extern "C" void orbfe_homography_destroy(orbfe_homography *h)
-{
-    if (!h) return;
-    DeviceGuard dg(h->device);
-    (void)hipStreamSynchronize(h->last_stream);
-    (void)hipStreamSynchronize(h->stream);
-    homo_free(h);
-    delete h;
-}
+extern "C" void orbfe_homography_destroy(orbfe_homography *h) { orb_destroy(h, homo_free); }
 
 extern "C" void *orbfe_homography_get_stream(orbfe_homography *h) { return h ? (void *)h->stream : nullptr; }
 
@@ -769,9 +743,6 @@ extern "C" orbfe_status orbfe_homography_kat(int32_t what, int32_t n, const void
 {
     if (n < 0 || !out || (!in && n > 0) || what < ORBFE_HOMO_KAT_RNG || what > ORBFE_HOMO_KAT_JACOBI8) return ORBFE_ERR_ARG;
     if (n == 0) return ORBFE_OK;
-    int32_t device = -1;   // runs on the caller's current device
-    const orbfe_status rs = orb_resolve_device(&device);
-    if (rs != ORBFE_OK) return rs;
     size_t in_b = 0, out_b = 0;
     switch (what) {
     case ORBFE_HOMO_KAT_RNG: in_b = sizeof(uint64_t); out_b = (size_t)n * 4; break;
@@ -780,16 +751,8 @@ extern "C" orbfe_status orbfe_homography_kat(int32_t what, int32_t n, const void
     case ORBFE_HOMO_KAT_JACOBI9: in_b = (size_t)n * 81 * 8; out_b = (size_t)n * 90 * 8; break;
     default: in_b = (size_t)n * 64 * 8; out_b = (size_t)n * 72 * 8; break;
     }
-    void *d_in = nullptr, *d_out = nullptr;
-    ORBFE_HIP(hipMalloc(&d_in, in_b));
-    if (hipMalloc(&d_out, out_b) != hipSuccess) {
-        (void)hipFree(d_in);
-        orbfe_set_error("orbfe_homography_kat: device allocation failed");
-        return ORBFE_ERR_NOMEM;
-    }
-    hipError_t e = hipMemcpy(d_in, in, in_b, hipMemcpyHostToDevice);
-    const unsigned T = 128, B = (unsigned)((n + T - 1) / T);
-    if (e == hipSuccess) {
+    return orb_kat_run("orbfe_homography_kat", in, in_b, out, out_b, 0, [&](void *d_in, void *d_out, void *) {
+        const unsigned T = 128, B = (unsigned)((n + T - 1) / T);
         switch (what) {
         case ORBFE_HOMO_KAT_RNG: k_homo_kat_rng<<<1, 64>>>(*(const uint64_t *)in, n, (uint32_t *)d_out); break;
         case ORBFE_HOMO_KAT_HYPOT: k_homo_kat_hypot<<<B, T>>>(n, (const double *)d_in, (double *)d_out); break;
@@ -797,14 +760,5 @@ extern "C" orbfe_status orbfe_homography_kat(int32_t what, int32_t n, const void
         case ORBFE_HOMO_KAT_JACOBI9: k_homo_kat_jacobi<9><<<B, T>>>(n, (double *)d_in, (double *)d_out); break;
         default: k_homo_kat_jacobi<8><<<B, T>>>(n, (double *)d_in, (double *)d_out); break;
         }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) {
-        orbfe_set_error("orbfe_homography_kat: %s", hipGetErrorString(e));
-        return ORBFE_ERR_HIP;
-    }
-    return ORBFE_OK;
+    });
 }

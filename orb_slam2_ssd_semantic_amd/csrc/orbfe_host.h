@@ -1,9 +1,11 @@
 // orbfe_host.h -- the host scaffold every handle of liborbfe.so is built from: the device guard, "which device", the grow-only
-// device / pinned buffers and the allocate-all / free-all pair of the fixed-size handles.  Host code only; include after
-// orbfe_common.h.
+// device / pinned buffers, the allocate-all / free-all pair of the fixed-size handles with the head and tail of their create
+// and the body of their destroy, and the runner of the known-answer entry points.  Host code only; include after
+// orbfe_common.h.  csrc/orbfe_ransac.h builds the RANSAC solver handles on top of it.
 #pragma once
 
 #include <initializer_list>
+#include <new>
 
 #include "orbfe_common.h"
 
@@ -110,25 +112,108 @@ struct PinBuf {
     }
 };
 
-// The fixed-size handles (orbfe_flow, orbfe_homography) allocate everything in create: a stream of their own plus a list of
-// device blocks.  orb_alloc_all stops at the first failure; the caller then frees what there is with orb_free_all (its own
-// list of the same pointers, also what destroy uses) and answers ORBFE_ERR_NOMEM.
+// The fixed-size handles (orbfe_flow, orbfe_homography, orbfe_sim3, orbfe_pnp) allocate everything in create: a stream of
+// their own plus a list of device blocks.  orb_alloc_all stops at the first failure; orb_create_finish then frees what there
+// is through the handle's free function (orb_free_all over the same pointers, also what destroy uses) and answers
+// ORBFE_ERR_NOMEM.
 struct OrbAlloc {
     void **p;
     size_t bytes;
 };
 
-inline bool orb_alloc_all(hipStream_t *stream, std::initializer_list<OrbAlloc> blocks)
+template <class T>
+inline OrbAlloc orb_blk(T **p, size_t bytes) { return OrbAlloc{(void **)p, bytes}; }
+
+inline bool orb_alloc_all(hipStream_t *stream, const OrbAlloc *blocks, size_t count)
 {
     if (hipStreamCreateWithFlags(stream, hipStreamNonBlocking) != hipSuccess) return false;
-    for (const OrbAlloc &a : blocks)
-        if (hipMalloc(a.p, a.bytes) != hipSuccess) return false;
+    for (size_t i = 0; i < count; i++)
+        if (hipMalloc(blocks[i].p, blocks[i].bytes) != hipSuccess) return false;
     return true;
 }
+
+inline bool orb_alloc_all(hipStream_t *stream, std::initializer_list<OrbAlloc> blocks) { return orb_alloc_all(stream, blocks.begin(), blocks.size()); }
 
 inline void orb_free_all(hipStream_t stream, std::initializer_list<void *> blocks)
 {
     for (void *p : blocks)
         if (p) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
+}
+
+// The head of create for the handles sized by (points, sets): the argument limits, the device, the handle itself with `device`
+// and `max_sets` set.  The caller sets its DeviceGuard, allocates, and ends with orb_create_finish.
+constexpr int32_t ORB_MAX_POINTS = 1 << 24, ORB_MAX_SETS = 1 << 20;
+
+template <class H>
+orbfe_status orb_create_begin(int32_t *device, int32_t max_points, int32_t max_sets, H **out, H **h)
+{
+    if (!out) return ORBFE_ERR_ARG;
+    *out = nullptr;
+    if (max_points < 1 || max_sets < 1 || max_points > ORB_MAX_POINTS || max_sets > ORB_MAX_SETS) return ORBFE_ERR_ARG;
+    const orbfe_status rs = orb_resolve_device(device);
+    if (rs != ORBFE_OK) return rs;
+    *h = new (std::nothrow) H();
+    if (!*h) return ORBFE_ERR_NOMEM;
+    (*h)->device = *device;
+    (*h)->max_sets = max_sets;
+    return ORBFE_OK;
+}
+
+// The tail of create for any handle with `stream` and `last_stream`: ok is what orb_alloc_all answered, free_blocks the
+// handle's free function (the one destroy uses: it skips the blocks that were never allocated).
+template <class H>
+orbfe_status orb_create_finish(bool ok, const char *name, H *h, void (*free_blocks)(H *), H **out)
+{
+    if (!ok) {
+        (void)hipGetLastError();
+        orbfe_set_error("%s: device allocation failed", name);
+        free_blocks(h);
+        delete h;
+        return ORBFE_ERR_NOMEM;
+    }
+    h->last_stream = h->stream;
+    *out = h;
+    return ORBFE_OK;
+}
+
+// destroy: work of the last call may still run on the caller's stream (last_stream) or on the handle's own
+template <class H>
+void orb_destroy(H *h, void (*free_blocks)(H *))
+{
+    if (!h) return;
+    DeviceGuard dg(h->device);
+    (void)hipStreamSynchronize(h->last_stream);
+    (void)hipStreamSynchronize(h->stream);
+    free_blocks(h);
+    delete h;
+}
+
+// A known-answer entry point (*_kat) on the caller's current device: in_b bytes of `in` go to the device, launch(d_in, d_out,
+// d_ws) enqueues the kernel on the null stream (d_ws: ws_b bytes of workspace, nullptr for 0), out_b bytes come back.  A
+// failed allocation answers ORBFE_ERR_NOMEM, any other runtime failure ORBFE_ERR_HIP, as create does: error text set, the
+// runtime's sticky error cleared.
+template <class Launch>
+orbfe_status orb_kat_run(const char *name, const void *in, size_t in_b, void *out, size_t out_b, size_t ws_b, Launch launch)
+{
+    int32_t device = -1;
+    const orbfe_status rs = orb_resolve_device(&device);
+    if (rs != ORBFE_OK) return rs;
+    void *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr;
+    hipError_t e = hipMalloc(&d_in, in_b);
+    if (e == hipSuccess) e = hipMalloc(&d_out, out_b);
+    if (e == hipSuccess && ws_b) e = hipMalloc(&d_ws, ws_b);
+    const bool nomem = e != hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch(d_in, d_out, d_ws);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost);
+    for (void *p : {d_in, d_out, d_ws})
+        if (p) (void)hipFree(p);
+    if (e == hipSuccess) return ORBFE_OK;
+    (void)hipGetLastError();
+    orbfe_set_error("%s: %s", name, nomem ? "device allocation failed" : hipGetErrorString(e));
+    return nomem ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP;
 }

@@ -10,13 +10,13 @@
 //                  Refine runs once per best mask, cooperatively: per-point steps one point per lane, every sum one entry per
 //                  lane walking the inliers in index order, the SVDs and beta solves on lane 0.
 //   k_pnp_prepare  the constructor: ordered compaction of the keypoints that have a usable map point.
+// The handle, its taps and the host form's round trip are csrc/orbfe_ransac.h; here are the solver's own arrays, the argument
+// checks and the kernels.
 #include <float.h>
 #include <math.h>
 
-#include <new>
-
 #include "orbfe_common.h"
-#include "orbfe_host.h"
+#include "orbfe_ransac.h"
 #include "orbfe_epnp.h"
 
 namespace {
@@ -25,8 +25,6 @@ constexpr int PN_K = 64;    // hypotheses per chunk: one wave, one lane each
 constexpr int PN_T = 256;   // k_pnp_ransac workgroup
 constexpr int PN_MAX_ITERATIONS = 1 << 20;
 constexpr int PN_SLAB = 13;   // doubles of Refine's workspace per correspondence: pws 3, us 2, alphas 4, pcs 3, reprojection term 1
-
-__device__ inline int index_from_draw(int32_t r, int size) { return (int)(((double)(r & 0x7fffffff) / 2147483648.0) * (double)size); }
 
 // the four swap-with-back / pop-back selections out of a fresh 0 .. n-1 (n >= 4) without the list: only the positions that took
 // the back element differ from their index, and a later write to a position hides an earlier one
@@ -91,7 +89,7 @@ struct PnArgs {
     uint8_t *key_mask;
     double *slab;      // [max_points][PN_SLAB]: Refine's per-correspondence workspace
     int32_t *ridx;     // [max_points]: Refine's index list
-    int max_points;
+    int max_points;    // bounds all sets of a batch together
     orbfe_pnp_iter *tap_iter;   // [tap_sets][ORBFE_PNP_TAP_ITERS]
     float *tap_err;             // [tap_sets][max_points]
     int32_t *tap_info;          // [tap_sets][2]: iterations run, points of the set
@@ -448,85 +446,34 @@ __global__ void k_pnp_kat_pose(int n, const double *in, double *out, double *ws)
 
 }  // namespace
 
-struct orbfe_pnp {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t last_stream = nullptr;
-    int max_points = 0, max_sets = 0;
-    int tap_cap = 0;         // sets the taps cover; 0 until orbfe_pnp_set_tap_iteration allocates them
-    int tap_sets = 0;        // sets of the last call the taps cover
-    int tap_iteration = 0;   // the iteration whose errors the next call records
-    int tap_launched = 0;    // ... and the one the last call recorded
-    float *d_P3 = nullptr, *d_P2 = nullptr, *d_sig = nullptr, *d_tap_err = nullptr;
+struct orbfe_pnp : RansacHandle {
+    float *d_P3 = nullptr, *d_P2 = nullptr, *d_sig = nullptr;
     double *d_slab = nullptr;
-    uint8_t *d_best_mask = nullptr, *d_mask = nullptr;
-    int32_t *d_off = nullptr, *d_ridx = nullptr, *d_tap_info = nullptr;
-    orbfe_pnp_set *d_set = nullptr;
-    orbfe_pnp_state *d_state = nullptr;
-    orbfe_pnp_result *d_result = nullptr;
-    orbfe_pnp_iter *d_tap_iter = nullptr;
-    DevBuf draws;
+    int32_t *d_ridx = nullptr;
+    std::vector<OrbAlloc> blocks(size_t np)
+    {
+        return {orb_blk(&d_P3, np * 12), orb_blk(&d_P2, np * 8), orb_blk(&d_sig, np * 4), orb_blk(&d_slab, np * PN_SLAB * sizeof(double)),
+                orb_blk(&d_ridx, np * 4)};
+    }
 };
 
-static void pnp_free(orbfe_pnp *h)
-{
-    h->draws.release();
-    orb_free_all(h->stream, {h->d_P3, h->d_P2, h->d_sig, h->d_tap_err, h->d_slab, h->d_best_mask, h->d_mask, h->d_off, h->d_ridx,
-                             h->d_tap_info, h->d_set, h->d_state, h->d_result, h->d_tap_iter});
-}
+static const RansacSizes PN_SIZES = {sizeof(orbfe_pnp_set), sizeof(orbfe_pnp_state), sizeof(orbfe_pnp_result), sizeof(orbfe_pnp_iter), 1,
+                                     ORBFE_PNP_TAP_SETS, ORBFE_PNP_TAP_ITERS};
 
 extern "C" orbfe_status orbfe_pnp_create(int32_t device, int32_t max_points, int32_t max_sets, orbfe_pnp **out)
 {
-    if (!out) return ORBFE_ERR_ARG;
-    *out = nullptr;
-    if (max_points < 1 || max_sets < 1 || max_points > (1 << 24) || max_sets > (1 << 20)) return ORBFE_ERR_ARG;
-    const orbfe_status rs = orb_resolve_device(&device);
-    if (rs != ORBFE_OK) return rs;
-    orbfe_pnp *h = new (std::nothrow) orbfe_pnp();
-    if (!h) return ORBFE_ERR_NOMEM;
-    DeviceGuard dg(device);
-    h->device = device;
-    h->max_points = max_points;
-    h->max_sets = max_sets;
-    const size_t np = (size_t)max_points;
-    auto blk = [](auto **p, size_t bytes) { return OrbAlloc{(void **)p, bytes}; };
-    const bool ok = orb_alloc_all(
-        &h->stream, {blk(&h->d_P3, np * 12), blk(&h->d_P2, np * 8), blk(&h->d_sig, np * 4), blk(&h->d_slab, np * PN_SLAB * sizeof(double)),
-                     blk(&h->d_ridx, np * 4), blk(&h->d_best_mask, np), blk(&h->d_mask, np), blk(&h->d_off, 2 * sizeof(int32_t)),
-                     blk(&h->d_set, sizeof(orbfe_pnp_set)), blk(&h->d_state, sizeof(orbfe_pnp_state)),
-                     blk(&h->d_result, sizeof(orbfe_pnp_result))});
-    if (!ok) {
-        (void)hipGetLastError();
-        orbfe_set_error("orbfe_pnp_create: device allocation failed");
-        pnp_free(h);
-        delete h;
-        return ORBFE_ERR_NOMEM;
-    }
-    h->last_stream = h->stream;
-    *out = h;
-    return ORBFE_OK;
+    return ransac_create("orbfe_pnp_create", PN_SIZES, device, max_points, max_sets, out);
 }
 
-extern "C" void orbfe_pnp_destroy(orbfe_pnp *h)
-{
-    if (!h) return;
-    DeviceGuard dg(h->device);
-    (void)hipStreamSynchronize(h->last_stream);
-    (void)hipStreamSynchronize(h->stream);
-    pnp_free(h);
-    delete h;
-}
+extern "C" void orbfe_pnp_destroy(orbfe_pnp *h) { orb_destroy(h, ransac_free<orbfe_pnp>); }
 
 extern "C" void *orbfe_pnp_get_stream(orbfe_pnp *h) { return h ? (void *)h->stream : nullptr; }
-
-// what the x86-64 conversion of the reference gives for a double outside int's range or a NaN
-static int32_t pnp_to_int(double v) { return v > -2147483649.0 && v < 2147483648.0 ? (int32_t)v : INT32_MIN; }
 
 extern "C" orbfe_status orbfe_pnp_ransac_params(double probability, int32_t min_inliers, int32_t max_its, int32_t min_set, float epsilon,
                                                 int32_t n, orbfe_pnp_params *out)
 {
     if (!out) return ORBFE_ERR_ARG;
-    int32_t n_min = pnp_to_int((double)((float)n * epsilon));
+    int32_t n_min = x86_double_to_int((double)((float)n * epsilon));
     if (n_min < min_inliers) n_min = min_inliers;
     if (n_min < min_set) n_min = min_set;
     if (epsilon < (float)n_min / (float)n) epsilon = (float)n_min / (float)n;
@@ -534,7 +481,7 @@ extern "C" orbfe_status orbfe_pnp_ransac_params(double probability, int32_t min_
     if (n_min == n)
         its = 1;
     else
-        its = pnp_to_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
+        its = x86_double_to_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
     if (its > max_its) its = max_its;
     if (its < 1) its = 1;
     out->min_inliers = n_min;
@@ -561,15 +508,7 @@ static orbfe_status pnp_launch(orbfe_pnp *h, PnArgs &a, int nsets, hipStream_t s
 {
     a.slab = h->d_slab;
     a.ridx = h->d_ridx;
-    a.max_points = h->max_points;
-    a.tap_iter = h->d_tap_iter;
-    a.tap_err = h->d_tap_err;
-    a.tap_info = h->d_tap_info;
-    a.tap_sets = nsets < h->tap_cap ? nsets : h->tap_cap;
-    a.tap_iteration = h->tap_iteration;
-    h->last_stream = st;
-    h->tap_sets = a.tap_sets;
-    h->tap_launched = a.tap_iteration;
+    ransac_bind_taps(h, a, nsets, st);
     if (nsets == 0) return ORBFE_OK;
     k_pnp_ransac<<<nsets, PN_T, 0, st>>>(a);
     ORBFE_HIP(hipGetLastError());
@@ -599,45 +538,16 @@ extern "C" orbfe_status orbfe_pnp_iterate(orbfe_pnp *h, const float *P3Dw, const
         return ORBFE_ERR_ARG;
     }
     DeviceGuard dg(h->device);
-    hipStream_t st = h->stream;
-    const size_t nd = 4 * (size_t)total;
-    ORBFE_HIP(h->draws.ensure((nd ? nd : 1) * sizeof(int32_t)));
     orbfe_pnp_set set = {};
     for (int k = 0; k < 4; k++) set.K[k] = K[k];
     set.params = *params;
     set.n_iterations = n_iterations;
-    const int32_t off[2] = {0, n};
-    ORBFE_HIP(hipMemcpyAsync(h->d_off, off, sizeof(off), hipMemcpyHostToDevice, st));
-    ORBFE_HIP(hipMemcpyAsync(h->d_set, &set, sizeof(set), hipMemcpyHostToDevice, st));
-    ORBFE_HIP(hipMemcpyAsync(h->d_state, state, sizeof(*state), hipMemcpyHostToDevice, st));
-    if (nd) ORBFE_HIP(hipMemcpyAsync(h->draws.p, draws, nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (n > 0) {
-        ORBFE_HIP(hipMemcpyAsync(h->d_P3, P3Dw, (size_t)n * 12, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_P2, P2D, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_sig, sigma2, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_best_mask, best_mask, (size_t)n, hipMemcpyHostToDevice, st));
-    }
     PnArgs a = {};
-    a.off = h->d_off;
     a.P3 = h->d_P3;
     a.P2 = h->d_P2;
     a.sig = h->d_sig;
-    a.sets = h->d_set;
-    a.draws = h->draws.as<int32_t>();
-    a.state = h->d_state;
-    a.best_mask = h->d_best_mask;
-    a.result = h->d_result;
-    a.mask = h->d_mask;
-    const orbfe_status s = pnp_launch(h, a, 1, st);
-    if (s != ORBFE_OK) return s;
-    ORBFE_HIP(hipMemcpyAsync(state, h->d_state, sizeof(*state), hipMemcpyDeviceToHost, st));
-    ORBFE_HIP(hipMemcpyAsync(result, h->d_result, sizeof(*result), hipMemcpyDeviceToHost, st));
-    if (n > 0) {
-        ORBFE_HIP(hipMemcpyAsync(best_mask, h->d_best_mask, (size_t)n, hipMemcpyDeviceToHost, st));
-        if (mask) ORBFE_HIP(hipMemcpyAsync(mask, h->d_mask, (size_t)n, hipMemcpyDeviceToHost, st));
-    }
-    ORBFE_HIP(hipStreamSynchronize(st));
-    return ORBFE_OK;
+    return ransac_host_call(h, PN_SIZES, a, pnp_launch, n, &set, state, draws, 4 * (size_t)total,
+                            {{h->d_P3, P3Dw, 12}, {h->d_P2, P2D, 8}, {h->d_sig, sigma2, 4}}, best_mask, result, mask);
 }
 
 extern "C" orbfe_status orbfe_pnp_iterate_device(orbfe_pnp *h, const int32_t *d_offsets, const float *d_P3Dw, const float *d_P2D,
@@ -698,92 +608,30 @@ extern "C" orbfe_status orbfe_pnp_prepare_device(orbfe_pnp *h, const void *d_key
 
 extern "C" orbfe_status orbfe_pnp_set_tap_iteration(orbfe_pnp *h, int32_t iteration)
 {
-    if (!h || iteration < 0) return ORBFE_ERR_ARG;
-    if (!h->tap_cap) {   // the taps are test equipment: a handle that never asks for them neither holds nor writes them
-        const size_t nt = (size_t)(h->max_sets < ORBFE_PNP_TAP_SETS ? h->max_sets : ORBFE_PNP_TAP_SETS), np = (size_t)h->max_points;
-        DeviceGuard dg(h->device);
-        if (hipMalloc((void **)&h->d_tap_info, nt * 2 * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void **)&h->d_tap_err, nt * np * sizeof(float)) != hipSuccess ||
-            hipMalloc((void **)&h->d_tap_iter, nt * ORBFE_PNP_TAP_ITERS * sizeof(orbfe_pnp_iter)) != hipSuccess) {
-            (void)hipGetLastError();
-            for (void **p : {(void **)&h->d_tap_info, (void **)&h->d_tap_err, (void **)&h->d_tap_iter}) {
-                if (*p) (void)hipFree(*p);
-                *p = nullptr;
-            }
-            orbfe_set_error("orbfe_pnp_set_tap_iteration: device allocation of the taps failed");
-            return ORBFE_ERR_NOMEM;
-        }
-        h->tap_cap = (int)nt;
-    }
-    h->tap_iteration = iteration;
-    return ORBFE_OK;
+    return ransac_set_tap_iteration(h, PN_SIZES, "orbfe_pnp_set_tap_iteration", iteration);
 }
 
 extern "C" orbfe_status orbfe_pnp_tap(orbfe_pnp *h, int32_t set, int32_t stage, void *dst, size_t cap, int32_t *count)
 {
     if (!h || !dst || !count || stage < ORBFE_PNP_TAP_ITERATIONS || stage > ORBFE_PNP_TAP_ERRORS) return ORBFE_ERR_ARG;
-    if (set < 0 || set >= h->tap_sets) return ORBFE_ERR_STATE;
-    DeviceGuard dg(h->device);
-    ORBFE_HIP(hipStreamSynchronize(h->last_stream));
-    int32_t info[2];
-    ORBFE_HIP(hipMemcpy(info, h->d_tap_info + 2 * (size_t)set, sizeof(info), hipMemcpyDeviceToHost));
-    if (stage == ORBFE_PNP_TAP_ITERATIONS) {
-        const int32_t k = info[0] < ORBFE_PNP_TAP_ITERS ? info[0] : ORBFE_PNP_TAP_ITERS;
-        if (cap < (size_t)k * sizeof(orbfe_pnp_iter)) return ORBFE_ERR_CAP;
-        if (k > 0)
-            ORBFE_HIP(hipMemcpy(dst, h->d_tap_iter + (size_t)set * ORBFE_PNP_TAP_ITERS, (size_t)k * sizeof(orbfe_pnp_iter), hipMemcpyDeviceToHost));
-        *count = k;
-        return ORBFE_OK;
-    }
-    if (h->tap_launched >= info[0]) return ORBFE_ERR_STATE;   // that iteration was not run
-    const int32_t n = info[1];
-    if (cap < (size_t)n * sizeof(float)) return ORBFE_ERR_CAP;
-    if (n > 0) ORBFE_HIP(hipMemcpy(dst, h->d_tap_err + (size_t)set * h->max_points, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    *count = n;
-    return ORBFE_OK;
+    return ransac_tap(h, PN_SIZES, set, stage == ORBFE_PNP_TAP_ITERATIONS, dst, cap, count);
 }
 
 extern "C" orbfe_status orbfe_pnp_kat(int32_t what, int32_t n, const double *in, double *out)
 {
     if (n < 0 || !out || (!in && n > 0) || what < ORBFE_PNP_KAT_SVD3 || what > ORBFE_PNP_KAT_COMPUTE_POSE) return ORBFE_ERR_ARG;
     if (n == 0) return ORBFE_OK;
-    if (what == ORBFE_PNP_KAT_COMPUTE_POSE && n < 1) return ORBFE_ERR_ARG;
-    int32_t device = -1;   // runs on the caller's current device
-    const orbfe_status rs = orb_resolve_device(&device);
-    if (rs != ORBFE_OK) return rs;
-    size_t in_b, out_b, ws_b = 0;
-    if (what == ORBFE_PNP_KAT_COMPUTE_POSE) {
-        in_b = (4 + 5 * (size_t)n) * sizeof(double);
-        out_b = 17 * sizeof(double);
-        ws_b = (size_t)n * PN_SLAB * sizeof(double);
-    } else {
-        int id, od;
-        epnp_kat_sizes(what, &id, &od);
-        in_b = (size_t)n * id * sizeof(double);
-        out_b = (size_t)n * od * sizeof(double);
-    }
-    void *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr;
-    hipError_t e = hipMalloc(&d_in, in_b);
-    if (e == hipSuccess) e = hipMalloc(&d_out, out_b);
-    if (e == hipSuccess && ws_b) e = hipMalloc(&d_ws, ws_b);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_b, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        if (what == ORBFE_PNP_KAT_COMPUTE_POSE) {
+    const bool pose = what == ORBFE_PNP_KAT_COMPUTE_POSE;
+    int id = 0, od = 0;
+    if (!pose) epnp_kat_sizes(what, &id, &od);
+    const size_t in_b = (pose ? 4 + 5 * (size_t)n : (size_t)n * id) * sizeof(double);
+    const size_t out_b = (pose ? 17 : (size_t)n * od) * sizeof(double);
+    const size_t ws_b = pose ? (size_t)n * PN_SLAB * sizeof(double) : 0;
+    return orb_kat_run("orbfe_pnp_kat", in, in_b, out, out_b, ws_b, [&](void *d_in, void *d_out, void *d_ws) {
+        const unsigned T = 64, B = (unsigned)((n + T - 1) / T);
+        if (pose)
             k_pnp_kat_pose<<<1, 64>>>(n, (const double *)d_in, (double *)d_out, (double *)d_ws);
-        } else {
-            const unsigned T = 64, B = (unsigned)((n + T - 1) / T);
+        else
             k_pnp_kat<<<B, T>>>(what, n, (const double *)d_in, (double *)d_out);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_ws) (void)hipFree(d_ws);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        orbfe_set_error("orbfe_pnp_kat: %s", hipGetErrorString(e));
-        return ORBFE_ERR_HIP;
-    }
-    return ORBFE_OK;
+    });
 }

@@ -9,13 +9,13 @@
 //                   lane 0 replays the acceptance rule in iteration order and stops at the first return.  The best mask is
 //                   recomputed from the best model.
 //   k_sim3_prepare  the constructor's Rcw * Xw + tcw for both keyframes.
+// The handle, its taps and the host form's round trip are csrc/orbfe_ransac.h; here are the solver's own arrays, the argument
+// checks and the kernels.
 #include <float.h>
 #include <math.h>
 
-#include <new>
-
 #include "orbfe_common.h"
-#include "orbfe_host.h"
+#include "orbfe_ransac.h"
 #include "orbfe_jacobi.h"
 
 namespace {
@@ -262,8 +262,6 @@ __device__ void compute_sim3(const float *P1, const float *P2, bool fix_scale, f
 }
 
 // ---- draws, projection ---------------------------------------------------------------------------------------------------------
-__device__ inline int index_from_draw(int32_t r, int size) { return (int)(((double)(r & 0x7fffffff) / 2147483648.0) * (double)size); }
-
 // the three swap-with-back / pop-back selections out of 0 .. n-1 (n >= 3) without the list: after the first removal position
 // p0 holds n-1; after the second, position p1 holds what position n-2 held
 __device__ inline void triple_from_draws(const int32_t *d, int n, int *tri)
@@ -334,9 +332,9 @@ struct SmArgs {
     uint8_t *mask;
     const int32_t *idx1;
     uint8_t *key_mask;
-    int max_pairs;
+    int max_points;              // bounds one set
     orbfe_sim3_iter *tap_iter;   // [tap_sets][ORBFE_SIM3_TAP_ITERS]
-    float *tap_err;              // [tap_sets][max_pairs][2]
+    float *tap_err;              // [tap_sets][max_points][2]
     int32_t *tap_info;           // [tap_sets][2]: iterations run, pairs of the set
     int tap_sets, tap_iteration;
 };
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(SM_T) void k_sim3_ransac(SmArgs a)
         a.tap_info[2 * set] = 0;
         a.tap_info[2 * set + 1] = 0;
     }
-    if (n < 0 || n > a.max_pairs) {   // nothing but these four words is written
+    if (n < 0 || n > a.max_points) {   // nothing but these four words is written
         if (tid == 0) {
             res->found = 0;
             res->no_more = 1;
@@ -435,7 +433,7 @@ __global__ __launch_bounds__(SM_T) void k_sim3_ransac(SmArgs a)
                 const unsigned long long b = __ballot(in);
                 if ((tid & 63) == 0 && b) atomicAdd(&sCnt[h], __popcll(b));
                 if (tapped && valid && base + h == a.tap_iteration) {
-                    float *te = a.tap_err + ((size_t)set * a.max_pairs + i) * 2;
+                    float *te = a.tap_err + ((size_t)set * a.max_points + i) * 2;
                     te[0] = e1;
                     te[1] = e2;
                 }
@@ -547,72 +545,20 @@ __global__ void k_sim3_kat_rotation(int n, float *A, float *out)
 
 }  // namespace
 
-struct orbfe_sim3 {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t last_stream = nullptr;
-    int max_pairs = 0, max_sets = 0;
-    int tap_cap = 0;         // sets the taps cover; 0 until orbfe_sim3_set_tap_iteration allocates them
-    int tap_sets = 0;        // sets of the last call the taps cover
-    int tap_iteration = 0;   // the iteration whose errors the next call records
-    int tap_launched = 0;    // ... and the one the last call recorded
-    float *d_X1 = nullptr, *d_X2 = nullptr, *d_sig1 = nullptr, *d_sig2 = nullptr, *d_tap_err = nullptr;
-    uint8_t *d_best_mask = nullptr, *d_mask = nullptr;
-    int32_t *d_off = nullptr, *d_tap_info = nullptr;
-    orbfe_sim3_set *d_set = nullptr;
-    orbfe_sim3_state *d_state = nullptr;
-    orbfe_sim3_result *d_result = nullptr;
-    orbfe_sim3_iter *d_tap_iter = nullptr;
-    DevBuf draws;
+struct orbfe_sim3 : RansacHandle {   // max_points is the create call's max_pairs
+    float *d_X1 = nullptr, *d_X2 = nullptr, *d_sig1 = nullptr, *d_sig2 = nullptr;
+    std::vector<OrbAlloc> blocks(size_t np) { return {orb_blk(&d_X1, np * 12), orb_blk(&d_X2, np * 12), orb_blk(&d_sig1, np * 4), orb_blk(&d_sig2, np * 4)}; }
 };
 
-static void sim3_free(orbfe_sim3 *h)
-{
-    h->draws.release();
-    orb_free_all(h->stream, {h->d_X1, h->d_X2, h->d_sig1, h->d_sig2, h->d_tap_err, h->d_best_mask, h->d_mask, h->d_off, h->d_tap_info,
-                             h->d_set, h->d_state, h->d_result, h->d_tap_iter});
-}
+static const RansacSizes SM_SIZES = {sizeof(orbfe_sim3_set), sizeof(orbfe_sim3_state), sizeof(orbfe_sim3_result), sizeof(orbfe_sim3_iter), 2,
+                                     ORBFE_SIM3_TAP_SETS, ORBFE_SIM3_TAP_ITERS};
 
 extern "C" orbfe_status orbfe_sim3_create(int32_t device, int32_t max_pairs, int32_t max_sets, orbfe_sim3 **out)
 {
-    if (!out) return ORBFE_ERR_ARG;
-    *out = nullptr;
-    if (max_pairs < 1 || max_sets < 1 || max_pairs > (1 << 24) || max_sets > (1 << 20)) return ORBFE_ERR_ARG;
-    const orbfe_status rs = orb_resolve_device(&device);
-    if (rs != ORBFE_OK) return rs;
-    orbfe_sim3 *h = new (std::nothrow) orbfe_sim3();
-    if (!h) return ORBFE_ERR_NOMEM;
-    DeviceGuard dg(device);
-    h->device = device;
-    h->max_pairs = max_pairs;
-    h->max_sets = max_sets;
-    const size_t np = (size_t)max_pairs;
-    auto blk = [](auto **p, size_t bytes) { return OrbAlloc{(void **)p, bytes}; };
-    const bool ok = orb_alloc_all(
-        &h->stream, {blk(&h->d_X1, np * 12), blk(&h->d_X2, np * 12), blk(&h->d_sig1, np * 4), blk(&h->d_sig2, np * 4), blk(&h->d_best_mask, np),
-                     blk(&h->d_mask, np), blk(&h->d_off, 2 * sizeof(int32_t)), blk(&h->d_set, sizeof(orbfe_sim3_set)),
-                     blk(&h->d_state, sizeof(orbfe_sim3_state)), blk(&h->d_result, sizeof(orbfe_sim3_result))});
-    if (!ok) {
-        (void)hipGetLastError();
-        orbfe_set_error("orbfe_sim3_create: device allocation failed");
-        sim3_free(h);
-        delete h;
-        return ORBFE_ERR_NOMEM;
-    }
-    h->last_stream = h->stream;
-    *out = h;
-    return ORBFE_OK;
+    return ransac_create("orbfe_sim3_create", SM_SIZES, device, max_pairs, max_sets, out);
 }
 
-extern "C" void orbfe_sim3_destroy(orbfe_sim3 *h)
-{
-    if (!h) return;
-    DeviceGuard dg(h->device);
-    (void)hipStreamSynchronize(h->last_stream);
-    (void)hipStreamSynchronize(h->stream);
-    sim3_free(h);
-    delete h;
-}
+extern "C" void orbfe_sim3_destroy(orbfe_sim3 *h) { orb_destroy(h, ransac_free<orbfe_sim3>); }
 
 extern "C" void *orbfe_sim3_get_stream(orbfe_sim3 *h) { return h ? (void *)h->stream : nullptr; }
 
@@ -620,28 +566,14 @@ extern "C" int32_t orbfe_sim3_ransac_iterations(double probability, int32_t min_
 {
     if (n <= 0) return 1;
     const float epsilon = (float)min_inliers / (float)n;
-    long long its;
-    if (min_inliers == n) {
-        its = 1;
-    } else {
-        const double v = ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3)));
-        its = v > -2147483648.0 && v < 2147483648.0 ? (long long)v : -2147483648LL;   // what the x86-64 conversion of the reference gives
-    }
+    int32_t its = min_inliers == n ? 1 : x86_double_to_int(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
     if (its > max_its) its = max_its;
-    return its < 1 ? 1 : (int32_t)its;
+    return its < 1 ? 1 : its;
 }
 
 static orbfe_status sim3_launch(orbfe_sim3 *h, SmArgs &a, int nsets, hipStream_t st)
 {
-    a.max_pairs = h->max_pairs;
-    a.tap_iter = h->d_tap_iter;
-    a.tap_err = h->d_tap_err;
-    a.tap_info = h->d_tap_info;
-    a.tap_sets = nsets < h->tap_cap ? nsets : h->tap_cap;
-    a.tap_iteration = h->tap_iteration;
-    h->last_stream = st;
-    h->tap_sets = a.tap_sets;
-    h->tap_launched = a.tap_iteration;
+    ransac_bind_taps(h, a, nsets, st);
     if (nsets == 0) return ORBFE_OK;
     k_sim3_ransac<<<nsets, SM_T, 0, st>>>(a);
     ORBFE_HIP(hipGetLastError());
@@ -657,8 +589,8 @@ extern "C" orbfe_status orbfe_sim3_iterate(orbfe_sim3 *h, const float *X1, const
         orbfe_set_error("orbfe_sim3_iterate: a required pointer is NULL or n < 0");
         return ORBFE_ERR_ARG;
     }
-    if (n > h->max_pairs) {
-        orbfe_set_error("%d pairs exceed max_pairs %d", n, h->max_pairs);
+    if (n > h->max_points) {
+        orbfe_set_error("%d pairs exceed max_pairs %d", n, h->max_points);
         return ORBFE_ERR_ARG;
     }
     if (n_iterations < 0 || n_iterations > SM_MAX_ITERATIONS || (n_iterations > 0 && !draws)) {
@@ -670,49 +602,19 @@ extern "C" orbfe_status orbfe_sim3_iterate(orbfe_sim3 *h, const float *X1, const
         return ORBFE_ERR_ARG;
     }
     DeviceGuard dg(h->device);
-    hipStream_t st = h->stream;
-    const size_t nd = 3 * (size_t)n_iterations;
-    ORBFE_HIP(h->draws.ensure((nd ? nd : 1) * sizeof(int32_t)));
     orbfe_sim3_set set = {};
     for (int k = 0; k < 4; k++) set.K1[k] = K1[k], set.K2[k] = K2[k];
     set.fix_scale = fix_scale != 0;
     set.min_inliers = min_inliers;
     set.max_its = max_its;
     set.n_iterations = n_iterations;
-    const int32_t off[2] = {0, n};
-    ORBFE_HIP(hipMemcpyAsync(h->d_off, off, sizeof(off), hipMemcpyHostToDevice, st));
-    ORBFE_HIP(hipMemcpyAsync(h->d_set, &set, sizeof(set), hipMemcpyHostToDevice, st));
-    ORBFE_HIP(hipMemcpyAsync(h->d_state, state, sizeof(*state), hipMemcpyHostToDevice, st));
-    if (nd) ORBFE_HIP(hipMemcpyAsync(h->draws.p, draws, nd * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (n > 0) {
-        ORBFE_HIP(hipMemcpyAsync(h->d_X1, X1, (size_t)n * 12, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_X2, X2, (size_t)n * 12, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_sig1, sigma2_1, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_sig2, sigma2_2, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(h->d_best_mask, best_mask, (size_t)n, hipMemcpyHostToDevice, st));
-    }
     SmArgs a = {};
-    a.off = h->d_off;
     a.X1 = h->d_X1;
     a.X2 = h->d_X2;
     a.sig1 = h->d_sig1;
     a.sig2 = h->d_sig2;
-    a.sets = h->d_set;
-    a.draws = h->draws.as<int32_t>();
-    a.state = h->d_state;
-    a.best_mask = h->d_best_mask;
-    a.result = h->d_result;
-    a.mask = h->d_mask;
-    const orbfe_status s = sim3_launch(h, a, 1, st);
-    if (s != ORBFE_OK) return s;
-    ORBFE_HIP(hipMemcpyAsync(state, h->d_state, sizeof(*state), hipMemcpyDeviceToHost, st));
-    ORBFE_HIP(hipMemcpyAsync(result, h->d_result, sizeof(*result), hipMemcpyDeviceToHost, st));
-    if (n > 0) {
-        ORBFE_HIP(hipMemcpyAsync(best_mask, h->d_best_mask, (size_t)n, hipMemcpyDeviceToHost, st));
-        if (mask) ORBFE_HIP(hipMemcpyAsync(mask, h->d_mask, (size_t)n, hipMemcpyDeviceToHost, st));
-    }
-    ORBFE_HIP(hipStreamSynchronize(st));
-    return ORBFE_OK;
+    return ransac_host_call(h, SM_SIZES, a, sim3_launch, n, &set, state, draws, 3 * (size_t)n_iterations,
+                            {{h->d_X1, X1, 12}, {h->d_X2, X2, 12}, {h->d_sig1, sigma2_1, 4}, {h->d_sig2, sigma2_2, 4}}, best_mask, result, mask);
 }
 
 extern "C" orbfe_status orbfe_sim3_iterate_device(orbfe_sim3 *h, const int32_t *d_offsets, const float *d_X1, const float *d_X2,
@@ -773,58 +675,19 @@ extern "C" orbfe_status orbfe_sim3_prepare_device(orbfe_sim3 *h, const float *d_
 
 extern "C" orbfe_status orbfe_sim3_set_tap_iteration(orbfe_sim3 *h, int32_t iteration)
 {
-    if (!h || iteration < 0) return ORBFE_ERR_ARG;
-    if (!h->tap_cap) {   // the taps are test equipment: a handle that never asks for them neither holds nor writes them
-        const size_t nt = (size_t)(h->max_sets < ORBFE_SIM3_TAP_SETS ? h->max_sets : ORBFE_SIM3_TAP_SETS), np = (size_t)h->max_pairs;
-        DeviceGuard dg(h->device);
-        if (hipMalloc((void **)&h->d_tap_info, nt * 2 * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void **)&h->d_tap_err, nt * np * 2 * sizeof(float)) != hipSuccess ||
-            hipMalloc((void **)&h->d_tap_iter, nt * ORBFE_SIM3_TAP_ITERS * sizeof(orbfe_sim3_iter)) != hipSuccess) {
-            (void)hipGetLastError();
-            for (void **p : {(void **)&h->d_tap_info, (void **)&h->d_tap_err, (void **)&h->d_tap_iter}) {
-                if (*p) (void)hipFree(*p);
-                *p = nullptr;
-            }
-            orbfe_set_error("orbfe_sim3_set_tap_iteration: device allocation of the taps failed");
-            return ORBFE_ERR_NOMEM;
-        }
-        h->tap_cap = (int)nt;
-    }
-    h->tap_iteration = iteration;
-    return ORBFE_OK;
+    return ransac_set_tap_iteration(h, SM_SIZES, "orbfe_sim3_set_tap_iteration", iteration);
 }
 
 extern "C" orbfe_status orbfe_sim3_tap(orbfe_sim3 *h, int32_t set, int32_t stage, void *dst, size_t cap, int32_t *count)
 {
     if (!h || !dst || !count || stage < ORBFE_SIM3_TAP_ITERATIONS || stage > ORBFE_SIM3_TAP_ERRORS) return ORBFE_ERR_ARG;
-    if (set < 0 || set >= h->tap_sets) return ORBFE_ERR_STATE;
-    DeviceGuard dg(h->device);
-    ORBFE_HIP(hipStreamSynchronize(h->last_stream));
-    int32_t info[2];
-    ORBFE_HIP(hipMemcpy(info, h->d_tap_info + 2 * (size_t)set, sizeof(info), hipMemcpyDeviceToHost));
-    if (stage == ORBFE_SIM3_TAP_ITERATIONS) {
-        const int32_t k = info[0] < ORBFE_SIM3_TAP_ITERS ? info[0] : ORBFE_SIM3_TAP_ITERS;
-        if (cap < (size_t)k * sizeof(orbfe_sim3_iter)) return ORBFE_ERR_CAP;
-        if (k > 0)
-            ORBFE_HIP(hipMemcpy(dst, h->d_tap_iter + (size_t)set * ORBFE_SIM3_TAP_ITERS, (size_t)k * sizeof(orbfe_sim3_iter), hipMemcpyDeviceToHost));
-        *count = k;
-        return ORBFE_OK;
-    }
-    if (h->tap_launched >= info[0]) return ORBFE_ERR_STATE;   // that iteration was not run
-    const int32_t n = info[1];
-    if (cap < (size_t)n * 2 * sizeof(float)) return ORBFE_ERR_CAP;
-    if (n > 0) ORBFE_HIP(hipMemcpy(dst, h->d_tap_err + (size_t)set * h->max_pairs * 2, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    *count = n;
-    return ORBFE_OK;
+    return ransac_tap(h, SM_SIZES, set, stage == ORBFE_SIM3_TAP_ITERATIONS, dst, cap, count);
 }
 
 extern "C" orbfe_status orbfe_sim3_kat(int32_t what, int32_t n, const void *in, void *out)
 {
     if (n < 0 || !out || (!in && n > 0) || what < ORBFE_SIM3_KAT_JACOBI4 || what > ORBFE_SIM3_KAT_ROTATION) return ORBFE_ERR_ARG;
     if (n == 0) return ORBFE_OK;
-    int32_t device = -1;   // runs on the caller's current device
-    const orbfe_status rs = orb_resolve_device(&device);
-    if (rs != ORBFE_OK) return rs;
     size_t in_b = 0, out_b = 0;
     switch (what) {
     case ORBFE_SIM3_KAT_JACOBI4: in_b = (size_t)n * 64; out_b = (size_t)n * 80; break;
@@ -832,29 +695,12 @@ extern "C" orbfe_status orbfe_sim3_kat(int32_t what, int32_t n, const void *in, 
     case ORBFE_SIM3_KAT_ROTATION: in_b = (size_t)n * 64; out_b = (size_t)n * 36; break;
     default: in_b = (size_t)n * 8; out_b = (size_t)n * 8; break;
     }
-    void *d_in = nullptr, *d_out = nullptr;
-    ORBFE_HIP(hipMalloc(&d_in, in_b));
-    if (hipMalloc(&d_out, out_b) != hipSuccess) {
-        (void)hipFree(d_in);
-        orbfe_set_error("orbfe_sim3_kat: device allocation failed");
-        return ORBFE_ERR_NOMEM;
-    }
-    hipError_t e = hipMemcpy(d_in, in, in_b, hipMemcpyHostToDevice);
-    const unsigned T = 128, B = (unsigned)((n + T - 1) / T);
-    if (e == hipSuccess) {
+    return orb_kat_run("orbfe_sim3_kat", in, in_b, out, out_b, 0, [&](void *d_in, void *d_out, void *) {
+        const unsigned T = 128, B = (unsigned)((n + T - 1) / T);
         switch (what) {
         case ORBFE_SIM3_KAT_JACOBI4: k_sim3_kat_jacobi4<<<B, T>>>(n, (float *)d_in, (float *)d_out); break;
         case ORBFE_SIM3_KAT_ROTATION: k_sim3_kat_rotation<<<B, T>>>(n, (float *)d_in, (float *)d_out); break;
         default: k_sim3_kat_trig<<<B, T>>>(what, n, (const double *)d_in, (double *)d_out); break;
         }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) {
-        orbfe_set_error("orbfe_sim3_kat: %s", hipGetErrorString(e));
-        return ORBFE_ERR_HIP;
-    }
-    return ORBFE_OK;
+    });
 }

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _ransac
 from ._ffi import Handle, stream_arg, tensor_ptr
 
 TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY, TAP_WARP = range(7)
@@ -88,10 +88,9 @@ class Flow(Handle):
                        "orbfe_flow_compute_masks_device")
             return masks, ones
         H = homographies
-        if H.dtype != torch.float64 or tuple(H.shape) != (n, 3, 3) or not H.is_cuda or not H.is_contiguous():
-            raise ValueError("homographies must be a contiguous torch float64 [n, 3, 3] on the device")
-        if use is not None and (use.dtype != torch.int32 or tuple(use.shape) != (n,) or not use.is_cuda or not use.is_contiguous()):
-            raise ValueError("use must be a contiguous torch int32 [n] on the device")
+        _ransac.check_tensor(H, torch.float64, "homographies", "float64 [n, 3, 3]", (n, 3, 3))
+        if use is not None:
+            _ransac.check_tensor(use, torch.int32, "use", "int32 [n]", (n,))
         _ffi.check(self._L.orbfe_flow_compute_masks_homo_device(self.h, tensor_ptr(frames), n, w, h, w, frames.stride(0), tensor_ptr(H),
                                                                 None if use is None else tensor_ptr(use), float(threshold), tensor_ptr(masks), w,
                                                                 masks.stride(0), tensor_ptr(ones), st),

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _ransac
 from ._ffi import Handle, stream_arg, tensor_ptr
 
 RANSAC = 8
@@ -58,9 +58,7 @@ class Homography(Handle):
         (H float64 [nsets, 3, 3], ok int32 [nsets], mask uint8 [N]) on the device; ok = result and n_i > min_pairs.  Enqueued
         on `stream` (default: torch's current stream), no synchronisation."""
         import torch
-        for t, dt, name in ((offsets, torch.int32, "offsets"), (src, torch.float32, "src"), (dst, torch.float32, "dst")):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous torch {dt} tensor on the device")
+        _ransac.check_tensors((offsets, torch.int32, "offsets"), (src, torch.float32, "src"), (dst, torch.float32, "dst"))
         nsets = offsets.numel() - 1
         dev = offsets.device
         if H is None:
@@ -91,10 +89,7 @@ def find_homography(src, dst, method=RANSAC, threshold=3.0, max_iters=2000, conf
     """cv::findHomography(src, dst, method, threshold, mask, max_iters, confidence): (H float64 [3, 3] or None, mask uint8 [n]).
     method is RANSAC (8) or 0.  One cached handle per device, grown to the largest point count seen."""
     n = len(_pairs(src))
-    h = _default.get(device)
-    if h is None or h.max_pairs < n:
-        h = _default[device] = Homography(max(n, 4096), 1, device)
-    return h.find(src, dst, method, threshold, max_iters, confidence)
+    return _ransac.default_handle(_default, Homography, "max_pairs", device, n).find(src, dst, method, threshold, max_iters, confidence)
 
 
 def kat(what, data, n=None):

@@ -1,12 +1,11 @@
 """The reference's PnPsolver (src/PnPsolver.cc) on the GPU: EPnP on four correspondences inside the RANSAC loop of `iterate`,
 Refine's EPnP over the best inliers, through the C-ABI of csrc/orbfe_pnp.hip.  The random draws are an input (raw values in
 [0, 2^31 - 1], four per iteration), so a run can be replayed.  No CPU fallback."""
-import ctypes as C
-
 import numpy as np
 
-from . import _ffi
-from ._ffi import Handle, stream_arg, tensor_ptr
+from . import _ffi, _ransac
+from ._ffi import stream_arg, tensor_ptr
+from ._ransac import TAP_ERRORS, TAP_ITERATIONS, TAP_ITERS, TAP_SETS  # noqa: F401
 
 PARAMS_DTYPE = np.dtype([("min_inliers", "<i4"), ("max_its", "<i4"), ("epsilon", "<f4"), ("th2", "<f4")])
 STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("reserved", "<i4", (2,)), ("best_Tcw", "<f4", (4, 4))])
@@ -17,8 +16,6 @@ SET_DTYPE = np.dtype([("K", "<f4", (4,)), ("params", PARAMS_DTYPE), ("n_iteratio
 ITER_DTYPE = np.dtype([("quad", "<i4", (4,)), ("N", "<i4"), ("n_inliers", "<i4"), ("refine_ran", "<i4"), ("refine_inliers", "<i4"),
                        ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])
 assert (PARAMS_DTYPE.itemsize, STATE_DTYPE.itemsize, RESULT_DTYPE.itemsize, SET_DTYPE.itemsize, ITER_DTYPE.itemsize) == (16, 80, 96, 48, 128)
-TAP_ITERATIONS, TAP_ERRORS = range(2)
-TAP_SETS, TAP_ITERS = 32, 512
 (KAT_SVD3, KAT_SVD12, KAT_SVD6X3, KAT_SVD6X4, KAT_SVD6X5, KAT_SOLVE6X3, KAT_SOLVE6X4, KAT_SOLVE6X5, KAT_INVERT3, KAT_QR_SOLVE,
  KAT_COMPUTE_POSE) = range(11)
 _KAT_SHAPE = {KAT_SVD3: (3, 3), KAT_SVD12: (12, 12), KAT_SVD6X3: (6, 3), KAT_SVD6X4: (6, 4), KAT_SVD6X5: (6, 5), KAT_SOLVE6X3: (6, 3),
@@ -39,23 +36,15 @@ def iterations(state, params, n_iterations):
     return int(_ffi.lib().orbfe_pnp_iterations(_ffi.ptr(state), _ffi.ptr(params), int(n_iterations)))
 
 
-class PnP(Handle):
+class PnP(_ransac.RansacHandle):
     """Device scratch for PnP solvers of at most max_points correspondences (host form; in the device form, of all sets of a
-    batch together) and batches of at most max_sets solvers."""
+    batch together) and batches of at most max_sets solvers.  The error tap is float32 [n]: error2."""
 
-    _HANDLE, _DESTROY = "h", "orbfe_pnp_destroy"
+    _PREFIX, ITER_DTYPE = "orbfe_pnp", ITER_DTYPE
 
     def __init__(self, max_points=4096, max_sets=64, device=0):
-        self._L = _ffi.lib()
-        self.h = C.c_void_p()
-        _ffi.check(self._L.orbfe_pnp_create(device, max_points, max_sets, C.byref(self.h)), "orbfe_pnp_create")
-        self.device = device
+        super().__init__(max_points, max_sets, device)
         self.max_points = max_points
-        self.max_sets = max_sets
-
-    @property
-    def stream(self):
-        return self._L.orbfe_pnp_get_stream(self.h)
 
     def iterate(self, P3Dw, P2D, sigma2, K, params, n_iterations, draws, state, best_mask):
         """One solver's iterate(n_iterations) on host arrays.  state (STATE_DTYPE [1]) and best_mask (uint8 [n]) are updated in
@@ -75,22 +64,10 @@ class PnP(Handle):
         k = np.ascontiguousarray(K, np.float32).reshape(4)
         res = np.zeros(1, RESULT_DTYPE)
         mask = np.zeros(n, np.uint8)
-        _ffi.check(self._L.orbfe_pnp_iterate(self.h, _ffi.ptr(P3), _ffi.ptr(P2), _ffi.ptr(sg), n, _ffi.ptr(k), _ffi.ptr(params),
-                                             int(n_iterations), _ffi.ptr(d) if len(d) else None, _ffi.ptr(state),
-                                             _ffi.ptr(best_mask) if n else None, _ffi.ptr(res), _ffi.ptr(mask) if n else None),
-                   "orbfe_pnp_iterate")
+        self._call("iterate", self.h, _ffi.ptr(P3), _ffi.ptr(P2), _ffi.ptr(sg), n, _ffi.ptr(k), _ffi.ptr(params), int(n_iterations),
+                   _ffi.ptr(d) if len(d) else None, _ffi.ptr(state), _ffi.ptr(best_mask) if n else None, _ffi.ptr(res),
+                   _ffi.ptr(mask) if n else None)
         return res[0], mask
-
-    def set_tap_iteration(self, iteration):
-        _ffi.check(self._L.orbfe_pnp_set_tap_iteration(self.h, int(iteration)), "orbfe_pnp_set_tap_iteration")
-
-    def tap(self, set_index, stage):
-        """A stage of the last call: TAP_ITERATIONS -> ITER_DTYPE [iterations run]; TAP_ERRORS -> float32 [n] error2 of the
-        iteration chosen with set_tap_iteration before the call."""
-        cnt = C.c_int32()
-        out = np.zeros(TAP_ITERS, ITER_DTYPE) if stage == TAP_ITERATIONS else np.zeros(self.max_points, np.float32)
-        _ffi.check(self._L.orbfe_pnp_tap(self.h, set_index, stage, _ffi.ptr(out), out.nbytes, C.byref(cnt)), "orbfe_pnp_tap")
-        return out[:cnt.value].copy()
 
     def iterate_device(self, offsets, P3Dw, P2D, sigma2, sets, draws, state, best_mask, result=None, mask=None, keypoint_index=None,
                        key_mask=None, stream=None):
@@ -102,11 +79,9 @@ class PnP(Handle):
         import torch
         nsets = offsets.numel() - 1
         dev = offsets.device
-        for t, dt, name in ((offsets, torch.int32, "offsets"), (P3Dw, torch.float32, "P3Dw"), (P2D, torch.float32, "P2D"),
-                            (sigma2, torch.float32, "sigma2"), (sets, torch.uint8, "sets"), (draws, torch.int32, "draws"),
-                            (state, torch.uint8, "state"), (best_mask, torch.uint8, "best_mask")):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous torch {dt} tensor on the device")
+        _ransac.check_tensors((offsets, torch.int32, "offsets"), (P3Dw, torch.float32, "P3Dw"), (P2D, torch.float32, "P2D"),
+                              (sigma2, torch.float32, "sigma2"), (sets, torch.uint8, "sets"), (draws, torch.int32, "draws"),
+                              (state, torch.uint8, "state"), (best_mask, torch.uint8, "best_mask"))
         if sets.numel() != nsets * SET_DTYPE.itemsize or state.numel() != nsets * STATE_DTYPE.itemsize:
             raise ValueError("sets / state must hold one record per set")
         if P3Dw.shape[0] > self.max_points:
@@ -115,14 +90,11 @@ class PnP(Handle):
             result = torch.zeros((nsets, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         if mask is None:
             mask = torch.zeros(max(P3Dw.shape[0], 1), dtype=torch.uint8, device=dev)
-        _ffi.check(self._L.orbfe_pnp_iterate_device(self.h, tensor_ptr(offsets), tensor_ptr(P3Dw), tensor_ptr(P2D), tensor_ptr(sigma2),
-                                                    tensor_ptr(sets), tensor_ptr(draws), nsets, tensor_ptr(state), tensor_ptr(best_mask),
-                                                    tensor_ptr(result), tensor_ptr(mask),
-                                                    tensor_ptr(keypoint_index) if keypoint_index is not None else None,
-                                                    tensor_ptr(key_mask) if key_mask is not None else None, stream_arg(dev, stream)),
-                   "orbfe_pnp_iterate_device")
+        self._call("iterate_device", self.h, tensor_ptr(offsets), tensor_ptr(P3Dw), tensor_ptr(P2D), tensor_ptr(sigma2), tensor_ptr(sets),
+                   tensor_ptr(draws), nsets, tensor_ptr(state), tensor_ptr(best_mask), tensor_ptr(result), tensor_ptr(mask),
+                   tensor_ptr(keypoint_index) if keypoint_index is not None else None,
+                   tensor_ptr(key_mask) if key_mask is not None else None, stream_arg(dev, stream))
         return result, mask[:P3Dw.shape[0]]
-
 
     def prepare_device(self, keys, level_sigma2, mappoint_index, mappoint_pos, stream=None):
         """The constructor on torch device tensors: keys uint8 [n_keys, 28] (KP_DTYPE bytes of mvKeysUn), level_sigma2 float32
@@ -130,10 +102,8 @@ class PnP(Handle):
         sigma2 [n_keys], P3Dw [n_keys, 3], keypoint_index int32 [n_keys], count int32 [1]) on the device; the first `count`
         rows are the solver's vectors, in keypoint order.  No synchronisation."""
         import torch
-        for t, dt, name in ((keys, torch.uint8, "keys"), (level_sigma2, torch.float32, "level_sigma2"),
-                            (mappoint_index, torch.int32, "mappoint_index"), (mappoint_pos, torch.float32, "mappoint_pos")):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous torch {dt} tensor on the device")
+        _ransac.check_tensors((keys, torch.uint8, "keys"), (level_sigma2, torch.float32, "level_sigma2"),
+                              (mappoint_index, torch.int32, "mappoint_index"), (mappoint_pos, torch.float32, "mappoint_pos"))
         n = mappoint_index.numel()
         if keys.numel() != n * _ffi.KP_DTYPE.itemsize:
             raise ValueError("keys must hold one 28-byte record per entry of mappoint_index")
@@ -143,10 +113,9 @@ class PnP(Handle):
         P3Dw = torch.zeros((n, 3), dtype=torch.float32, device=dev)
         kp = torch.zeros(n, dtype=torch.int32, device=dev)
         count = torch.zeros(1, dtype=torch.int32, device=dev)
-        _ffi.check(self._L.orbfe_pnp_prepare_device(self.h, tensor_ptr(keys), n, tensor_ptr(level_sigma2), level_sigma2.numel(),
-                                                    tensor_ptr(mappoint_index), tensor_ptr(mappoint_pos), mappoint_pos.shape[0],
-                                                    tensor_ptr(P2D), tensor_ptr(sigma2), tensor_ptr(P3Dw), tensor_ptr(kp), tensor_ptr(count), n,
-                                                    stream_arg(dev, stream)), "orbfe_pnp_prepare_device")
+        self._call("prepare_device", self.h, tensor_ptr(keys), n, tensor_ptr(level_sigma2), level_sigma2.numel(), tensor_ptr(mappoint_index),
+                   tensor_ptr(mappoint_pos), mappoint_pos.shape[0], tensor_ptr(P2D), tensor_ptr(sigma2), tensor_ptr(P3Dw), tensor_ptr(kp),
+                   tensor_ptr(count), n, stream_arg(dev, stream))
         return P2D, sigma2, P3Dw, kp, count
 
 
@@ -154,10 +123,7 @@ _default = {}
 
 
 def _handle(device, n):
-    h = _default.get(device)
-    if h is None or h.max_points < n:
-        h = _default[device] = PnP(max(n, 4096), 1, device)
-    return h
+    return _ransac.default_handle(_default, PnP, "max_points", device, n)
 
 
 def pnp_iterate_device(handle, offsets, P3Dw, P2D, sigma2, sets, draws, state, best_mask, **kw):
@@ -170,11 +136,13 @@ def pnp_prepare_device(handle, keys, level_sigma2, mappoint_index, mappoint_pos,
     return handle.prepare_device(keys, level_sigma2, mappoint_index, mappoint_pos, **kw)
 
 
-class PnPSolver:
+class PnPSolver(_ransac.RansacSolver):
     """Mirrors the reference's class on flattened inputs: P3Dw [n, 3] positions of the matched map points, P2D [n, 2] their
     undistorted keypoints, sigma2 [n] the level sigma^2 of each, K = (fx, fy, cx, cy).  keypoint_index / n_keys (mvKeyPointIndices /
     the size of vpMapPointMatches) make iterate's mask a per-keypoint one.  Draws come from `draws` of each call, or from `rand` (a
     callable returning k raw values in [0, 2^31 - 1]; default: a numpy generator seeded with `seed`)."""
+
+    DRAWS = 4
 
     def __init__(self, P3Dw, P2D, sigma2, K, keypoint_index=None, n_keys=None, device=0, handle=None, rand=None, seed=0):
         self.P3Dw = np.ascontiguousarray(P3Dw, np.float32).reshape(-1, 3)
@@ -182,15 +150,8 @@ class PnPSolver:
         self.sigma2 = np.ascontiguousarray(sigma2, np.float32).reshape(-1)
         self.N = len(self.P3Dw)
         self.K = K
-        self.keypoint_index = None if keypoint_index is None else np.asarray(keypoint_index, np.int64)
-        self.n_keys = self.N if n_keys is None else int(n_keys)
-        self._h = handle if handle is not None else _handle(device, self.N)
-        if rand is None:
-            rng = np.random.default_rng(seed)
-            rand = lambda k: rng.integers(0, 2 ** 31, k)   # noqa: E731
-        self._rand = rand
-        self.state = np.zeros(1, STATE_DTYPE)
-        self.best_mask = np.zeros(self.N, np.uint8)
+        self._setup(handle if handle is not None else _handle(device, self.N), STATE_DTYPE, keypoint_index, n_keys, rand, seed)
+        self.keypoint_index, self.n_keys = self._index, self._n_out
         self.set_ransac_parameters()
 
     def set_ransac_parameters(self, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991):
@@ -203,18 +164,12 @@ class PnPSolver:
         """-> (Tcw float32 [4, 4] or None, no_more, inlier mask bool [n_keys], n_inliers).  Four draws per iteration that can run
         are read (self.iterations(n_iterations) of them); self.iterations_run tells how many ran."""
         n_iterations = int(n_iterations)
-        if draws is None:
-            draws = self._rand(4 * max(self.iterations(n_iterations), 0))
+        draws = self._draws(draws, self.iterations(n_iterations))
         res, mask = self._h.iterate(self.P3Dw, self.P2D, self.sigma2, self.K, self.params, n_iterations, draws, self.state, self.best_mask)
         self.iterations_run = int(res["iterations_run"])
         self.result = res
-        inl = np.zeros(self.n_keys, bool)
-        if self.keypoint_index is None:
-            inl[:self.N] = mask.astype(bool)
-        else:
-            inl[self.keypoint_index[mask.astype(bool)]] = True
         Tcw = res["Tcw"].copy() if res["found"] else None
-        return Tcw, bool(res["no_more"]), inl, int(res["n_inliers"])
+        return Tcw, bool(res["no_more"]), self._scatter(mask), int(res["n_inliers"])
 
     def find(self, draws=None):
         Tcw, _, inl, n = self.iterate(int(self.params["max_its"][0]), draws)

@@ -6,55 +6,24 @@
 // back to the front of a per-thread queue, so the rand() stream is consumed exactly as the reference consumes it.  State lives
 // in the members the reference's header declares: mnIterations, mnBestInliers, mBestTcw, mvbBestInliers, the mRansac* values
 // (th2 in mRansacTh).  The EPnP helpers the header declares are not defined; nothing calls them.
-#include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <deque>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 struct CvMat;   // named by the header's private signatures only
 
 #include <PnPsolver.h>
 
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 namespace ORB_SLAM2
 {
 namespace
 {
-void check(orbfe_status s, const char *what)
-{
-    if (s != ORBFE_OK) throw std::runtime_error(std::string(what) + ": " + orbfe_strerror(s) + " (" + orbfe_last_error() + ")");
-}
+using namespace orbfe_shim;
 
 // one handle per thread, grown to the largest correspondence count seen
-orbfe_pnp *handle_for(int n)
-{
-    struct Holder {
-        orbfe_pnp *h = nullptr;
-        int cap = 0;
-        ~Holder() { orbfe_pnp_destroy(h); }
-    };
-    static thread_local Holder hold;
-    if (!hold.h || n > hold.cap) {
-        orbfe_pnp_destroy(hold.h);
-        hold.h = nullptr;
-        const int cap = n > 4096 ? n : 4096;
-        check(orbfe_pnp_create(-1, cap, 1, &hold.h), "orbfe_pnp_create");
-        hold.cap = cap;
-    }
-    return hold.h;
-}
-
-// draws handed to a call that it did not use, oldest first
-std::deque<int32_t> &pending()
-{
-    static thread_local std::deque<int32_t> q;
-    return q;
-}
+orbfe_pnp *handle_for(int n) { return orbfe_shim::handle_for<orbfe_pnp, orbfe_pnp_create, orbfe_pnp_destroy>(n, "orbfe_pnp_create"); }
 
 cv::Mat mat4(const float *T)
 {
@@ -144,22 +113,12 @@ cv::Mat PnPsolver::iterate(int nIterations, bool &bNoMore, std::vector<bool> &vb
         for (int e = 0; e < 16; e++) st.best_Tcw[e] = mBestTcw.at<float>(e / 4, e % 4);
     std::vector<uint8_t> best(N, 0), mask(N, 0);
     for (size_t i = 0; i < mvbBestInliers.size() && i < (size_t)N; i++) best[i] = mvbBestInliers[i];
-    std::deque<int32_t> &q = pending();
-    std::vector<int32_t> draws(4 * (size_t)orbfe_pnp_iterations(&st, &prm, nIterations));
-    for (size_t k = 0; k < draws.size(); k++) {
-        if (!q.empty()) {
-            draws[k] = q.front();
-            q.pop_front();
-        } else {
-            draws[k] = (int32_t)rand();
-        }
-    }
+    const std::vector<int32_t> draws = take_draws(4 * (size_t)orbfe_pnp_iterations(&st, &prm, nIterations));
     orbfe_pnp_result res;
     memset(&res, 0, sizeof(res));
     const orbfe_status status = orbfe_pnp_iterate(handle_for(N), P3.data(), P2.data(), mvSigma2.data(), N, K, &prm, nIterations, draws.data(), &st,
                                                   best.data(), &res, mask.data());
-    const size_t used = status == ORBFE_OK ? 4 * (size_t)res.iterations_run : 0;
-    for (size_t k = draws.size(); k > used; k--) q.push_front(draws[k - 1]);
+    give_back(draws, status == ORBFE_OK ? 4 * (size_t)res.iterations_run : 0);
     check(status, "orbfe_pnp_iterate");
     mnIterations = st.iterations;
     if (st.best_inliers > mnBestInliers) {

@@ -7,53 +7,22 @@
 // sigma^2 values are kept, as float bit patterns, in mvSigmaSquare1 / 2 (declared by the header, never used by the reference):
 // the library truncates 9.210 * sigma2 to size_t itself.  The ComputeSim3 / CheckInliers / Project helpers the header declares
 // are not defined; nothing calls them.
-#include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <deque>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 #include <Sim3Solver.h>
 
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 namespace ORB_SLAM2
 {
 namespace
 {
-void check(orbfe_status s, const char *what)
-{
-    if (s != ORBFE_OK) throw std::runtime_error(std::string(what) + ": " + orbfe_strerror(s) + " (" + orbfe_last_error() + ")");
-}
+using namespace orbfe_shim;
 
 // one handle per thread, grown to the largest correspondence count seen
-orbfe_sim3 *handle_for(int n)
-{
-    struct Holder {
-        orbfe_sim3 *h = nullptr;
-        int cap = 0;
-        ~Holder() { orbfe_sim3_destroy(h); }
-    };
-    static thread_local Holder hold;
-    if (!hold.h || n > hold.cap) {
-        orbfe_sim3_destroy(hold.h);
-        hold.h = nullptr;
-        const int cap = n > 4096 ? n : 4096;
-        check(orbfe_sim3_create(-1, cap, 1, &hold.h), "orbfe_sim3_create");
-        hold.cap = cap;
-    }
-    return hold.h;
-}
-
-// draws handed to a call that it did not use, oldest first
-std::deque<int32_t> &pending()
-{
-    static thread_local std::deque<int32_t> q;
-    return q;
-}
+orbfe_sim3 *handle_for(int n) { return orbfe_shim::handle_for<orbfe_sim3, orbfe_sim3_create, orbfe_sim3_destroy>(n, "orbfe_sim3_create"); }
 
 size_t float_bits(float v)
 {
@@ -165,21 +134,11 @@ cv::Mat Sim3Solver::iterate(int nIterations, bool &bNoMore, std::vector<bool> &v
     }
     std::vector<uint8_t> best(N, 0), mask(N, 0);
     for (size_t i = 0; i < mvbBestInliers.size() && i < (size_t)N; i++) best[i] = mvbBestInliers[i];
-    std::deque<int32_t> &q = pending();
-    std::vector<int32_t> draws(3 * (size_t)nIterations);
-    for (size_t k = 0; k < draws.size(); k++) {
-        if (!q.empty()) {
-            draws[k] = q.front();
-            q.pop_front();
-        } else {
-            draws[k] = (int32_t)rand();
-        }
-    }
+    const std::vector<int32_t> draws = take_draws(3 * (size_t)nIterations);
     orbfe_sim3_result res;
     const orbfe_status status = orbfe_sim3_iterate(handle_for(N), X1.data(), X2.data(), s1.data(), s2.data(), N, K1, K2, mbFixScale, mRansacMinInliers,
                                                    mRansacMaxIts, nIterations, draws.data(), &st, best.data(), &res, mask.data());
-    const size_t used = status == ORBFE_OK ? 3 * (size_t)res.iterations_run : 0;
-    for (size_t k = draws.size(); k > used; k--) q.push_front(draws[k - 1]);
+    give_back(draws, status == ORBFE_OK ? 3 * (size_t)res.iterations_run : 0);
     check(status, "orbfe_sim3_iterate");
     mnIterations = st.iterations;
     if (res.iterations_run > 0) {   // every iteration that reached the best replaced it; the state says with what

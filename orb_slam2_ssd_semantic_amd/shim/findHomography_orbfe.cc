@@ -3,36 +3,17 @@
 // and runs on the GPU through orbfe_find_homography (csrc/orbfe_homography.hip): the H and mask of the restated OpenCV 3.2
 // path (tests/homography_oracle.py).  With ORBFE_WITH_OPENCV the real cv::findHomography is used and this file is empty.
 #ifndef ORBFE_WITH_OPENCV
-#include <stdexcept>
-#include <string>
-
 #include "cv_stub/orbfe_cv_stub.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 namespace cv {
 
-static void check(orbfe_status s, const char *what)
-{
-    if (s != ORBFE_OK) throw std::runtime_error(std::string(what) + ": " + orbfe_strerror(s) + " (" + orbfe_last_error() + ")");
-}
+using orbfe_shim::check;
 
 // one handle per thread, grown to the largest point count seen
 static orbfe_homography *handle_for(int n)
 {
-    struct Holder {
-        orbfe_homography *h = nullptr;
-        int cap = 0;
-        ~Holder() { orbfe_homography_destroy(h); }
-    };
-    static thread_local Holder hold;
-    if (!hold.h || n > hold.cap) {
-        orbfe_homography_destroy(hold.h);
-        hold.h = nullptr;
-        int cap = n > 4096 ? n : 4096;
-        check(orbfe_homography_create(-1, cap, 1, &hold.h), "orbfe_homography_create");
-        hold.cap = cap;
-    }
-    return hold.h;
+    return orbfe_shim::handle_for<orbfe_homography, orbfe_homography_create, orbfe_homography_destroy>(n, "orbfe_homography_create");
 }
 
 Mat findHomography(const std::vector<Point2f> &srcPoints, const std::vector<Point2f> &dstPoints, int method,

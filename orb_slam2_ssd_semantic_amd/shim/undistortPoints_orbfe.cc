@@ -4,30 +4,19 @@
 // it.  The stub Mat has no channels, so the points are an N x 2 CV_32F matrix (the reference's reshape(2) / reshape(1) pair drops
 // out).  With ORBFE_WITH_OPENCV the real cv::undistortPoints is used and this file is empty.
 #ifndef ORBFE_WITH_OPENCV
-#include <stdexcept>
-#include <string>
-#include <vector>
-
 #include "cv_stub/orbfe_cv_stub.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 namespace cv {
 
-static void check(orbfe_status s, const char *what)
-{
-    if (s != ORBFE_OK) throw std::runtime_error(std::string(what) + ": " + orbfe_strerror(s) + " (" + orbfe_last_error() + ")");
-}
+using orbfe_shim::check;
 
 // one matcher per thread (its stream and scratch carry the call)
 static orbfe_matcher *matcher()
 {
-    struct Holder {
-        orbfe_matcher *m = nullptr;
-        ~Holder() { orbfe_matcher_destroy(m); }
-    };
-    static thread_local Holder hold;
-    if (!hold.m) check(orbfe_matcher_create(-1, &hold.m), "orbfe_matcher_create");
-    return hold.m;
+    static thread_local orbfe_shim::Holder<orbfe_matcher, orbfe_matcher_destroy> hold;
+    if (!hold.h) check(orbfe_matcher_create(-1, &hold.h), "orbfe_matcher_create");
+    return hold.h;
 }
 
 static void read3x3(const Mat &m, const char *name, float out[9])

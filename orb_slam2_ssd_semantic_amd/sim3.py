@@ -1,12 +1,11 @@
 """The reference's Sim3Solver (src/Sim3Solver.cc) on the GPU: Horn's closed form on three correspondences inside the RANSAC loop
 of `iterate`, through the C-ABI of csrc/orbfe_sim3.hip.  The random draws are an input (raw values in [0, 2^31 - 1], three per
 iteration), so a run can be replayed.  No CPU fallback."""
-import ctypes as C
-
 import numpy as np
 
-from . import _ffi
-from ._ffi import Handle, stream_arg, tensor_ptr
+from . import _ffi, _ransac
+from ._ffi import stream_arg, tensor_ptr
+from ._ransac import TAP_ERRORS, TAP_ITERATIONS, TAP_ITERS, TAP_SETS  # noqa: F401
 
 MODEL_DTYPE = np.dtype([("T12", "<f4", (4, 4)), ("R", "<f4", (3, 3)), ("t", "<f4", (3,)), ("s", "<f4"), ("reserved", "<f4", (3,))])
 STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("reserved", "<i4", (2,)), ("best", MODEL_DTYPE)])
@@ -15,8 +14,6 @@ SET_DTYPE = np.dtype([("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("fix_scale", "<
                       ("n_iterations", "<i4"), ("draws_offset", "<i4"), ("key_offset", "<i4"), ("n_keys", "<i4"), ("reserved", "<i4")])
 ITER_DTYPE = np.dtype([("triple", "<i4", (3,)), ("n_inliers", "<i4"), ("T12", "<f4", (4, 4))])
 assert (MODEL_DTYPE.itemsize, STATE_DTYPE.itemsize, RESULT_DTYPE.itemsize, SET_DTYPE.itemsize, ITER_DTYPE.itemsize) == (128, 144, 144, 64, 80)
-TAP_ITERATIONS, TAP_ERRORS = range(2)
-TAP_SETS, TAP_ITERS = 32, 512
 KAT_JACOBI4, KAT_ATAN2, KAT_SIN, KAT_COS, KAT_ROTATION = range(5)
 
 
@@ -25,23 +22,15 @@ def ransac_iterations(probability, min_inliers, max_its, n):
     return int(_ffi.lib().orbfe_sim3_ransac_iterations(float(probability), int(min_inliers), int(max_its), int(n)))
 
 
-class Sim3(Handle):
+class Sim3(_ransac.RansacHandle):
     """Device scratch for Sim3 solvers of at most max_pairs correspondences (host form) and batches of at most max_sets
-    solvers (device form)."""
+    solvers (device form).  The error tap is float32 [n, 2]: (err1, err2)."""
 
-    _HANDLE, _DESTROY = "h", "orbfe_sim3_destroy"
+    _PREFIX, ITER_DTYPE, _ERR_SHAPE = "orbfe_sim3", ITER_DTYPE, (2,)
 
     def __init__(self, max_pairs=4096, max_sets=64, device=0):
-        self._L = _ffi.lib()
-        self.h = C.c_void_p()
-        _ffi.check(self._L.orbfe_sim3_create(device, max_pairs, max_sets, C.byref(self.h)), "orbfe_sim3_create")
-        self.device = device
+        super().__init__(max_pairs, max_sets, device)
         self.max_pairs = max_pairs
-        self.max_sets = max_sets
-
-    @property
-    def stream(self):
-        return self._L.orbfe_sim3_get_stream(self.h)
 
     def iterate(self, X1, X2, sigma2_1, sigma2_2, K1, K2, fix_scale, min_inliers, max_its, n_iterations, draws, state, best_mask):
         """One solver's iterate(n_iterations) on host arrays.  state (STATE_DTYPE [1]) and best_mask (uint8 [n]) are updated in
@@ -62,38 +51,20 @@ class Sim3(Handle):
             raise ValueError("state must be a STATE_DTYPE array, best_mask a contiguous uint8 array")
         res = np.zeros(1, RESULT_DTYPE)
         mask = np.zeros(n, np.uint8)
-        _ffi.check(self._L.orbfe_sim3_iterate(self.h, _ffi.ptr(X1), _ffi.ptr(X2), _ffi.ptr(s1), _ffi.ptr(s2), n, _ffi.ptr(k1), _ffi.ptr(k2),
-                                              int(bool(fix_scale)), int(min_inliers), int(max_its), int(n_iterations),
-                                              _ffi.ptr(d) if len(d) else None, _ffi.ptr(state), _ffi.ptr(best_mask) if n else None,
-                                              _ffi.ptr(res), _ffi.ptr(mask) if n else None), "orbfe_sim3_iterate")
+        self._call("iterate", self.h, _ffi.ptr(X1), _ffi.ptr(X2), _ffi.ptr(s1), _ffi.ptr(s2), n, _ffi.ptr(k1), _ffi.ptr(k2),
+                   int(bool(fix_scale)), int(min_inliers), int(max_its), int(n_iterations), _ffi.ptr(d) if len(d) else None, _ffi.ptr(state),
+                   _ffi.ptr(best_mask) if n else None, _ffi.ptr(res), _ffi.ptr(mask) if n else None)
         return res[0], mask
-
-    def set_tap_iteration(self, iteration):
-        _ffi.check(self._L.orbfe_sim3_set_tap_iteration(self.h, int(iteration)), "orbfe_sim3_set_tap_iteration")
-
-    def tap(self, set_index, stage):
-        """A stage of the last call: TAP_ITERATIONS -> ITER_DTYPE [iterations run]; TAP_ERRORS -> float32 [n, 2] (err1, err2) of
-        the iteration chosen with set_tap_iteration before the call."""
-        cnt = C.c_int32()
-        if stage == TAP_ITERATIONS:
-            out = np.zeros(TAP_ITERS, ITER_DTYPE)
-        else:
-            out = np.zeros((self.max_pairs, 2), np.float32)
-        _ffi.check(self._L.orbfe_sim3_tap(self.h, set_index, stage, _ffi.ptr(out), out.nbytes, C.byref(cnt)), "orbfe_sim3_tap")
-        return out[:cnt.value].copy()
 
     def prepare_device(self, world1, world2, Rcw1, tcw1, Rcw2, tcw2, stream=None):
         """The constructor's camera-frame points on torch device tensors: world1 / world2 float32 [n, 3] -> (X1, X2)"""
         import torch
-        for t, name in ((world1, "world1"), (world2, "world2")):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous torch float32 tensor on the device")
+        _ransac.check_tensors((world1, torch.float32, "world1", "float32 tensor"), (world2, torch.float32, "world2", "float32 tensor"))
         n = world1.shape[0]
         X1, X2 = torch.empty_like(world1), torch.empty_like(world2)
         pose = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in (Rcw1, tcw1, Rcw2, tcw2)]
-        _ffi.check(self._L.orbfe_sim3_prepare_device(self.h, tensor_ptr(world1), tensor_ptr(world2), n, *[_ffi.ptr(p) for p in pose],
-                                                     tensor_ptr(X1), tensor_ptr(X2), stream_arg(world1.device, stream)),
-                   "orbfe_sim3_prepare_device")
+        self._call("prepare_device", self.h, tensor_ptr(world1), tensor_ptr(world2), n, *[_ffi.ptr(p) for p in pose], tensor_ptr(X1),
+                   tensor_ptr(X2), stream_arg(world1.device, stream))
         return X1, X2
 
     def iterate_device(self, offsets, X1, X2, sigma2_1, sigma2_2, sets, draws, state, best_mask, result=None, mask=None, idx1=None,
@@ -106,23 +77,19 @@ class Sim3(Handle):
         import torch
         nsets = offsets.numel() - 1
         dev = offsets.device
-        for t, dt, name in ((offsets, torch.int32, "offsets"), (X1, torch.float32, "X1"), (X2, torch.float32, "X2"),
-                            (sigma2_1, torch.float32, "sigma2_1"), (sigma2_2, torch.float32, "sigma2_2"), (sets, torch.uint8, "sets"),
-                            (draws, torch.int32, "draws"), (state, torch.uint8, "state"), (best_mask, torch.uint8, "best_mask")):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous torch {dt} tensor on the device")
+        _ransac.check_tensors((offsets, torch.int32, "offsets"), (X1, torch.float32, "X1"), (X2, torch.float32, "X2"),
+                              (sigma2_1, torch.float32, "sigma2_1"), (sigma2_2, torch.float32, "sigma2_2"), (sets, torch.uint8, "sets"),
+                              (draws, torch.int32, "draws"), (state, torch.uint8, "state"), (best_mask, torch.uint8, "best_mask"))
         if sets.numel() != nsets * SET_DTYPE.itemsize or state.numel() != nsets * STATE_DTYPE.itemsize:
             raise ValueError("sets / state must hold one record per set")
         if result is None:
             result = torch.zeros((nsets, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         if mask is None:
             mask = torch.zeros(max(X1.shape[0], 1), dtype=torch.uint8, device=dev)
-        _ffi.check(self._L.orbfe_sim3_iterate_device(self.h, tensor_ptr(offsets), tensor_ptr(X1), tensor_ptr(X2), tensor_ptr(sigma2_1),
-                                                     tensor_ptr(sigma2_2), tensor_ptr(sets), tensor_ptr(draws), nsets, tensor_ptr(state),
-                                                     tensor_ptr(best_mask), tensor_ptr(result), tensor_ptr(mask),
-                                                     tensor_ptr(idx1) if idx1 is not None else None,
-                                                     tensor_ptr(key_mask) if key_mask is not None else None, stream_arg(dev, stream)),
-                   "orbfe_sim3_iterate_device")
+        self._call("iterate_device", self.h, tensor_ptr(offsets), tensor_ptr(X1), tensor_ptr(X2), tensor_ptr(sigma2_1), tensor_ptr(sigma2_2),
+                   tensor_ptr(sets), tensor_ptr(draws), nsets, tensor_ptr(state), tensor_ptr(best_mask), tensor_ptr(result), tensor_ptr(mask),
+                   tensor_ptr(idx1) if idx1 is not None else None, tensor_ptr(key_mask) if key_mask is not None else None,
+                   stream_arg(dev, stream))
         return result, mask[:X1.shape[0]]
 
 
@@ -130,10 +97,7 @@ _default = {}
 
 
 def _handle(device, n):
-    h = _default.get(device)
-    if h is None or h.max_pairs < n:
-        h = _default[device] = Sim3(max(n, 4096), 1, device)
-    return h
+    return _ransac.default_handle(_default, Sim3, "max_pairs", device, n)
 
 
 def sim3_iterate_device(handle, offsets, X1, X2, sigma2_1, sigma2_2, sets, draws, state, best_mask, **kw):
@@ -141,11 +105,13 @@ def sim3_iterate_device(handle, offsets, X1, X2, sigma2_1, sigma2_2, sets, draws
     return handle.iterate_device(offsets, X1, X2, sigma2_1, sigma2_2, sets, draws, state, best_mask, **kw)
 
 
-class Sim3Solver:
+class Sim3Solver(_ransac.RansacSolver):
     """Mirrors the reference's class on flattened inputs: X1 / X2 [n, 3] camera-frame points of the matched map points (or world
     positions with the two poses, see from_world), their level sigma^2 values, K = (fx, fy, cx, cy) of each keyframe.  idx1 /
     n1 (mvnIndices1 / mN1) make iterate's mask a per-keypoint one.  Draws come from `draws` of each call, or from `rand` (a
     callable returning k raw values in [0, 2^31 - 1]; default: a numpy generator seeded with `seed`)."""
+
+    DRAWS = 3
 
     def __init__(self, X1, X2, sigma2_1, sigma2_2, K1, K2, fix_scale=True, idx1=None, n1=None, device=0, handle=None, rand=None, seed=0):
         self.X1 = np.ascontiguousarray(X1, np.float32).reshape(-1, 3)
@@ -155,15 +121,8 @@ class Sim3Solver:
         self.sigma2_2 = np.ascontiguousarray(sigma2_2, np.float32).reshape(-1)
         self.K1, self.K2 = K1, K2
         self.fix_scale = bool(fix_scale)
-        self.idx1 = None if idx1 is None else np.asarray(idx1, np.int64)
-        self.n1 = self.N if n1 is None else int(n1)
-        self._h = handle if handle is not None else _handle(device, self.N)
-        if rand is None:
-            rng = np.random.default_rng(seed)
-            rand = lambda k: rng.integers(0, 2 ** 31, k)   # noqa: E731
-        self._rand = rand
-        self.state = np.zeros(1, STATE_DTYPE)
-        self.best_mask = np.zeros(self.N, np.uint8)
+        self._setup(handle if handle is not None else _handle(device, self.N), STATE_DTYPE, idx1, n1, rand, seed)
+        self.idx1, self.n1 = self._index, self._n_out
         self.set_ransac_parameters()
 
     @classmethod
@@ -185,18 +144,11 @@ class Sim3Solver:
         """-> (T12 float32 [4, 4] or None, no_more, inlier mask bool [n1], n_inliers).  Three draws per iteration run are
         consumed; self.iterations_run tells how many ran."""
         n_iterations = int(n_iterations)
-        if draws is None:
-            draws = self._rand(3 * max(n_iterations, 0))
         res, mask = self._h.iterate(self.X1, self.X2, self.sigma2_1, self.sigma2_2, self.K1, self.K2, self.fix_scale, self.min_inliers,
-                                    self.max_its, n_iterations, draws, self.state, self.best_mask)
+                                    self.max_its, n_iterations, self._draws(draws, n_iterations), self.state, self.best_mask)
         self.iterations_run = int(res["iterations_run"])
-        inl = np.zeros(self.n1, bool)
-        if self.idx1 is None:
-            inl[:self.N] = mask.astype(bool)
-        else:
-            inl[self.idx1[mask.astype(bool)]] = True
         T12 = res["model"]["T12"].copy() if res["found"] else None
-        return T12, bool(res["no_more"]), inl, int(res["n_inliers"])
+        return T12, bool(res["no_more"]), self._scatter(mask), int(res["n_inliers"])
 
     def find(self, draws=None):
         T12, _, inl, n = self.iterate(self.max_its, draws)

@@ -4,6 +4,8 @@ case table with the taps of every iteration run, the rules of the acceptance sca
 the batched device form against host calls with the scatter into the frame mask, the argument errors and the Python class.
 NaNs compare by position (the payload and sign of a generated NaN belong to the processor); every other value compares as
 bits."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -338,3 +340,40 @@ def test_argument_errors(pn):
     cnt = np.zeros(1, np.int32)
     assert L.orbfe_pnp_tap(h2.h, 0, 0, _ffi.ptr(np.zeros(128, np.uint8)), 128, _ffi.ptr(cnt)) == _ffi.ORBFE_ERR_STATE
     h2.close()
+    # the batched form: (h, offsets, P3Dw, P2D, sigma2, sets, draws, nsets, state, best_mask, result, mask, keypoint_index, key_mask, stream)
+    one = C.c_void_p(8)
+    assert L.orbfe_pnp_iterate_device(pn.h, one, one, one, one, one, one, 33, one, one, one, one, None, None, None) == _ffi.ORBFE_ERR_ARG
+    assert "max_sets" in _ffi.last_error()
+    assert L.orbfe_pnp_iterate_device(pn.h, one, one, one, one, one, one, 1, one, one, one, one, one, None, None) == _ffi.ORBFE_ERR_ARG
+    assert L.orbfe_pnp_iterate_device(pn.h, one, one, None, one, one, one, 1, one, one, one, one, None, None, None) == _ffi.ORBFE_ERR_ARG
+    for past in (1, 31):   # the last call that ran had one set
+        assert L.orbfe_pnp_tap(pn.h, past, 0, _ffi.ptr(np.zeros(128, np.uint8)), 128, _ffi.ptr(cnt)) == _ffi.ORBFE_ERR_STATE, past
+
+
+@pytest.mark.gpu
+def test_tap_capacity_and_an_iteration_that_did_not_run():
+    """orbfe_pnp_tap: one byte short of the iteration records is ORBFE_ERR_CAP, exactly enough is ORBFE_OK with every record;
+    the errors of an iteration at or past iterations_run were not recorded: ORBFE_ERR_STATE"""
+    L = _ffi.lib()
+    sc = PC.scene(1, 20, inlier_ratio=1.0)
+    params = PN.ransac_params(0.99, 10, 300, 4, 0.5, n=20)
+    args = (sc["P3Dw"], sc["P2D"], sc["sigma2"], PC.K, params, 5)
+    with PnP(64, 1) as h:
+        state = np.zeros(1, PN.STATE_DTYPE)
+        d = PC.draws_for(1, PN.iterations(state, params, 5))
+        h.set_tap_iteration(0)
+        res, _ = h.iterate(*args, d, state, np.zeros(20, np.uint8))
+        run = int(res["iterations_run"])
+        assert run >= 1
+        need = run * PN.ITER_DTYPE.itemsize
+        buf = np.zeros(need, np.uint8)
+        cnt = C.c_int32(-1)
+        assert L.orbfe_pnp_tap(h.h, 0, PN.TAP_ITERATIONS, _ffi.ptr(buf), need - 1, C.byref(cnt)) == _ffi.ORBFE_ERR_CAP
+        assert L.orbfe_pnp_tap(h.h, 0, PN.TAP_ITERATIONS, _ffi.ptr(buf), need, C.byref(cnt)) == _ffi.ORBFE_OK and cnt.value == run
+        err = np.zeros(64, np.float32)
+        assert L.orbfe_pnp_tap(h.h, 0, PN.TAP_ERRORS, _ffi.ptr(err), err.nbytes, C.byref(cnt)) == _ffi.ORBFE_OK and cnt.value == 20
+        for k in (run, run + 1):   # the same call again, recording an iteration it does not reach
+            h.set_tap_iteration(k)
+            res, _ = h.iterate(*args, d, np.zeros(1, PN.STATE_DTYPE), np.zeros(20, np.uint8))
+            assert int(res["iterations_run"]) == run
+            assert L.orbfe_pnp_tap(h.h, 0, PN.TAP_ERRORS, _ffi.ptr(err), err.nbytes, C.byref(cnt)) == _ffi.ORBFE_ERR_STATE, k

@@ -355,6 +355,32 @@ def test_argument_errors(sm):
 
 
 @pytest.mark.gpu
+def test_tap_capacity_and_an_iteration_that_did_not_run():
+    """orbfe_sim3_tap: one byte short of the iteration records is ORBFE_ERR_CAP, exactly enough is ORBFE_OK with every record;
+    the errors of an iteration at or past iterations_run were not recorded: ORBFE_ERR_STATE"""
+    L = _ffi.lib()
+    c = SC.full_table()["n_64"]
+    args = (c["X1"], c["X2"], c["sigma2_1"], c["sigma2_2"], c["K1"], c["K2"], 1, 20, 300, 5, c["calls"][0][1])
+    with Sim3(64, 1) as h:
+        h.set_tap_iteration(0)
+        res, _ = h.iterate(*args, np.zeros(1, S3.STATE_DTYPE), np.zeros(64, np.uint8))
+        run = int(res["iterations_run"])
+        assert 1 <= run <= 5
+        need = run * S3.ITER_DTYPE.itemsize
+        buf = np.zeros(need, np.uint8)
+        cnt = C.c_int32(-1)
+        assert L.orbfe_sim3_tap(h.h, 0, S3.TAP_ITERATIONS, _ffi.ptr(buf), need - 1, C.byref(cnt)) == _ffi.ORBFE_ERR_CAP
+        assert L.orbfe_sim3_tap(h.h, 0, S3.TAP_ITERATIONS, _ffi.ptr(buf), need, C.byref(cnt)) == _ffi.ORBFE_OK and cnt.value == run
+        err = np.zeros((64, 2), F)
+        assert L.orbfe_sim3_tap(h.h, 0, S3.TAP_ERRORS, _ffi.ptr(err), err.nbytes, C.byref(cnt)) == _ffi.ORBFE_OK and cnt.value == 64
+        for k in (run, run + 1):   # the same call again, recording an iteration it does not reach
+            h.set_tap_iteration(k)
+            res, _ = h.iterate(*args, np.zeros(1, S3.STATE_DTYPE), np.zeros(64, np.uint8))
+            assert int(res["iterations_run"]) == run
+            assert L.orbfe_sim3_tap(h.h, 0, S3.TAP_ERRORS, _ffi.ptr(err), err.nbytes, C.byref(cnt)) == _ffi.ORBFE_ERR_STATE, k
+
+
+@pytest.mark.gpu
 def test_python_class(sm):
     c = SC.full_table()["second_call"]
     outs, osolver = SC.reference("second_call")
