@@ -1,21 +1,12 @@
-// orbfe_api.hip -- host side of the extractor C-ABI (include/orbfe.h): constructor tables, per-size plan,
-// device buffers, stream/event plumbing.  All pixel work happens in the kernel files (one per stage: orbfe_kernels.h); there is no CPU path.
-//
-// Reference behaviour restated here (paths relative to /root/reference):
-//   constructor tables            src/ORBextractor.cc:399-466
-//   level sizes / pyramid layout  src/ORBextractor.cc:1117-1145
-//   FAST cell grid + skip rules   src/ORBextractor.cc:771-816
-//   quadtree roots                src/ORBextractor.cc:545-564
-//   cv::resize coefficient tables OpenCV 3.2 imgwarp.cpp
-#include <math.h>
+// orbfe_api.hip -- host side of the extractor C-ABI (include/orbfe.h): device buffers, stream/event plumbing, the call sequence of
+// a batch.  The constructor tables and the per-size plan come from orbfe_plan.hip, which needs no device; this file uploads them.
+// All pixel work happens in the kernel files (one per stage: orbfe_kernels.h); there is no CPU path.
 #include <stdarg.h>
 #include <stdlib.h>
 
 #include <algorithm>
 
-#include "orbfe_common.h"
-#include "orbfe_host.h"
-#include "orbfe_kernels.h"
+#include "orbfe_extractor.h"
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -58,735 +49,59 @@ extern "C" int32_t orbfe_device_count(void)
     return n;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// handle
-// ---------------------------------------------------------------------------------------------------
-#define ORBFE_PROF_RING 64
-// rows a FAST / blur wave walks down.  Measured on MI355X (256 x 640x480): 24..48 rows are equally fast and ~5 % faster
-// than 64+ -- the 6..8 warm-up rows of a block are nearly free, while shorter waves balance the CUs better.
-#define ORBFE_ROWS_PER_WAVE 40
-// event marks of one profiled call: 0 start, 1 pyramid done, 2 FAST done, 3 quadtree done, 4 describe start, 5 end (launch
-// stream); 6 / 7 around the blur (on whichever stream it ran)
-#define ORBFE_EV_N 8
-// auto FAST mode: above this share of pixel pairs passing the necessary test the dense form is the cheaper one.  Measured per
-// 1024 frames of 640x480 (tools/compact_ab.py, profiles/r05_compact_ab.json; dense / lane-compacting, ms): pass rate 0.84 (S)
-// 1.47 / 2.14; 0.43 1.40 / 1.62; 0.38 1.42 / 1.55; 0.29 1.36 / 1.39; 0.18 (S_tum) 1.33 / 1.12; 0.076 1.26 / 0.92;
-// 0.02 1.22 / 0.74 -- break-even near 0.27
-#define ORBFE_AUTO_DENSE_RATE 0.25
-// ... and a launch that does not fill the GPU is bound by its longest wave, not by issue slots, and the dense form has the shorter
-// wave (FAST stage of ONE 640x480 frame: 18 us dense / 21 us compacting on S_tum, 20 / 26 on S; 8 frames: 29 / 34 and 31 / 44 --
-// tools/fast_mode_latency.py): below this many wave row steps per call (about 29 frames of 640x480 with 8 levels: 4 890 each) auto is dense
-#define ORBFE_AUTO_MIN_ROW_STEPS 140000
-#define ORBFE_AUTO_HOLD_MIN 16    // dense calls after a probe above the rate; doubles with every such probe in a row ...
-#define ORBFE_AUTO_HOLD_MAX 256   // ... up to this (a probe call on corner-saturated frames costs +45 % of its FAST stage)
-#define ORBFE_AUTO_PROBE_EVERY 8  // compacting calls between two looks at the pass rate
+// Collects the answer of a finished automatic FAST-mode probe into auto_last; never waits.  true: there was one.
+static bool collect_auto_probe(orbfe_handle *h)
+{
+    if (h->auto_pending && hipEventQuery(h->ev_auto) == hipSuccess) {
+        memcpy(h->auto_last, h->h_auto.p, sizeof(h->auto_last));
+        h->auto_pending = false;
+        return true;
+    }
+    (void)hipGetLastError();   // hipErrorNotReady is not an error of ours
+    return false;
+}
 
-struct orbfe_handle {
-    orbfe_params prm;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = true;      // false: the stream belongs to a pipeline (orbfe_internal_create_on_stream); no host copy streams then
-    bool own_side = true;        // false: the side stream (blur) is one the pipeline shares among its pipes
-    // constructor tables (src/ORBextractor.cc:404-439)
-    float scale[ORBFE_MAX_LEVELS], inv_scale[ORBFE_MAX_LEVELS], sigma2[ORBFE_MAX_LEVELS], inv_sigma2[ORBFE_MAX_LEVELS];
-    int feat[ORBFE_MAX_LEVELS];
-    // plan for the current frame size
-    OrbPlan plan;
-    bool plan_valid = false;
-    std::vector<OrbCell> cells;
-    std::vector<OrbTab> tabs;
-    DevBuf d_plan, d_tabs, d_flanes, d_flanes_c, d_blanes, d_blanesR;
-    // per-batch blocks
-    DevBuf d_pyr, d_blur, d_skeys, d_scount, d_knode, d_qtbox, d_qtnodes, d_sel, d_nsel, d_nkeys, d_pad;
-    // sticky overflow word + FAST sparse-variant statistics: [0] int32 overflow bits, [2..7] 3 x uint64 counters
-    DevBuf d_misc;
-    int fast_mode = 3;            // 0 dense, 1 sparse shortcuts, 2 lane-compacting, 3 auto (default): 2 or 0 by batch size and observed pass rate (orbfe_set_fast_mode)
-    bool fast_stats = false;
-    // auto mode: the lane-compacting kernel reports {row steps, batches, parked pairs} of a sample of its waves; the counters are
-    // copied to pinned host memory behind the kernel and looked at -- without waiting -- by a later call
-    PinBuf h_auto;                // 3 x uint64
-    hipEvent_t ev_auto = nullptr;
-    bool auto_pending = false;
-    int auto_dense_left = 0;      // calls still to run dense before the pass rate is probed again
-    int auto_hold = ORBFE_AUTO_HOLD_MIN;   // length of the next dense run
-    int auto_since = 0;           // compacting calls since the last probe
-    int auto_form = 2;            // the form the last probe chose (before the first answer: compacting, the probe's own form)
-    uint64_t auto_last[3] = {0, 0, 0};
-    int64_t fast_row_steps = 0;
-    // The most recent batched call: its stream (only compared, never dereferenced: the caller may have destroyed it) and an
-    // event recorded behind its last launch.  All calls of a handle share the scratch blocks, so a call on another stream
-    // waits for that event first, and whoever needs the results on the host (taps, mvImagePyramid, re-planning, the
-    // overflow word, destroy) synchronises the event, not the stream.
-    hipStream_t last_stream = nullptr;
-    bool last_stream_valid = false;
-    hipEvent_t ev_last = nullptr;
-    // host-API staging
-    // two sets, so that the H2D of chunk i+1, the kernels of chunk i and the D2H of chunk i-1 overlap
-    DevBuf d_stage[2], d_okps[2], d_odesc[2], d_on[2];
-    PinBuf h_stage[2], h_okps[2], h_odesc[2], h_on[2], h_ovf;
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_cmp[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    // last call (for taps / mvImagePyramid)
-    const uint8_t *last_gray = nullptr;
-    int64_t last_gray_fstride = 0;
-    int32_t last_gray_pitch = 0;
-    int32_t last_nframes = 0;
-    // profiling: ring of event sets so a timed region of many asynchronous calls can be averaged afterwards
-    bool profiling = false;
-    hipEvent_t ev[ORBFE_PROF_RING][ORBFE_EV_N];
-    int prof_calls = 0;  // calls recorded since profiling was (re-)enabled
-    bool ev_ok = false;
-    // blur depends on the pyramid only, the quadtree on FAST only: the blur runs on a side stream next to the
-    // latency-bound quadtree (overlap 2), next to FAST + quadtree (1), or in line (0).  -1 = by batch size: 2 for
-    // batches that fill the chip (>= 128 frames: 3.71 -> 3.62 ms per 1024 frames, the HBM-bound blur fills the
-    // quadtree's idle VALU / memory slots; next to the VALU-bound FAST pass it gains nothing), 0 for small ones
-    int overlap = -1;
-    int fuse_fast_pyr = 0;   // 1 / 2: FAST(l) + resize(l -> l + 1) in one launch per level (ORBFE_FUSE_FAST_PYR; 2 = the two kinds of
-                             // workgroups dealt out proportionally over the grid, 1 = resize workgroups first)
-    int fuse_fast_pyr_levels = ORBFE_MAX_LEVELS;   // levels fused that way; the rest: plain resizes + one FAST launch
-    int fuse_blur_pyr = 0;   // 1: blur + pyramid in one chained pass over the levels (ORBFE_FUSE_BLUR_PYR)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;   // the side-stream FAST of ORBFE_OPT_FUSE_FAST_PYR = 3 (developer builds)
-    // tuning options (orbfe_set_option; 0 / -1 = built-in choice).  The plan-shaping ones invalidate the plan.
-    int opt_rows = 0, opt_rows_fast = 0, opt_rows_blur = 0;
-    int opt_blur_pieces = 1, opt_blur_updown = 1, opt_debug = 0;
-    OrbOpts kopts = {0, 0, {0, 0, 0}};
-    // ORBFE_OPT_REUSE_IDENTICAL_INPUT (orbfe_extract only): the frame of the last single-frame host call is still in the pinned
-    // staging block h_stage[0] and its results in h_okps[0]; a call that brings the same pixels gets those results back without
-    // touching the GPU.  reuse_valid is dropped by every other use of the handle (run_batch) and by every option change.
-    int opt_reuse = 0;
-    bool reuse_valid = false, last_reused = false;
-    int reuse_w = 0, reuse_h = 0, reuse_cap = 0;
-    int64_t reuse_hits = 0;
+// The handle's untimed events and the streams it may own, listed once: create_impl makes them, orbfe_destroy drains the streams
+// and destroys both.  A pipe of a pipeline borrows `stream` (and then has no copy streams) and possibly `side`.
+struct OwnedStream {
+    hipStream_t *s;
+    bool own;
 };
-
-// waits until the last batched call of the handle has finished, on whichever stream it ran
-static hipError_t wait_last_call(orbfe_handle *h)
+static std::vector<OwnedStream> handle_streams(orbfe_handle *h)
 {
-    if (!h->last_stream_valid) return hipSuccess;
-    return hipEventSynchronize(h->ev_last);
+    return {{&h->stream, h->own_stream}, {&h->side, h->own_side}, {&h->s_in, h->own_stream}, {&h->s_out, h->own_stream}};
+}
+static std::vector<hipEvent_t *> handle_events(orbfe_handle *h)
+{
+    return {&h->ev_last, &h->ev_fork, &h->ev_join, &h->ev_in[0], &h->ev_cmp[0], &h->ev_out[0], &h->ev_in[1], &h->ev_cmp[1], &h->ev_out[1],
+            &h->ev_fork2, &h->ev_auto, &h->ev_join2};
 }
 
-static inline int cv_round_f(float v) { return (int)lrintf(v); }  // cvRound: half-to-even
-
-static void host_umax(int umax[16])
-{
-    // src/ORBextractor.cc:449-465
-    int v, v0;
-    const int vmax = (int)floorf(ORBFE_HALF_PATCH * sqrtf(2.f) / 2 + 1);
-    const int vmin = (int)ceilf(ORBFE_HALF_PATCH * sqrtf(2.f) / 2);
-    const double hp2 = ORBFE_HALF_PATCH * ORBFE_HALF_PATCH;
-    for (v = 0; v < 16; ++v) umax[v] = 0;
-    for (v = 0; v <= vmax; ++v) umax[v] = (int)lrint(sqrt(hp2 - v * v));
-    for (v = ORBFE_HALF_PATCH, v0 = 0; v >= vmin; --v) {
-        while (umax[v0] == umax[v0 + 1]) ++v0;
-        umax[v] = v0;
-        ++v0;
-    }
-}
-
-// cv::resize coefficient table of one axis
-static void resize_axis(int ssize, int dsize, bool is_x, OrbTab *out)
-{
-    const double inv_scale = (double)dsize / ssize;
-    const double scale = 1. / inv_scale;
-    for (int d = 0; d < dsize; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= s;
-        if (is_x) {
-            if (s < 0) { f = 0; s = 0; }
-            if (s >= ssize - 1) { f = 0; s = ssize - 1; }
-        }
-        auto sat = [](int v) { return (int16_t)std::min(32767, std::max(-32768, v)); };
-        out[d].s = (int16_t)s;
-        out[d].c0 = sat(cv_round_f((1.f - f) * 2048));
-        out[d].c1 = sat(cv_round_f(f * 2048));
-        out[d].pad = 0;
-    }
-}
-
+// The plan of a w x ht frame (orbfe_plan.hip builds it on the host), uploaded and committed to the handle.
 static orbfe_status build_plan(orbfe_handle *h, int w, int ht)
 {
     if (h->plan_valid && h->plan.w == w && h->plan.h == ht) return ORBFE_OK;
-    const int nl = h->prm.nlevels;
-    OrbPlan P;
-    memset(&P, 0, sizeof(P));
-    P.nlevels = nl;
-    P.w = w;
-    P.h = ht;
-    P.ini_th = std::min(255, std::max(0, h->prm.ini_th_fast));
-    P.min_th = std::min(255, std::max(0, h->prm.min_th_fast));
-    P.blur_rounding = h->prm.blur_rounding;
-    P.dbg = h->opt_debug;
-    // Rows a FAST / blur wave walks.  Long runs amortise the 8 (FAST) / 6 (blur) halo rows -- right for batches, whose waves
-    // fill the chip anyway.  A handle made for the online call (a frame or a few per call) is latency-bound instead: one wave's
-    // walk IS the kernel's duration, so it takes short runs and more waves: single 640x480 frame, FAST 41 -> 25 -> 21 us and blur
-    // 19 -> 11 -> 9 us with 40 -> 16 -> 8 rows (ORBFE_OPT_ROWS overrides, 8..512).
-    int rows_per_wave = h->prm.max_batch <= 2 ? 8 : (h->prm.max_batch <= 8 ? 16 : ORBFE_ROWS_PER_WAVE);
-    if (h->opt_rows >= 8 && h->opt_rows <= 512) rows_per_wave = h->opt_rows;
-    // the FAST and the blur walk can take different run lengths (ORBFE_OPT_ROWS_FAST / ORBFE_OPT_ROWS_BLUR; A/B in
-    // profiles/r04_ab_experiments.json): a longer run amortises the 8 (FAST) / 6 (blur) halo steps, a shorter one balances better
-    int rows_fast = rows_per_wave, rows_blur = rows_per_wave;
-    if (h->opt_rows_fast >= 8 && h->opt_rows_fast <= 512) rows_fast = h->opt_rows_fast;
-    if (h->opt_rows_blur >= 8 && h->opt_rows_blur <= 512) rows_blur = h->opt_rows_blur;
-    std::vector<OrbCell> cells;
-    std::vector<OrbTab> tabs;
-    int64_t off = 0;
-    int key_off = 0, sel_off = 0, cell_cap = 1, max_sel = 0;
-    for (int l = 0; l < nl; ++l) {
-        OrbLevel &L = P.lv[l];
-        L.w = cv_round_f((float)w * h->inv_scale[l]);   // src/ORBextractor.cc:1122
-        L.h = cv_round_f((float)ht * h->inv_scale[l]);
-        L.pitch = orb_align_up(L.w, 64);
-        L.off = (int32_t)off;
-        off = orb_align_up64(off + (int64_t)L.pitch * L.h, 256);
-        if (off > 0x7FFFFFFF) { orbfe_set_error("pyramid slice exceeds 2 GiB"); return ORBFE_ERR_SIZE; }
-        // FAST grid (src/ORBextractor.cc:780-796)
-        const int minb = ORBFE_EDGE - 3;
-        const int maxbx = L.w - ORBFE_EDGE + 3, maxby = L.h - ORBFE_EDGE + 3;
-        const float width = (float)(maxbx - minb), height = (float)(maxby - minb);
-        const float W = 30;
-        if (width < W || height < W) {
-            orbfe_set_error("level %d (%dx%d) is smaller than one 30-px FAST cell plus borders", l, L.w, L.h);
-            return ORBFE_ERR_SIZE;
-        }
-        L.ncols = (int)(width / W);
-        L.nrows = (int)(height / W);
-        L.wcell = (int)ceilf(width / L.ncols);
-        L.hcell = (int)ceilf(height / L.nrows);
-        L.cell0 = (int)cells.size();
-        int key_cap = 0;
-        for (int i = 0; i < L.nrows; ++i) {
-            const float iniY = (float)(minb + i * L.hcell);
-            float maxY = iniY + L.hcell + 6;
-            if (iniY >= maxby - 3) continue;  // :803
-            if (maxY > maxby) maxY = (float)maxby;
-            for (int j = 0; j < L.ncols; ++j) {
-                const float iniX = (float)(minb + j * L.wcell);
-                float maxX = iniX + L.wcell + 6;
-                if (iniX >= maxbx - 6) continue;  // :812
-                if (maxX > maxbx) maxX = (float)maxbx;
-                OrbCell c;
-                c.level = (uint16_t)l;
-                c.x0 = (uint16_t)iniX;
-                c.y0 = (uint16_t)iniY;
-                c.tw = (uint16_t)((int)maxX - (int)iniX);
-                c.th = (uint16_t)((int)maxY - (int)iniY);
-                c.ox = (uint16_t)(j * L.wcell);
-                c.oy = (uint16_t)(i * L.hcell);
-                c.pad = 0;
-                if (c.tw > ORBFE_TILE_MAX || c.th > ORBFE_TILE_MAX) {
-                    orbfe_set_error("FAST tile %dx%d exceeds %d", c.tw, c.th, ORBFE_TILE_MAX);
-                    return ORBFE_ERR_SIZE;
-                }
-                // strict 3x3 NMS keeps at most one keypoint per 2x2 block of the detectable interior
-                const int iw = std::max(0, (int)c.tw - 6), ih = std::max(0, (int)c.th - 6);
-                const int worst = ((iw + 1) / 2) * ((ih + 1) / 2);
-                cell_cap = std::max(cell_cap, worst);
-                key_cap += worst;
-                cells.push_back(c);
-            }
-        }
-        L.ncells = (int)cells.size() - L.cell0;
-        {
-            // non-skipped cells form a full (rows x cols) sub-grid (the skip rules depend on i or j alone)
-            int ncc = 0;
-            for (int k = L.cell0; k < (int)cells.size() && cells[k].y0 == cells[L.cell0].y0; ++k) ++ncc;
-            L.ncc = ncc;
-        }
-        {
-            const OrbCell &clast = cells.back();
-            L.ix1 = L.ncells ? clast.x0 + clast.tw - 3 : ORBFE_EDGE;
-            L.iy1 = L.ncells ? clast.y0 + clast.th - 3 : ORBFE_EDGE;
-        }
-        L.nfeat = h->feat[l];
-        // quadtree roots (src/ORBextractor.cc:545-559)
-        L.nini = (int)roundf((float)(maxbx - minb) / (float)(maxby - minb));
-        if (L.nini < 1 || L.nini > ORBFE_MAX_ROOTS) {  // 0 roots: the reference divides by zero (:547)
-            orbfe_set_error("level %d aspect ratio gives %d quadtree roots (supported: 1..%d)", l, L.nini, ORBFE_MAX_ROOTS);
-            return ORBFE_ERR_SIZE;
-        }
-        L.hx = (float)(maxbx - minb) / L.nini;
-        for (int i = 0; i <= L.nini; ++i) L.root_x[i] = (int)(L.hx * (float)i);
-        L.key_off = key_off;
-        L.key_cap = key_cap;
-        key_off += orb_align_up(std::max(key_cap, 1), 64);
-        L.sel_cap = std::max(L.nfeat + 2, 4 * L.nini);
-        L.sel_off = sel_off;
-        sel_off += orb_align_up(L.sel_cap, 64);
-        max_sel = std::max(max_sel, L.sel_cap);
-        L.scale = h->scale[l];
-        L.patch_size = (float)(int)(ORBFE_PATCH * h->scale[l]);  // :846
-        if (l >= 1) {
-            const OrbLevel &S = P.lv[l - 1];
-            if (S.w >= 2 * L.w) {  // k_pyr_walk: the 4 source pairs of a lane must fit one 8-byte window
-                orbfe_set_error("scale factor too large: level %d is less than half as wide as level %d", l, l - 1);
-                return ORBFE_ERR_ARG;
-            }
-            // tap tables, 4-entry aligned and padded by 8 (a lane reads the taps of its 4 pixels / 8 rows as
-            // 16-byte loads; entries past the end repeat the last one)
-            auto add_axis = [&](int ssize, int dsize, bool is_x) {
-                while (tabs.size() % 4) tabs.push_back(OrbTab{0, 0, 0, 0});
-                const int at = (int)tabs.size();
-                tabs.resize(tabs.size() + dsize + 8);
-                resize_axis(ssize, dsize, is_x, &tabs[at]);
-                for (int i = 0; i < 8; ++i) tabs[at + dsize + i] = tabs[at + dsize - 1];
-                return at;
-            };
-            L.xtab = add_axis(S.w, L.w, true);
-            L.ytab = add_axis(S.h, L.h, false);
-            // k_pyr_walk completes at most one destination row per source row: the source row index must grow strictly
-            for (int d = 1; d < L.h; ++d)
-                if (tabs[(size_t)L.ytab + d].s <= tabs[(size_t)L.ytab + d - 1].s) {
-                    orbfe_set_error("level %d: vertical resize taps are not strictly increasing", l);
-                    return ORBFE_ERR_ARG;
-                }
-            if (orbk_pyramid_lds_bytes(L.h) > 64 * 1024) {
-                orbfe_set_error("level %d too tall for the pyramid kernel's LDS tap table", l);
-                return ORBFE_ERR_SIZE;
-            }
-        }
-        if (L.w > 4095 + 2 * ORBFE_MINB || L.h > 4095 + 2 * ORBFE_MINB) {
-            orbfe_set_error("level %d exceeds the 12-bit key coordinate range", l);
-            return ORBFE_ERR_SIZE;
-        }
-    }
-#ifdef ORBFE_DEVELOPER
-    // Two pyramid levels per launch (ORBFE_OPT_PYR_FUSE, developer builds): for B = 1, 3, 5, ... with a level C = B + 1 above
-    // it, the tiling of B and the first C column / row every tile column / row owns (C pixel (x2, y2) belongs to the tile that
-    // holds its top-left tap (sx(x2), sy(y2)) in its own -- non-overlap -- part).
-    for (int l = 1; l + 1 < nl; l += 2) {
-        OrbLevel &B = P.lv[l];
-        const OrbLevel &C = P.lv[l + 1];
-        const int ngroups = (B.w + 3) / 4;
-        const int ntx0 = (ngroups + 63) / 64;
-        int gx = std::max(2, std::min(64, (ngroups + ntx0 - 1) / ntx0 + (ntx0 > 1 ? 1 : 0)));
-        int gy = std::max(1, 256 / gx);
-        const int trows = gy * ORBFE_PW_ROWS;
-        if (trows < 2 || orbk_pyramid2_lds_bytes(gx, gy) > 60 * 1024) continue;
-        const int tiles_x = ngroups <= gx ? 1 : (ngroups - 1 + gx - 2) / (gx - 1);
-        const int tiles_y = B.h <= trows ? 1 : (B.h - 1 + trows - 2) / (trows - 1);
-        auto add_i32 = [&](const std::vector<int32_t> &v) {
-            while (tabs.size() % 4) tabs.push_back(OrbTab{0, 0, 0, 0});
-            const int at = (int)tabs.size();
-            tabs.resize(tabs.size() + (v.size() + 1) / 2 + 1);
-            memcpy(&tabs[(size_t)at], v.data(), v.size() * sizeof(int32_t));
-            return at;
-        };
-        std::vector<int32_t> cxs((size_t)tiles_x + 1), cys((size_t)tiles_y + 1);
-        for (int t = 0; t <= tiles_x; ++t) {
-            int x2 = 0;
-            if (t == tiles_x) x2 = C.w;
-            else
-                while (x2 < C.w && tabs[(size_t)C.xtab + x2].s < t * (gx - 1) * 4) ++x2;
-            cxs[(size_t)t] = x2;
-        }
-        for (int t = 0; t <= tiles_y; ++t) {
-            int y2 = 0;
-            if (t == tiles_y) y2 = C.h;
-            else
-                while (y2 < C.h && tabs[(size_t)C.ytab + y2].s < t * (trows - 1)) ++y2;
-            cys[(size_t)t] = y2;
-        }
-        B.p2_gx = gx; B.p2_gy = gy; B.p2_tx = tiles_x; B.p2_ty = tiles_y;
-        B.p2_cxs = add_i32(cxs);
-        B.p2_cys = add_i32(cys);
-    }
-#endif
-    P.ncells = (int)cells.size();
-    P.cell_cap = cell_cap;
-    P.max_ncells = 1;
-    for (int l = 0; l < nl; ++l) P.max_ncells = std::max(P.max_ncells, P.lv[l].ncells);
-    P.keys_per_frame = key_off;
-    P.sel_per_frame = sel_off;
-    // node arrays: one slot more than the largest list, rounded to 64 (only the sort buffer inside is a power of two)
-    const int M = orb_align_up(std::max(max_sel + 1, 64), 64);
-    P.node_cap = M;
-    P.max_nini = 1;
-    for (int l = 0; l < nl; ++l) P.max_nini = std::max(P.max_nini, P.lv[l].nini);
-    // Node arrays normally sit in LDS; a level asking for more nodes than fit (about 2400 features on ONE level) keeps them
-    // in global scratch.  What remains is the width of the node index the keys of deep trees carry (14 bits).
-    if (M > 16383) {
-        orbfe_set_error("nfeatures too large: %d quadtree nodes on one level (at most 16383)", max_sel);
-        return ORBFE_ERR_ARG;
-    }
-    for (int l = 0; l < nl; ++l)
-        if (P.lv[l].ncells >= (1 << 16) || P.lv[l].wcell > 63 || P.lv[l].hcell > 63) {
-            orbfe_set_error("level %d: %d FAST cells / cell size exceed the 16 + 6 + 6 bit candidate-order key", l, P.lv[l].ncells);
-            return ORBFE_ERR_SIZE;
-        }
-    P.pyr_frame_bytes = off;
-    if (tabs.empty()) tabs.resize(1);
-    // FAST lane list: per level, per (balanced) row block of <= ORBFE_ROWS_PER_WAVE rows, the 4-px columns x = 16, 20, ... < ix1 form a
-    // strip; strips are packed back to back into single-level waves of 64 lanes.  Where a wave boundary falls inside a
-    // strip, each side gets one halo lane (computes neighbour strengths, outputs nothing).
-    std::vector<OrbLane> flanes, clanes;
-    {
-        std::vector<OrbLane> stream;
-        for (int l = 0; l < nl; ++l) {
-            const OrbLevel &L = P.lv[l];
-            const int rows = L.iy1 - ORBFE_EDGE, ncol = (L.ix1 - 16 + 3) / 4;
-            if (rows <= 0 || ncol <= 0) continue;
-            const int frb = rows_fast;
-            const int nblk = (rows + frb - 1) / frb, rb = (rows + nblk - 1) / nblk;
-            for (int k = 0; k < nblk; ++k) {
-                const int ys = ORBFE_EDGE + k * rb, nr = std::min(rb, L.iy1 - ys);
-                for (int c = 0; c < ncol && nr > 0; ++c) {
-                    OrbLane ln;
-                    ln.x = (uint16_t)(16 + 4 * c);
-                    ln.ys = (uint16_t)ys;
-                    ln.nrows = (uint16_t)nr;
-                    ln.flags = (uint16_t)(l << 8);
-                    stream.push_back(ln);
-                }
-            }
-        }
-        auto same_strip = [](const OrbLane &a, const OrbLane &b2) {
-            return (a.flags >> 8) == (b2.flags >> 8) && a.ys == b2.ys && b2.x == a.x + 4;
-        };
-        // The dense kernel of batch handles (k_fast_map_u) walks whole CELL ROWS: a run of rows starts on a cell-row boundary and
-        // ends on one (or at the end of the detectable interior), and a wave holds runs of ONE length only -- the reference's FAST
-        // never looks across a cell boundary (:798-838), so such a run needs no strength row of its neighbours, and everything that
-        // depends on the position inside the run alone is scalar in the kernel.  k cell rows per run, k = rows_fast / hcell rounded (1 for the default
-        // 40 rows and the ~31-row cells of every shipped configuration).  Handles made for a few frames per call (rows_fast < 24)
-        // keep short balanced runs and the generic kernel: such a call is bound by the length of one wave's walk.
-        const bool cellrows = rows_fast >= 24;
-        P.fast_cellrows = cellrows ? 1 : 0;
-        std::vector<OrbLane> ustream;
-        if (cellrows)
-            for (int l = 0; l < nl; ++l) {
-                const OrbLevel &L = P.lv[l];
-                const int rows = L.iy1 - ORBFE_EDGE, ncol = (L.ix1 - 16 + 3) / 4;
-                if (rows <= 0 || ncol <= 0) continue;
-                const int kc = std::max(1, (rows_fast + L.hcell / 2) / L.hcell), rb = kc * L.hcell;
-                for (int ys = ORBFE_EDGE; ys < L.iy1; ys += rb) {
-                    const int nr = std::min(rb, L.iy1 - ys);
-                    for (int c = 0; c < ncol; ++c) {
-                        OrbLane ln;
-                        ln.x = (uint16_t)(16 + 4 * c);
-                        ln.ys = (uint16_t)ys;
-                        ln.nrows = (uint16_t)nr;
-                        ln.flags = (uint16_t)(l << 8);
-                        ustream.push_back(ln);
-                    }
-                }
-            }
-        const std::vector<OrbLane> &dstream = cellrows ? ustream : stream;
-        size_t i = 0;
-        for (int l = 0; l <= ORBFE_MAX_LEVELS; ++l) P.fwave_off[l] = -1;
-        while (i < dstream.size()) {
-            const int lvl = dstream[i].flags >> 8;
-            const size_t w0 = flanes.size();
-            const OrbLane first = dstream[i];
-            // cell-row form: runs of ONE length per wave (every run starts on a cell row: the lanes are in step)
-            auto fits = [&](const OrbLane &ln) { return !cellrows || ln.nrows == first.nrows; };
-            if (P.fwave_off[lvl] < 0) P.fwave_off[lvl] = (int)(w0 / 64);
-            if (i > 0 && same_strip(dstream[i - 1], dstream[i])) {  // continuing a cut strip: left halo first
-                OrbLane hl = dstream[i - 1];
-                hl.flags |= 1;
-                flanes.push_back(hl);
-            }
-            while (i < dstream.size() && (dstream[i].flags >> 8) == lvl && fits(dstream[i]) && flanes.size() - w0 < 64) {
-                const bool more = i + 1 < dstream.size() && same_strip(dstream[i], dstream[i + 1]);
-                if (flanes.size() - w0 == 63 && more) {  // last slot and the strip goes on: right halo, lane moves on
-                    OrbLane hr = dstream[i];
-                    hr.flags |= 1;
-                    flanes.push_back(hr);
-                    break;
-                }
-                flanes.push_back(dstream[i]);
-                ++i;
-            }
-            while (flanes.size() - w0 < 64) {  // dead lanes (cell-row form: they carry the wave's run, as its scalar row state wants)
-                OrbLane d;
-                d.x = 16;
-                d.ys = cellrows ? first.ys : (uint16_t)ORBFE_EDGE;
-                d.nrows = cellrows ? first.nrows : (uint16_t)0;
-                d.flags = (uint16_t)((lvl << 8) | 1);
-                flanes.push_back(d);
-            }
-        }
-    // Lane list of the lane-compacting form (k_fast_map_c): the same strips, but EVERY piece of a strip inside a wave is closed by a halo
-    // lane on both sides (the 4-px column before / behind it, flag bit 0) -- its lanes take their left / right neighbour pixels from
-    // the neighbouring lanes, not from memory.  At the image's side borders the halo is the column outside the detectable interior
-    // (x = 12 / the column behind the last one: real pixels, nothing inside, nothing output).
-    {
-        size_t i = 0;
-        while (i < stream.size()) {
-            const int lvl = stream[i].flags >> 8;
-            const size_t w0 = clanes.size();
-            while (i < stream.size() && (stream[i].flags >> 8) == lvl && 64 - (clanes.size() - w0) >= 3) {
-                OrbLane hl = stream[i];
-                hl.x = (uint16_t)(hl.x - 4);
-                hl.flags |= 1;
-                clanes.push_back(hl);
-                size_t room = 64 - (clanes.size() - w0) - 1;   // the right halo takes the last slot
-                OrbLane last = stream[i];
-                while (room > 0) {
-                    last = stream[i];
-                    clanes.push_back(last);
-                    ++i;
-                    --room;
-                    if (!(i < stream.size() && same_strip(last, stream[i]))) break;
-                }
-                OrbLane hr = last;
-                hr.x = (uint16_t)(hr.x + 4);
-                hr.flags |= 1;
-                clanes.push_back(hr);
-            }
-            while (clanes.size() - w0 < 64) {  // dead lanes
-                OrbLane d;
-                d.x = 16;
-                d.ys = ORBFE_EDGE;
-                d.nrows = 0;
-                d.flags = (uint16_t)((lvl << 8) | 1);
-                clanes.push_back(d);
-            }
-        }
-    }
-    }
-    P.nfwaves = (int)(flanes.size() / 64);
-    P.nfwaves_c = (int)(clanes.size() / 64);
-    P.fwave_off[nl] = P.nfwaves;
-    for (int l = ORBFE_MAX_LEVELS; l > nl; --l) P.fwave_off[l] = P.nfwaves;
-    for (int l = nl - 1; l >= 0; --l)
-        if (P.fwave_off[l] < 0) P.fwave_off[l] = P.fwave_off[l + 1];   // a level without FAST rows
-    int64_t fast_row_steps = 0;  // wave row steps one frame costs k_fast_map (VALU model of bench.py's roofline)
-    for (int wv = 0; wv < P.nfwaves; ++wv) {
-        int mx = 0;
-        for (int i = 0; i < 64; ++i) mx = std::max(mx, (int)flanes[(size_t)wv * 64 + i].nrows);
-        fast_row_steps += mx + 8;
-    }
-    // blur lane list: every 4-px column of every (balanced, <= ORBFE_ROWS_PER_WAVE rows) row block, single-level waves, no
-    // halos.  Lanes do not talk to each other, so a wave can hold columns of different row blocks.  Columns whose 12-byte
-    // window [x - 4, x + 8) lies inside the row (flag bit 1: no reflected column) skip the byte rearrangement of the border
-    // path, so they get waves of their own.  Everything is laid out in 64-BYTE PIECES (16 lanes): the left and the right piece
-    // of a row block go to the border waves whole, the pieces between them to the interior waves -- every store instruction
-    // then writes whole 64-byte pieces.  (Border waves holding only the 2 - 3 reflected columns of 20-odd row blocks wrote a
-    // lone dword into 64 different lines per store: WRITE_SIZE was 1.19x the output, profiles/r04_ab_experiments.json;
-    // ORBFE_OPT_BLUR_PIECES = 0 brings that packing back for the A/B.)
-    // k_blur7's border lanes: folded horizontal weights per (level, lane type) -- tap t of output pixel c sits on column
-    // reflect101(c - 3 + t), and taps that land on the same column add up (at most 49 + 49: a byte)
-    for (int l = 0; l < nl; ++l) {
-        const OrbLevel &L = P.lv[l];
-        if (L.w < 16) { orbfe_set_error("level %d too narrow for the blur kernel", l); return ORBFE_ERR_SIZE; }
-        const int kern[7] = {18, 34, 49, 55, 49, 34, 18};
-        const int xlast = ((L.w - 1) / 4) * 4;
-        const int xs[4] = {4, 0, xlast - 4, xlast};   // a lane of every type
-        for (int ty = 0; ty < 4; ++ty) {
-            const int x = xs[ty], base = std::min(std::max(x - 4, 0), L.w - 12);
-            for (int j = 0; j < 4; ++j) {
-                const int c = std::min(x + j, L.w - 1);   // output pixels past the row's end are computed and not stored
-                for (int t = 0; t < 7; ++t) {
-                    int col = c - 3 + t;
-                    if (col < 0) col = -col;
-                    if (col >= L.w) col = 2 * L.w - 2 - col;
-                    const int bi = col - base;
-                    if (bi < 0 || bi > 11) { orbfe_set_error("level %d: blur window of column %d does not hold column %d", l, x, col); return ORBFE_ERR_SIZE; }
-                    P.blur_wt[l][ty][3 * j + bi / 4] += (uint32_t)kern[t] << (8 * (bi % 4));
-                }
-            }
-        }
-    }
-    std::vector<OrbLane> blanes;
-    std::vector<OrbLaneR> blanesR;   // the resize job of every blur lane (fused blur + pyramid pass), same index
-    const bool blur_pieces = h->opt_blur_pieces != 0;
-    const int blur_updown = std::max(0, std::min(2, h->opt_blur_updown));
-    for (int l = 0; l < nl; ++l) {
-        const OrbLevel &L = P.lv[l];
-        if (L.w < 16) { orbfe_set_error("level %d too narrow for the blur kernel", l); return ORBFE_ERR_SIZE; }
-        const int brb = rows_blur;
-        const int ncol = (L.w + 3) / 4, nblk = (L.h + brb - 1) / brb, rb = (L.h + nblk - 1) / nblk;
-        // first column of the 64-byte piece that holds the first column whose window reaches past the row's right end
-        const int right0 = (std::min(ncol - 1, std::max(0, (L.w - 8) / 4 + 1)) / 16) * 16;
-        P.bwave_off[l] = (int)(blanes.size() / 64);
-        // fused blur + pyramid pass: destination dword j of level l + 1 is carried by the blur lane of source column
-        // floor(j * ncol / ncolD) (injective: the level shrinks), i.e. by a lane whose blur window lies over its source pixels
-        std::vector<int> dword_of_col((size_t)ncol, -1);
-        if (l + 1 < nl) {
-            const int ncolD = (P.lv[l + 1].w + 3) / 4;
-            for (int j = 0; j < ncolD; ++j) {
-                const int c = std::min(ncol - 1, (int)((int64_t)j * ncol / ncolD));
-                if (dword_of_col[(size_t)c] >= 0) { orbfe_set_error("level %d: two destination dwords on one blur column", l); return ORBFE_ERR_SIZE; }
-                dword_of_col[(size_t)c] = j;
-            }
-        }
-        auto resize_job = [&](int c, int ys, int nr) {
-            OrbLaneR r = {0, 0, 0, 0};
-            if (l + 1 >= nl || c < 0 || dword_of_col[(size_t)c] < 0 || nr <= 0) return r;
-            const OrbLevel &D = P.lv[l + 1];
-            int d0 = 0;
-            while (d0 < D.h && tabs[(size_t)D.ytab + d0].s < ys) ++d0;          // first destination row whose upper source row is in the block
-            int d1 = d0;
-            while (d1 < D.h && tabs[(size_t)D.ytab + d1].s < ys + nr) ++d1;
-            r.dj = (uint16_t)dword_of_col[(size_t)c];
-            r.d0 = (uint16_t)d0;
-            r.nd = (uint16_t)(d1 - d0);
-            return r;
-        };
-        auto dead = [&](bool interior_wave) {
-            OrbLane d;
-            d.x = (uint16_t)(interior_wave ? 4 : 0);
-            d.ys = 0;
-            d.nrows = 0;
-            d.flags = (uint16_t)((l << 8) | 1 | (interior_wave ? 2 : 0));
-            return d;
-        };
-        const int fuse = h->fuse_blur_pyr;   // 0: blur only, 1: every blur lane carries a resize job, 2: resize jobs in waves of their own
-        auto blur_lane = [&](int c, int ys, int nr, bool interior) {
-            OrbLane ln;
-            ln.x = (uint16_t)(4 * c);
-            ln.ys = (uint16_t)ys;
-            ln.nrows = (uint16_t)nr;
-            ln.flags = (uint16_t)((l << 8) | (interior ? 2 : 0));
-            return ln;
-        };
-        auto is_interior = [&](int c) {
-            const bool no_reflection = 4 * c >= 4 && 4 * c + 8 <= L.w;
-            return blur_pieces ? (no_reflection && c >= 16 && c < right0) : no_reflection;
-        };
-        if (fuse == 2 && l + 1 < nl) {
-            // interior blur waves and resize waves of the same row blocks side by side in the wave list (a workgroup is four
-            // consecutive waves): whichever kind touches a source row second finds it in L1 / L2.  Two queues, whole waves of one
-            // kind are emitted as soon as they fill, so neither kind runs more than a row block ahead of the other.
-            std::vector<OrbLane> qb, qr;
-            std::vector<OrbLaneR> qrr;
-            const int ncolD = (P.lv[l + 1].w + 3) / 4;
-            auto flush = [&](bool all) {
-                while (qb.size() >= 64 || qr.size() >= 64 || (all && (!qb.empty() || !qr.empty()))) {
-                    if (qb.size() >= 64 || (all && !qb.empty())) {
-                        const size_t n = std::min<size_t>(64, qb.size());
-                        blanes.insert(blanes.end(), qb.begin(), qb.begin() + n);
-                        blanesR.insert(blanesR.end(), n, OrbLaneR{0, 0, 0, 0});
-                        qb.erase(qb.begin(), qb.begin() + n);
-                        while (blanes.size() % 64) { blanes.push_back(dead(true)); blanesR.push_back(OrbLaneR{0, 0, 0, 0}); }
-                    }
-                    if (qr.size() >= 64 || (all && !qr.empty())) {
-                        const size_t n = std::min<size_t>(64, qr.size());
-                        blanes.insert(blanes.end(), qr.begin(), qr.begin() + n);
-                        blanesR.insert(blanesR.end(), qrr.begin(), qrr.begin() + n);
-                        qr.erase(qr.begin(), qr.begin() + n);
-                        qrr.erase(qrr.begin(), qrr.begin() + n);
-                        while (blanes.size() % 64) {
-                            OrbLane d;
-                            d.x = 0; d.ys = 0; d.nrows = 0;
-                            d.flags = (uint16_t)((l << 8) | 4 | 1);
-                            blanes.push_back(d);
-                            blanesR.push_back(OrbLaneR{0, 0, 0, 0});
-                        }
-                    }
-                }
-            };
-            for (int k = 0; k < nblk; ++k) {
-                const int ys = k * rb, nr = std::min(rb, L.h - ys);
-                if (nr <= 0) continue;
-                for (int c = 0; c < ncol; ++c)
-                    if (is_interior(c)) qb.push_back(blur_lane(c, ys, nr, true));
-                // the destination rows whose upper source row lies in this row block, for every destination dword
-                OrbLaneR rows = resize_job(0, ys, nr);
-                if (dword_of_col[0] < 0) {   // resize_job wants a column that carries a dword: take the row range from any such column
-                    for (int c = 0; c < ncol; ++c)
-                        if (dword_of_col[(size_t)c] >= 0) { rows = resize_job(c, ys, nr); break; }
-                }
-                for (int j = 0; j < ncolD && rows.nd; ++j) {
-                    OrbLane ln;
-                    ln.x = 0; ln.ys = (uint16_t)ys; ln.nrows = 0;
-                    ln.flags = (uint16_t)((l << 8) | 4);
-                    qr.push_back(ln);
-                    qrr.push_back(OrbLaneR{(uint16_t)j, rows.d0, rows.nd, 0});
-                }
-                flush(false);
-            }
-            flush(true);
-            // border blur waves as in the plain layout
-            for (int k = 0; k < nblk; ++k) {
-                const int ys = k * rb, nr = std::min(rb, L.h - ys);
-                if (nr <= 0) continue;
-                for (int c = 0; c < ncol; ++c) {
-                    if (is_interior(c)) continue;
-                    blanes.push_back(blur_lane(c, ys, nr, false));
-                    blanesR.push_back(OrbLaneR{0, 0, 0, 0});
-                    if (blur_pieces && c == ncol - 1)
-                        while (blanes.size() % 16) { blanes.push_back(dead(false)); blanesR.push_back(OrbLaneR{0, 0, 0, 0}); }
-                }
-            }
-            while (blanes.size() % 64) { blanes.push_back(dead(false)); blanesR.push_back(OrbLaneR{0, 0, 0, 0}); }
-        } else
-        for (int pass = 0; pass < 2; ++pass) {  // 0: interior waves, 1: border waves
-            // Odd row blocks walk UPWARDS (flag bit 3, wave-uniform: the even blocks' lanes come first, then the odd blocks'; the
-            // kernel is vertically symmetric).  Two neighbouring row blocks then read the rows around their common boundary at the
-            // same end of their walks -- both at the start or both at the end; all waves of a frame are in flight together -- and
-            // the second reader finds the halo rows in L2 instead of HBM: FETCH_SIZE of the kernel -18 % when every level does it.
-            // Keeping the two directions in waves of their own can cost a level one more (partly filled) wave, i.e. instructions,
-            // which is what the pipeline as a whole is bound by: a (level, pass) is split only where the wave count stays the same
-            // (ORBFE_OPT_BLUR_UPDOWN = 0: never, 2: always; the fused blur + pyramid passes walk downwards only).
-            auto emit = [&](int nparity, std::vector<OrbLane> &ol, std::vector<OrbLaneR> &orr) {
-                for (int par = 0; par < nparity; ++par) {
-                    const uint16_t upflag = par ? 8 : 0;
-                    for (int k = 0; k < nblk; ++k) {
-                        if (nparity == 2 && (k & 1) != par) continue;
-                        const int ys = k * rb, nr = std::min(rb, L.h - ys);
-                        if (nr <= 0) continue;
-                        for (int c = 0; c < ncol; ++c) {
-                            const bool interior = is_interior(c);
-                            if (interior != (pass == 0)) continue;
-                            ol.push_back(blur_lane(c, ys, nr, interior));
-                            ol.back().flags |= upflag;
-                            orr.push_back(fuse == 1 ? resize_job(c, ys, nr) : OrbLaneR{0, 0, 0, 0});
-                            // the right piece is padded to its 16 slots, so that the next row block's left piece starts a piece again
-                            if (blur_pieces && pass == 1 && c == ncol - 1)
-                                while (ol.size() % 16) { ol.push_back(dead(false)); ol.back().flags |= upflag; orr.push_back(OrbLaneR{0, 0, 0, 0}); }
-                        }
-                    }
-                    // dead lanes: shadow a column of the wave's kind
-                    while (ol.size() % 64) { ol.push_back(dead(pass == 0)); ol.back().flags |= upflag; orr.push_back(OrbLaneR{0, 0, 0, 0}); }
-                }
-            };
-            std::vector<OrbLane> l1, l2;
-            std::vector<OrbLaneR> r1, r2;
-            emit(1, l1, r1);
-            if (fuse == 0 && blur_updown) emit(2, l2, r2);
-            const bool split = fuse == 0 && blur_updown && (blur_updown == 2 || l2.size() == l1.size());
-            blanes.insert(blanes.end(), (split ? l2 : l1).begin(), (split ? l2 : l1).end());
-            blanesR.insert(blanesR.end(), (split ? r2 : r1).begin(), (split ? r2 : r1).end());
-        }
-        P.bwave_off[l + 1] = (int)(blanes.size() / 64);
-    }
-    P.nbwaves = (int)(blanes.size() / 64);
-    P.blur_split = h->fuse_blur_pyr == 2;
-    if (P.ini_th < P.min_th) {
-        orbfe_set_error("iniThFAST (%d) must be >= minThFAST (%d)", P.ini_th, P.min_th);
-        return ORBFE_ERR_ARG;
-    }
-
-    ORBFE_HIP(h->d_plan.ensure(sizeof(OrbPlan)));
-    ORBFE_HIP(h->d_tabs.ensure(tabs.size() * sizeof(OrbTab)));
-    ORBFE_HIP(h->d_flanes.ensure(std::max<size_t>(flanes.size(), 1) * sizeof(OrbLane)));
-    ORBFE_HIP(h->d_flanes_c.ensure(std::max<size_t>(clanes.size(), 1) * sizeof(OrbLane)));
-    ORBFE_HIP(h->d_blanes.ensure(std::max<size_t>(blanes.size(), 1) * sizeof(OrbLane)));
-    ORBFE_HIP(h->d_blanesR.ensure(std::max<size_t>(blanesR.size(), 1) * sizeof(OrbLaneR)));
+    OrbPlanTables T;
+    const orbfe_status s = orb_plan_build(h->pin, w, ht, &T);
+    if (s != ORBFE_OK) return s;
+    const struct { DevBuf *buf; const void *p; size_t count, elem; } up[] = {
+        {&h->d_plan, &T.plan, 1, sizeof(OrbPlan)},
+        {&h->d_tabs, T.tabs.data(), T.tabs.size(), sizeof(OrbTab)},
+        {&h->d_flanes, T.flanes.data(), T.flanes.size(), sizeof(OrbLane)},
+        {&h->d_flanes_c, T.clanes.data(), T.clanes.size(), sizeof(OrbLane)},
+        {&h->d_blanes, T.blanes.data(), T.blanes.size(), sizeof(OrbLane)},
+        {&h->d_blanesR, T.blanesR.data(), T.blanesR.size(), sizeof(OrbLaneR)}};
+    for (const auto &u : up) ORBFE_HIP(u.buf->ensure(std::max<size_t>(u.count, 1) * u.elem));
     // synchronous copies: plans change rarely (frame size change), never inside the timed region.  Earlier batches may
     // still be in flight on the handle's stream or on the caller's stream of the previous device call: both are drained
     // before the plan tables they read are overwritten.
     ORBFE_HIP(hipStreamSynchronize(h->stream));
     ORBFE_HIP(wait_last_call(h));
-    ORBFE_HIP(hipMemcpy(h->d_plan.p, &P, sizeof(OrbPlan), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(h->d_tabs.p, tabs.data(), tabs.size() * sizeof(OrbTab), hipMemcpyHostToDevice));
-    if (!flanes.empty())
-        ORBFE_HIP(hipMemcpy(h->d_flanes.p, flanes.data(), flanes.size() * sizeof(OrbLane), hipMemcpyHostToDevice));
-    if (!clanes.empty())
-        ORBFE_HIP(hipMemcpy(h->d_flanes_c.p, clanes.data(), clanes.size() * sizeof(OrbLane), hipMemcpyHostToDevice));
-    if (!blanes.empty())
-        ORBFE_HIP(hipMemcpy(h->d_blanes.p, blanes.data(), blanes.size() * sizeof(OrbLane), hipMemcpyHostToDevice));
-    if (!blanesR.empty())
-        ORBFE_HIP(hipMemcpy(h->d_blanesR.p, blanesR.data(), blanesR.size() * sizeof(OrbLaneR), hipMemcpyHostToDevice));
-    ORBFE_HIP(orbk_prepare_octree(M, P.max_nini, P.w, P.h, P.max_ncells));
-    h->plan = P;
-    h->fast_row_steps = fast_row_steps;
-    h->cells.swap(cells);
-    h->tabs.swap(tabs);
+    for (const auto &u : up)
+        if (u.count) ORBFE_HIP(hipMemcpy(u.buf->p, u.p, u.count * u.elem, hipMemcpyHostToDevice));
+    ORBFE_HIP(orbk_prepare_octree(T.plan.node_cap, T.plan.max_nini, T.plan.w, T.plan.h, T.plan.max_ncells));
+    h->plan = T.plan;
+    h->fast_row_steps = T.fast_row_steps;
     h->plan_valid = true;
     return ORBFE_OK;
 }
@@ -849,11 +164,10 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
 {
     if (!p || !out) { orbfe_set_error("null argument"); return ORBFE_ERR_ARG; }
     *out = nullptr;
-    if (p->nlevels < 1 || p->nlevels > ORBFE_MAX_LEVELS || p->nfeatures < 0 || !(p->scale_factor > 1.0f) ||
-        p->max_batch < 1 || p->max_width < 1 || p->max_height < 1 || p->max_width > 4096 || p->max_height > 4096) {
-        orbfe_set_error("bad orbfe_params (nlevels 1..16, scale_factor > 1, max size <= 4096, max_batch >= 1)");
-        return ORBFE_ERR_ARG;
-    }
+    OrbPlanIn pin;
+    float sigma2[ORBFE_MAX_LEVELS] = {0}, inv_sigma2[ORBFE_MAX_LEVELS] = {0};
+    const orbfe_status cs = orb_ctor_tables(p, &pin, sigma2, inv_sigma2);
+    if (cs != ORBFE_OK) return cs;
     int dev = p->device;
     const orbfe_status rs = orb_resolve_device(&dev);
     if (rs != ORBFE_OK) return rs;
@@ -863,28 +177,9 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
     h->prm = *p;
     h->device = dev;
     DeviceGuard g(dev);
-    // src/ORBextractor.cc:404-421
-    const int nl = p->nlevels;
-    h->scale[0] = 1.0f;
-    h->sigma2[0] = 1.0f;
-    for (int i = 1; i < nl; ++i) {
-        h->scale[i] = h->scale[i - 1] * p->scale_factor;
-        h->sigma2[i] = h->scale[i] * h->scale[i];
-    }
-    for (int i = 0; i < nl; ++i) {
-        h->inv_scale[i] = 1.0f / h->scale[i];
-        h->inv_sigma2[i] = 1.0f / h->sigma2[i];
-    }
-    // src/ORBextractor.cc:426-439
-    const float factor = 1.0f / p->scale_factor;
-    float desired = p->nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nl));
-    int sum = 0;
-    for (int l = 0; l < nl - 1; ++l) {
-        h->feat[l] = cv_round_f(desired);
-        sum += h->feat[l];
-        desired *= factor;
-    }
-    h->feat[nl - 1] = std::max(p->nfeatures - sum, 0);
+    h->pin = pin;
+    memcpy(h->sigma2, sigma2, sizeof(sigma2));
+    memcpy(h->inv_sigma2, inv_sigma2, sizeof(inv_sigma2));
 
     auto fail = [&](orbfe_status s) {
         orbfe_destroy(h);
@@ -893,43 +188,22 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
     if (borrow) {
         h->stream = borrowed;
         h->own_stream = false;
-    } else if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        orbfe_set_error("hipStreamCreate failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(ORBFE_ERR_HIP);
+        if (borrowed_side) {
+            h->side = borrowed_side;
+            h->own_side = false;
+        }
     }
     for (int r = 0; r < ORBFE_PROF_RING; ++r)
         for (int i = 0; i < ORBFE_EV_N; ++i) h->ev[r][i] = nullptr;
     h->ev_ok = true;
+    bool made = true;
+    for (const OwnedStream &s : handle_streams(h))
+        if (s.own) made = made && hipStreamCreateWithFlags(s.s, hipStreamNonBlocking) == hipSuccess;
     for (int r = 0; r < ORBFE_PROF_RING; ++r)
-        for (int i = 0; i < ORBFE_EV_N; ++i)
-            if (hipEventCreate(&h->ev[r][i]) != hipSuccess) { orbfe_set_error("hipEventCreate failed"); return fail(ORBFE_ERR_HIP); }
-    if (borrow && borrowed_side) {
-        h->side = borrowed_side;
-        h->own_side = false;
-    }
-    if ((h->own_side && hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) ||
-        hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
-        orbfe_set_error("side stream / event creation failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(ORBFE_ERR_HIP);
-    }
-    if (h->own_stream && (hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking) != hipSuccess ||
-                          hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking) != hipSuccess)) {
-        orbfe_set_error("copy stream creation failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(ORBFE_ERR_HIP);
-    }
-    for (int k = 0; k < 2; ++k)
-        if (hipEventCreateWithFlags(&h->ev_in[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_cmp[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_out[k], hipEventDisableTiming) != hipSuccess) {
-            orbfe_set_error("pipeline event creation failed");
-            return fail(ORBFE_ERR_HIP);
-        }
-    if (hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_auto, hipEventDisableTiming) != hipSuccess || h->h_auto.ensure(64) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming) != hipSuccess) {
-        orbfe_set_error("event creation failed");
+        for (int i = 0; i < ORBFE_EV_N; ++i) made = made && hipEventCreate(&h->ev[r][i]) == hipSuccess;
+    for (hipEvent_t *e : handle_events(h)) made = made && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (!made || h->h_auto.ensure(64) != hipSuccess) {
+        orbfe_set_error("stream / event creation failed: %s", hipGetErrorString(hipGetLastError()));
         return fail(ORBFE_ERR_HIP);
     }
 #ifdef ORBFE_DEVELOPER
@@ -952,7 +226,7 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
     }
 #endif
     int umax[16];
-    host_umax(umax);
+    orb_host_umax(umax);
     if (orbk_upload_constants(umax) != hipSuccess) {
         orbfe_set_error("constant upload failed: %s", hipGetErrorString(hipGetLastError()));
         return fail(ORBFE_ERR_HIP);
@@ -972,10 +246,8 @@ extern "C" void orbfe_destroy(orbfe_handle *h)
     // nothing of this handle may still be running when its buffers go: the caller's last stream, the side stream of the
     // blur, the host pipeline's copy streams
     if (h->last_stream_valid && h->ev_last) (void)hipEventSynchronize(h->ev_last);
-    if (h->side) (void)hipStreamSynchronize(h->side);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->s_in) (void)hipStreamSynchronize(h->s_in);
-    if (h->s_out) (void)hipStreamSynchronize(h->s_out);
+    for (const OwnedStream &s : handle_streams(h))
+        if (*s.s) (void)hipStreamSynchronize(*s.s);
     DevBuf *bufs[] = {&h->d_plan, &h->d_tabs, &h->d_flanes, &h->d_flanes_c, &h->d_blanes, &h->d_blanesR, &h->d_pyr, &h->d_blur, &h->d_skeys, &h->d_scount, &h->d_knode, &h->d_qtbox, &h->d_qtnodes, &h->d_sel, &h->d_nsel, &h->d_nkeys, &h->d_pad,
                       &h->d_stage[0], &h->d_okps[0], &h->d_odesc[0], &h->d_on[0], &h->d_stage[1], &h->d_okps[1], &h->d_odesc[1], &h->d_on[1]};
     for (DevBuf *b : bufs) b->release();
@@ -983,26 +255,15 @@ extern "C" void orbfe_destroy(orbfe_handle *h)
     PinBuf *pins[] = {&h->h_stage[0], &h->h_okps[0], &h->h_odesc[0], &h->h_on[0], &h->h_stage[1], &h->h_okps[1], &h->h_odesc[1], &h->h_on[1]};
     for (PinBuf *b : pins) b->release();
     h->h_ovf.release();
-    for (int k = 0; k < 2; ++k) {
-        if (h->ev_in[k]) (void)hipEventDestroy(h->ev_in[k]);
-        if (h->ev_cmp[k]) (void)hipEventDestroy(h->ev_cmp[k]);
-        if (h->ev_out[k]) (void)hipEventDestroy(h->ev_out[k]);
-    }
-    if (h->s_in) (void)hipStreamDestroy(h->s_in);
-    if (h->s_out) (void)hipStreamDestroy(h->s_out);
     if (h->ev_ok)
         for (int r = 0; r < ORBFE_PROF_RING; ++r)
             for (int i = 0; i < ORBFE_EV_N; ++i)
                 if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
-    if (h->ev_last) (void)hipEventDestroy(h->ev_last);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_fork2) (void)hipEventDestroy(h->ev_fork2);
-    if (h->ev_auto) (void)hipEventDestroy(h->ev_auto);
+    for (hipEvent_t *e : handle_events(h))
+        if (*e) (void)hipEventDestroy(*e);
     h->h_auto.release();
-    if (h->ev_join2) (void)hipEventDestroy(h->ev_join2);
-    if (h->side && h->own_side) (void)hipStreamDestroy(h->side);
-    if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
+    for (const OwnedStream &s : handle_streams(h))
+        if (*s.s && s.own) (void)hipStreamDestroy(*s.s);
     delete h;
 }
 
@@ -1011,8 +272,8 @@ extern "C" orbfe_status orbfe_get_scales(const orbfe_handle *h, float *scale, fl
 {
     if (!h) return ORBFE_ERR_ARG;
     for (int i = 0; i < h->prm.nlevels; ++i) {
-        if (scale) scale[i] = h->scale[i];
-        if (inv_scale) inv_scale[i] = h->inv_scale[i];
+        if (scale) scale[i] = h->pin.scale[i];
+        if (inv_scale) inv_scale[i] = h->pin.inv_scale[i];
         if (sigma2) sigma2[i] = h->sigma2[i];
         if (inv_sigma2) inv_sigma2[i] = h->inv_sigma2[i];
     }
@@ -1022,7 +283,7 @@ extern "C" orbfe_status orbfe_get_scales(const orbfe_handle *h, float *scale, fl
 extern "C" orbfe_status orbfe_get_features_per_level(const orbfe_handle *h, int32_t *out)
 {
     if (!h || !out) return ORBFE_ERR_ARG;
-    for (int i = 0; i < h->prm.nlevels; ++i) out[i] = h->feat[i];
+    for (int i = 0; i < h->prm.nlevels; ++i) out[i] = h->pin.feat[i];
     return ORBFE_OK;
 }
 
@@ -1116,11 +377,11 @@ extern "C" orbfe_status orbfe_set_option(orbfe_handle *h, int32_t option, int32_
     bool replan = false;
     switch (option) {
     case ORBFE_OPT_OVERLAP: if (!in(-1, 2)) return ORBFE_ERR_ARG; h->overlap = value; break;
-    case ORBFE_OPT_ROWS: if (value && !in(8, 512)) return ORBFE_ERR_ARG; h->opt_rows = value; replan = true; break;
-    case ORBFE_OPT_ROWS_FAST: if (value && !in(8, 512)) return ORBFE_ERR_ARG; h->opt_rows_fast = value; replan = true; break;
-    case ORBFE_OPT_ROWS_BLUR: if (value && !in(8, 512)) return ORBFE_ERR_ARG; h->opt_rows_blur = value; replan = true; break;
-    case ORBFE_OPT_BLUR_PIECES: if (!in(0, 1)) return ORBFE_ERR_ARG; h->opt_blur_pieces = value; replan = true; break;
-    case ORBFE_OPT_BLUR_UPDOWN: if (!in(0, 2)) return ORBFE_ERR_ARG; h->opt_blur_updown = value; replan = true; break;
+    case ORBFE_OPT_ROWS: if (value && !in(8, 512)) return ORBFE_ERR_ARG; h->pin.opt_rows = value; replan = true; break;
+    case ORBFE_OPT_ROWS_FAST: if (value && !in(8, 512)) return ORBFE_ERR_ARG; h->pin.opt_rows_fast = value; replan = true; break;
+    case ORBFE_OPT_ROWS_BLUR: if (value && !in(8, 512)) return ORBFE_ERR_ARG; h->pin.opt_rows_blur = value; replan = true; break;
+    case ORBFE_OPT_BLUR_PIECES: if (!in(0, 1)) return ORBFE_ERR_ARG; h->pin.opt_blur_pieces = value; replan = true; break;
+    case ORBFE_OPT_BLUR_UPDOWN: if (!in(0, 2)) return ORBFE_ERR_ARG; h->pin.opt_blur_updown = value; replan = true; break;
     case ORBFE_OPT_PYR_ROWS: if (value && !in(2, ORBFE_PW_ROWS)) return ORBFE_ERR_ARG; h->kopts.pw_rows = value; break;
     case ORBFE_OPT_QT_THREADS_0:
     case ORBFE_OPT_QT_THREADS_1:
@@ -1134,14 +395,14 @@ extern "C" orbfe_status orbfe_set_option(orbfe_handle *h, int32_t option, int32_
 #else
         if (value != 0 && value != 50 && value != 51) return ORBFE_ERR_ARG;
 #endif
-        h->opt_debug = value;
+        h->pin.opt_debug = value;
         replan = true;
         break;
     case ORBFE_OPT_PYR_FUSE: if (!in(0, 1)) return ORBFE_ERR_ARG; if (developer_only()) return ORBFE_ERR_STATE; h->kopts.pyr_fuse = value; break;
     case ORBFE_OPT_FUSE_BLUR_PYR:
         if (!in(0, 2)) return ORBFE_ERR_ARG;
         if (developer_only()) return ORBFE_ERR_STATE;
-        h->fuse_blur_pyr = value;
+        h->pin.fuse_blur_pyr = value;
         if (value) h->fuse_fast_pyr = 0;   // one fusion at a time
         replan = true;
         break;
@@ -1149,14 +410,14 @@ extern "C" orbfe_status orbfe_set_option(orbfe_handle *h, int32_t option, int32_
         if (!in(0, 3)) return ORBFE_ERR_ARG;
         if (developer_only()) return ORBFE_ERR_STATE;
         h->fuse_fast_pyr = value;
-        if (value && h->fuse_blur_pyr) { h->fuse_blur_pyr = 0; replan = true; }
+        if (value && h->pin.fuse_blur_pyr) { h->pin.fuse_blur_pyr = 0; replan = true; }
         break;
     case ORBFE_OPT_FUSE_FAST_PYR_LEVELS:   // matters for the developer-only variant ORBFE_OPT_FUSE_FAST_PYR alone; 0 = all levels (the default)
         if (!in(0, ORBFE_MAX_LEVELS)) return ORBFE_ERR_ARG;
         if (developer_only()) return ORBFE_ERR_STATE;
         h->fuse_fast_pyr_levels = value ? value : ORBFE_MAX_LEVELS;
         break;
-    case ORBFE_OPT_BLUR_ROUNDING: if (!in(0, 1)) return ORBFE_ERR_ARG; h->prm.blur_rounding = value; replan = true; break;
+    case ORBFE_OPT_BLUR_ROUNDING: if (!in(0, 1)) return ORBFE_ERR_ARG; h->pin.blur_rounding = value; replan = true; break;
     case ORBFE_OPT_REUSE_IDENTICAL_INPUT: if (!in(0, 1)) return ORBFE_ERR_ARG; h->opt_reuse = value; break;
     default: orbfe_set_error("unknown option %d", option); return ORBFE_ERR_ARG;
     }
@@ -1187,10 +448,7 @@ extern "C" orbfe_status orbfe_get_fast_stats(orbfe_handle *h, uint64_t out[3], i
     DeviceGuard g(h->device);
     ORBFE_HIP(wait_last_call(h));
     if (h->fast_mode == 3) {   // auto: the counters belong to the mode selection; report its last completed probe
-        if (h->auto_pending && hipEventQuery(h->ev_auto) == hipSuccess) {
-            memcpy(h->auto_last, h->h_auto.p, sizeof(h->auto_last));
-            h->auto_pending = false;
-        }
+        (void)collect_auto_probe(h);
         for (int i = 0; i < 3; ++i) out[i] = h->auto_last[i];
         return ORBFE_OK;
     }
@@ -1259,9 +517,7 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
     if (fmode == 3 && (int64_t)nframes * h->fast_row_steps < ORBFE_AUTO_MIN_ROW_STEPS) {
         fmode = 0;
     } else if (fmode == 3) {
-        if (h->auto_pending && hipEventQuery(h->ev_auto) == hipSuccess) {   // never waits
-            memcpy(h->auto_last, h->h_auto.p, sizeof(h->auto_last));
-            h->auto_pending = false;
+        if (collect_auto_probe(h)) {
             if (h->auto_last[0] > 0 && (double)h->auto_last[2] > ORBFE_AUTO_DENSE_RATE * 128.0 * (double)h->auto_last[0]) {
                 h->auto_form = 0;
                 h->auto_dense_left = h->auto_hold;
@@ -1271,8 +527,6 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
                 h->auto_hold = ORBFE_AUTO_HOLD_MIN;
                 h->auto_since = 1;
             }
-        } else {
-            (void)hipGetLastError();   // hipErrorNotReady is not an error of ours
         }
         // A host that runs ahead of the GPU enqueues many calls before a probe's answer arrives: those follow the LAST answer
         // (auto_form), only the probe call itself is compacting when that answer was "dense".
@@ -1320,7 +574,7 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
     };
     int ov = h->overlap >= 0 ? h->overlap : (nframes >= 128 ? 2 : 0);
 #ifdef ORBFE_DEVELOPER
-    if (h->fuse_blur_pyr) {
+    if (h->pin.fuse_blur_pyr) {
         // blur(l) and resize(l -> l + 1) in one pass over level l, chained over the levels: level l is read from HBM once for
         // both.  The stage table then shows the fused chain under "pyramid" and nothing under "blur"; `overlap` does not apply
         // (there is no separate blur to put beside anything).
@@ -1644,225 +898,4 @@ extern "C" orbfe_status orbfe_extract_batch(orbfe_handle *h, const uint8_t *cons
     for (int i = 0; i < nframes; ++i)
         if (!grays[i]) { orbfe_set_error("grays[%d] is null", i); return ORBFE_ERR_ARG; }
     return extract_host(h, grays, nframes, w, ht, stride, kps, desc, cap, n_out);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// mvImagePyramid + stage taps
-// ---------------------------------------------------------------------------------------------------
-static orbfe_status check_tap(orbfe_handle *h, int frame, int level)
-{
-    if (!h) return ORBFE_ERR_ARG;
-    if (!h->plan_valid || h->last_nframes == 0) { orbfe_set_error("no extract call yet"); return ORBFE_ERR_STATE; }
-    if (frame < 0 || frame >= h->last_nframes || level < 0 || level >= h->plan.nlevels) {
-        orbfe_set_error("frame/level out of range");
-        return ORBFE_ERR_ARG;
-    }
-    return ORBFE_OK;
-}
-
-extern "C" orbfe_status orbfe_get_level_size(const orbfe_handle *h, int32_t level, int32_t *w, int32_t *ht)
-{
-    if (!h || !h->plan_valid || level < 0 || level >= h->plan.nlevels) return ORBFE_ERR_ARG;
-    if (w) *w = h->plan.lv[level].w;
-    if (ht) *ht = h->plan.lv[level].h;
-    return ORBFE_OK;
-}
-
-static inline int host_reflect101(int p, int len)
-{
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * len - 2 - p;
-    return p;
-}
-
-static orbfe_status fetch_level(orbfe_handle *h, const uint8_t *base, int pitch, int w, int ht, uint8_t *dst,
-                                int dst_stride, int border)
-{
-    std::vector<uint8_t> tmp((size_t)w * ht);
-    ORBFE_HIP(wait_last_call(h));
-    ORBFE_HIP(hipMemcpy2D(tmp.data(), (size_t)w, base, (size_t)pitch, (size_t)w, (size_t)ht, hipMemcpyDeviceToHost));
-    for (int y = -border; y < ht + border; ++y) {
-        const uint8_t *s = tmp.data() + (size_t)host_reflect101(y, ht) * w;
-        uint8_t *d = dst + (size_t)(y + border) * dst_stride;
-        if (border == 0) memcpy(d, s, (size_t)w);
-        else
-            for (int x = -border; x < w + border; ++x) d[x + border] = s[host_reflect101(x, w)];  // :1136-1142
-    }
-    return ORBFE_OK;
-}
-
-extern "C" orbfe_status orbfe_get_pyramid_level(orbfe_handle *h, int32_t frame, int32_t level, uint8_t *dst,
-                                                int32_t dst_stride, int32_t with_border)
-{
-    orbfe_status s = check_tap(h, frame, level);
-    if (s != ORBFE_OK) return s;
-    if (!dst) return ORBFE_ERR_ARG;
-    DeviceGuard g(h->device);
-    const OrbLevel &L = h->plan.lv[level];
-    const int border = with_border ? ORBFE_EDGE : 0;
-    if (dst_stride < L.w + 2 * border) return ORBFE_ERR_ARG;
-    if (level == 0)
-        return fetch_level(h, h->last_gray + (int64_t)frame * h->last_gray_fstride, h->last_gray_pitch, L.w, L.h, dst,
-                           dst_stride, border);
-    return fetch_level(h, (uint8_t *)h->d_pyr.p + (int64_t)frame * h->plan.pyr_frame_bytes + L.off, L.pitch, L.w, L.h,
-                       dst, dst_stride, border);
-}
-
-// The public mvImagePyramid in one go: every level of frame `frame` with its 19-px BORDER_REFLECT_101 frame, level l as a
-// (w_l + 38) x (h_l + 38) block with tight rows at offsets[l] of dst.  One kernel builds the blocks on the device, ONE
-// device-to-host copy brings them over (the per-level orbfe_get_pyramid_level path made 8 pageable 2-D copies and filled the
-// frames on the host: 9.6 ms for a 640x480 frame against 0.18 ms for the extraction itself).
-extern "C" orbfe_status orbfe_get_pyramid_padded(orbfe_handle *h, int32_t frame, uint8_t *dst, size_t cap, size_t *offsets, size_t *total)
-{
-    orbfe_status s = check_tap(h, frame, 0);
-    if (s != ORBFE_OK) return s;
-    DeviceGuard g(h->device);
-    const int nl = h->plan.nlevels;
-    uint32_t off[ORBFE_MAX_LEVELS + 1];
-    uint32_t at = 0;
-    for (int l = 0; l < nl; ++l) {
-        off[l] = at;
-        const OrbLevel &L = h->plan.lv[l];
-        at += (uint32_t)(((size_t)(L.w + 2 * ORBFE_EDGE) * (size_t)(L.h + 2 * ORBFE_EDGE) + 63) & ~(size_t)63);
-    }
-    off[nl] = at;
-    if (offsets)
-        for (int l = 0; l < nl; ++l) offsets[l] = off[l];
-    if (total) *total = at;
-    if (!dst) return ORBFE_OK;   // sizing call
-    if (cap < at) { orbfe_set_error("orbfe_get_pyramid_padded: %zu bytes needed, %zu given", (size_t)at, cap); return ORBFE_ERR_CAP; }
-    OrbPyrView v;
-    s = orbfe_internal_pyramid_view(h, frame, &v);
-    if (s != ORBFE_OK) return s;
-    ORBFE_HIP(wait_last_call(h));
-    ORBFE_HIP(h->d_pad.ensure(at));
-    ORBFE_HIP(orbk_launch_pad_pyramid(v, off, (uint8_t *)h->d_pad.p, h->stream));
-    ORBFE_HIP(hipMemcpyAsync(dst, h->d_pad.p, at, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP(hipStreamSynchronize(h->stream));
-    return ORBFE_OK;
-}
-
-// makes `stream` (a hipStream_t) wait for the handle's last batched call, wherever it ran: the pyramid readers of the
-// matcher (stereo) order themselves behind the extractor with it, without a host synchronisation
-int32_t orbfe_internal_order_after_last_call(orbfe_handle *h, void *stream)
-{
-    if (!h) return ORBFE_ERR_ARG;
-    if (!h->last_stream_valid || h->last_stream == (hipStream_t)stream) return ORBFE_OK;
-    DeviceGuard g(h->device);
-    ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_last, 0));
-    return ORBFE_OK;
-}
-
-int32_t orbfe_internal_pyramid_view(orbfe_handle *h, int frame, OrbPyrView *v)
-{
-    orbfe_status s = check_tap(h, frame, 0);
-    if (s != ORBFE_OK) return s;
-    DeviceGuard g(h->device);
-    v->nlevels = h->plan.nlevels;
-    v->device = h->device;
-    for (int l = 0; l < h->plan.nlevels; ++l) {
-        const OrbLevel &L = h->plan.lv[l];
-        v->ptr[l] = l == 0 ? h->last_gray + (int64_t)frame * h->last_gray_fstride
-                           : (const uint8_t *)h->d_pyr.p + (int64_t)frame * h->plan.pyr_frame_bytes + L.off;
-        v->pitch[l] = l == 0 ? h->last_gray_pitch : L.pitch;
-        v->w[l] = L.w;
-        v->h[l] = L.h;
-        v->scale[l] = h->scale[l];
-        v->inv_scale[l] = h->inv_scale[l];
-        v->fstride[l] = l == 0 ? h->last_gray_fstride : (int64_t)h->plan.pyr_frame_bytes;
-    }
-    v->nframes = h->last_nframes;
-    return ORBFE_OK;
-}
-
-extern "C" orbfe_status orbfe_tap_blurred_level(orbfe_handle *h, int32_t frame, int32_t level, uint8_t *dst,
-                                                int32_t dst_stride)
-{
-    orbfe_status s = check_tap(h, frame, level);
-    if (s != ORBFE_OK) return s;
-    if (!dst) return ORBFE_ERR_ARG;
-    DeviceGuard g(h->device);
-    const OrbLevel &L = h->plan.lv[level];
-    if (dst_stride < L.w) return ORBFE_ERR_ARG;
-    return fetch_level(h, (uint8_t *)h->d_blur.p + (int64_t)frame * h->plan.pyr_frame_bytes + L.off, L.pitch, L.w, L.h,
-                       dst, dst_stride, 0);
-}
-
-extern "C" orbfe_status orbfe_tap_candidates(orbfe_handle *h, int32_t frame, int32_t level, float *xyr, int32_t cap,
-                                             int32_t *n)
-{
-    orbfe_status s = check_tap(h, frame, level);
-    if (s != ORBFE_OK) return s;
-    if (!n) return ORBFE_ERR_ARG;
-    DeviceGuard g(h->device);
-    const OrbPlan &P = h->plan;
-    const OrbLevel &L = P.lv[level];
-    ORBFE_HIP(wait_last_call(h));
-    int32_t nk = 0, nsv = 0;
-    ORBFE_HIP(hipMemcpy(&nk, (int32_t *)h->d_nkeys.p + ((size_t)frame * P.nlevels + level) * ORBFE_NK_STRIDE, sizeof(int32_t),
-                        hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(&nsv, (int32_t *)h->d_scount.p + ((size_t)frame * P.nlevels + level) * ORBFE_NK_STRIDE, sizeof(int32_t),
-                        hipMemcpyDeviceToHost));
-    nsv = std::min(nsv, L.key_cap);
-    *n = nk;
-    if (nk > cap) return ORBFE_ERR_CAP;
-    if (nk == 0) return ORBFE_OK;
-    if (!xyr) return ORBFE_ERR_ARG;
-    // The device keeps the NMS survivors {key, ord} unordered and in place; the per-cell threshold fallback (:818-825) is
-    // the same rule k_octree applies: a survivor counts if it is above iniTh or its cell has no survivor above iniTh.
-    // `ord` is the rank key of the reference's candidate order.
-    std::vector<uint2> sv((size_t)nsv);
-    ORBFE_HIP(hipMemcpy(sv.data(), (uint2 *)h->d_skeys.p + (size_t)frame * P.keys_per_frame + L.key_off,
-                        sizeof(uint2) * (size_t)nsv, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> strong((size_t)L.ncells, 0);
-    for (const uint2 &e : sv)
-        if ((int)orb_key_r(e.x) >= P.ini_th && (e.y >> 12) < (uint32_t)L.ncells) strong[e.y >> 12] = 1;
-    std::vector<uint32_t> kv, ko;
-    for (const uint2 &e : sv)
-        if ((int)orb_key_r(e.x) >= P.ini_th || ((e.y >> 12) < (uint32_t)L.ncells && !strong[e.y >> 12])) {
-            kv.push_back(e.x);
-            ko.push_back(e.y);
-        }
-    if ((int)kv.size() != nk) {
-        orbfe_set_error("candidate tap: host filter found %d keys, device counted %d", (int)kv.size(), nk);
-        return ORBFE_ERR_STATE;
-    }
-    std::vector<int> order((size_t)nk);
-    for (int i = 0; i < nk; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return ko[a] < ko[b]; });
-    for (int i = 0; i < nk; ++i) {
-        const uint32_t k = kv[order[i]];
-        xyr[3 * i] = (float)orb_key_x(k);
-        xyr[3 * i + 1] = (float)orb_key_y(k);
-        xyr[3 * i + 2] = (float)orb_key_r(k);
-    }
-    return ORBFE_OK;
-}
-
-extern "C" orbfe_status orbfe_tap_selected(orbfe_handle *h, int32_t frame, int32_t level, float *xyr, int32_t cap,
-                                           int32_t *n)
-{
-    orbfe_status s = check_tap(h, frame, level);
-    if (s != ORBFE_OK) return s;
-    if (!n) return ORBFE_ERR_ARG;
-    DeviceGuard g(h->device);
-    const OrbPlan &P = h->plan;
-    const OrbLevel &L = P.lv[level];
-    ORBFE_HIP(wait_last_call(h));
-    int32_t ns = 0;
-    ORBFE_HIP(hipMemcpy(&ns, (int32_t *)h->d_nsel.p + (size_t)frame * P.nlevels + level, sizeof(int32_t),
-                        hipMemcpyDeviceToHost));
-    *n = ns;
-    if (ns > cap) return ORBFE_ERR_CAP;
-    if (ns == 0) return ORBFE_OK;
-    if (!xyr) return ORBFE_ERR_ARG;
-    std::vector<uint32_t> keys((size_t)ns);
-    ORBFE_HIP(hipMemcpy(keys.data(), (uint32_t *)h->d_sel.p + (size_t)frame * P.sel_per_frame + L.sel_off,
-                        sizeof(uint32_t) * (size_t)ns, hipMemcpyDeviceToHost));
-    for (int i = 0; i < ns; ++i) {
-        xyr[3 * i] = (float)orb_key_x(keys[i]);
-        xyr[3 * i + 1] = (float)orb_key_y(keys[i]);
-        xyr[3 * i + 2] = (float)orb_key_r(keys[i]);
-    }
-    return ORBFE_OK;
 }

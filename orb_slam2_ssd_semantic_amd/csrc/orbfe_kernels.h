@@ -1,4 +1,4 @@
-// orbfe_kernels.h -- launcher interface between the host API (orbfe_api.hip) and the hand-written HIP kernels (gfx950 / CDNA4,
+// orbfe_kernels.h -- launcher interface between the host API (orbfe_api.hip; the plan it uploads: orbfe_plan.hip) and the hand-written HIP kernels (gfx950 / CDNA4,
 // wave64) of the ORB extractor, one file per stage.
 //
 // Reference behaviour restated (paths relative to /root/reference):
@@ -70,7 +70,8 @@ size_t orbk_octree_box_bytes(int node_cap);
 size_t orbk_octree_node_bytes(int node_cap);  // global scratch per (frame, level) when the node arrays do not fit the LDS
 hipError_t orbk_prepare_octree(int node_cap, int max_nini, int w, int h, int ncells);
 #define ORBFE_PW_ROWS 16  // destination rows per lane run of the pyramid kernels (8, 24, 32 measured slower)
-size_t orbk_pyramid_lds_bytes(int dh);  // dynamic LDS of the pyramid kernel for a destination level of dh rows
+// dynamic LDS of the pyramid kernel for a destination level of dh rows (inline: the planner, orbfe_plan.hip, bounds it without the kernel file)
+inline size_t orbk_pyramid_lds_bytes(int dh) { return (size_t)(dh + 8) * sizeof(uint2) + (size_t)ORBFE_PW_ROWS * 256 * 4; }
 hipError_t orbk_launch_pyramid(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_fast(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_octree(const OrbLaunch &a, hipStream_t st);
@@ -83,10 +84,11 @@ hipError_t orbk_launch_fast_pyr(const OrbLaunch &a, int nfused, int spread, hipS
 hipError_t orbk_launch_fast_levels(const OrbLaunch &a, int l0, int l1, int clear, hipStream_t st);
 // blur of every level and the pyramid in one chained pass (replaces orbk_launch_pyramid + orbk_launch_blur)
 hipError_t orbk_launch_blur_pyr(const OrbLaunch &a, hipStream_t st);
-size_t orbk_pyramid2_lds_bytes(int gx, int gy);  // dynamic LDS of the two-level pyramid kernel for a tile of gx column groups x gy runs
+// dynamic LDS of the two-level pyramid kernel for a tile of gx column groups x gy runs
+inline size_t orbk_pyramid2_lds_bytes(int gx, int gy) { return (size_t)(gy * ORBFE_PW_ROWS + 8) * sizeof(uint2) + (size_t)gy * ORBFE_PW_ROWS * gx * 4; }
 #endif
 
-// device view of the pyramid the handle built in its last call (orbfe_api.hip), for kernels outside the extractor
+// device view of the pyramid the handle built in its last call (orbfe_taps.hip), for kernels outside the extractor
 struct OrbPyrView {
     int32_t nlevels, device;
     const uint8_t *ptr[ORBFE_MAX_LEVELS];

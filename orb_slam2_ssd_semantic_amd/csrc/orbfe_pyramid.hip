@@ -263,12 +263,6 @@ hipError_t orbk_launch_pad_pyramid(const OrbPyrView &v, const uint32_t *off, uin
 // ---------------------------------------------------------------------------------------------------
 // launchers (host)
 // ---------------------------------------------------------------------------------------------------
-size_t orbk_pyramid_lds_bytes(int dh) { return (size_t)(dh + 8) * sizeof(uint2) + (size_t)ORBFE_PW_ROWS * 256 * 4; }
-
-#ifdef ORBFE_DEVELOPER
-size_t orbk_pyramid2_lds_bytes(int gx, int gy) { return (size_t)(gy * ORBFE_PW_ROWS + 8) * sizeof(uint2) + (size_t)gy * ORBFE_PW_ROWS * gx * 4; }
-#endif
-
 static void pyr_launch_walk(const OrbLevel &D, const PyrArgs &pa, int nframes, hipStream_t st)
 {
     dim3 grid((pyr_walk_waves(D.w, pa.nrblk) + 3) / 4, nframes);
