@@ -582,8 +582,12 @@ orbfe_status orbfe_search_by_bow_batch_device(orbfe_matcher *m, const orbfe_keyp
  * the sequence through the Frame constructor = ORBextractor::operator(), then matched against its predecessor -- BASELINE
  * config 3) for a device-resident SEQUENCE in one call.
  *
- * A pipeline owns `npipes` pipes; a pipe = one extractor handle + one matcher handle + one stream.  A call cuts its
- * nframes into sub-batches of p->max_batch frames (the last one may be shorter) and runs sub-batch j on pipe j mod npipes,
+ * A pipeline owns `npipes` pipes; a pipe = one extractor handle + one matcher handle on one of the pipeline's streams.  The
+ * pipeline creates no more kernel streams than the process has hardware queues (GPU_MAX_HW_QUEUES, read once, default 4:
+ * streams that share a queue cannot overlap and stall each other at every cross-stream wait): with queues >= npipes + 1 every
+ * pipe has a stream and the pipes' blur a shared side stream, with fewer the side stream takes one queue and queues - 1 pipes
+ * take work.  A call cuts its
+ * nframes into sub-batches of p->max_batch frames (the last one may be shorter) and deals them round robin to those pipes,
  * so that the VALU-bound FAST pass of one sub-batch shares the chip with the HBM / LDS-bound stages of its neighbours
  * (one pipe 273 k, three pipes 302 k frames/s at 1024-frame sub-batches).  Frame k is matched against frame
  * k - 1 as orbfe_match_bf does (best <= th, ratio, rotation histogram) ACROSS sub-batch boundaries; frame 0 of a call is

@@ -160,6 +160,16 @@ orbfe_status orbfe_internal_create_on_stream(const orbfe_params *p, void *st, vo
     return create_impl(p, (hipStream_t)st, (hipStream_t)side, true, out);
 }
 
+// The side stream of a pipe's handle from its next call on (null: none).  The pipeline's device and host entry points plan their
+// streams apart (orbfe_pipe_plan.h) and hand each call's side stream in; a call joins its blur before it returns, so nothing of
+// the handle is left on the stream it gives up.
+orbfe_status orbfe_internal_set_side_stream(orbfe_handle *h, void *side)
+{
+    if (!h || h->own_side) return ORBFE_ERR_ARG;
+    h->side = (hipStream_t)side;
+    return ORBFE_OK;
+}
+
 static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hipStream_t borrowed_side, bool borrow, orbfe_handle **out)
 {
     if (!p || !out) { orbfe_set_error("null argument"); return ORBFE_ERR_ARG; }
@@ -188,10 +198,8 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
     if (borrow) {
         h->stream = borrowed;
         h->own_stream = false;
-        if (borrowed_side) {
-            h->side = borrowed_side;
-            h->own_side = false;
-        }
+        h->side = borrowed_side;   // null: the pipeline has no queue to spare for a side stream, the blur runs in `st` (overlap 0)
+        h->own_side = false;
     }
     for (int r = 0; r < ORBFE_PROF_RING; ++r)
         for (int i = 0; i < ORBFE_EV_N; ++i) h->ev[r][i] = nullptr;
@@ -573,6 +581,7 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
         return ORBFE_OK;
     };
     int ov = h->overlap >= 0 ? h->overlap : (nframes >= 128 ? 2 : 0);
+    if (!h->side) ov = 0;   // a pipe of a pipeline that fits its streams to the hardware queues and has none left for the blur
 #ifdef ORBFE_DEVELOPER
     if (h->pin.fuse_blur_pyr) {
         // blur(l) and resize(l -> l + 1) in one pass over level l, chained over the levels: level l is read from HBM once for
@@ -599,7 +608,7 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
     // pyramid, runs on the side stream BESIDE the pyramid chain (two FAST waves leave room for four resize waves on a SIMD),
     // FAST of the other levels after both; it has its own event pair (ev_fork2 / ev_join2), the blur fork keeps ev_fork / ev_join
     const bool ffp = h->fuse_fast_pyr == 1 || h->fuse_fast_pyr == 2;
-    const bool fside = h->fuse_fast_pyr == 3;
+    const bool fside = h->fuse_fast_pyr == 3 && h->side;
     if (fside) {
         ORBFE_HIP(orbk_launch_fast_levels(a, 0, 0, 1, st));   // the clear only
         ORBFE_HIP(hipEventRecord(h->ev_fork2, st));

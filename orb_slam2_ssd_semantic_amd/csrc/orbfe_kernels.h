@@ -103,5 +103,7 @@ struct orbfe_handle;
 // fills `v` for frame `frame` of the last batch and waits for the handle's own stream; ORBFE_ERR_STATE before any call
 int32_t orbfe_internal_pyramid_view(orbfe_handle *h, int frame, OrbPyrView *v);
 int32_t orbfe_internal_order_after_last_call(orbfe_handle *h, void *stream);
-// a handle for a pipe of orbfe_pipeline: `st` (the pipe's stream) serves as its own stream, `side` as its blur stream
+// a handle for a pipe of orbfe_pipeline: `st` (the pipe's stream) serves as its own stream, `side` as its blur stream (null: the blur
+// runs in the stream of the call); orbfe_internal_set_side_stream changes `side` between two calls
 orbfe_status orbfe_internal_create_on_stream(const orbfe_params *p, void *st, void *side, orbfe_handle **out);
+orbfe_status orbfe_internal_set_side_stream(orbfe_handle *h, void *side);

@@ -1,0 +1,79 @@
+// orbfe_pipe_plan.h -- the sequence pipeline's stream plan, made on the host without a device call: how many streams a pipeline
+// of P pipes creates on a runtime that has Q hardware queues, and which stream every pipe launches on.  orbfe_pipeline.hip
+// creates what orb_pipe_plan returns; tests/test_pipe_plan.py and tests/cpp/test_pipe_plan_sanitize.cpp reach it without a GPU.
+//
+// Why a plan: the HIP runtime gives every stream one hardware queue for life and, once all Q queues are taken, lets further
+// streams share them.  Packets of one queue run in submission order, so a cross-stream wait (hipStreamWaitEvent) of one stream
+// holds everything that was submitted behind it to the same queue -- the kernels of the OTHER streams on that queue included.
+// Two kernel streams on one queue therefore cannot overlap, and a wait of one of them stalls the other: a pipeline never creates
+// more kernel-carrying streams than there are queues.  A queue also runs one kernel at a time, so Q bounds the kernels in flight
+// whatever the streams are: what the plan decides is which Q kernels those are.  Measured on 4 queues with 12 pipes asked for
+// (profiles/pipe_queues.md): 3 kernel streams + the side stream that puts the blur beside the latency-bound quadtree beat 4 kernel
+// streams with the blur in line, which equal 12 streams that share the queues.
+#pragma once
+
+#include <errno.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#define ORBFE_PIPE_MAX_PIPES 64        // orbfe_pipeline_create's upper bound
+#define ORBFE_PIPE_DEFAULT_QUEUES 4    // the runtime's own default of GPU_MAX_HW_QUEUES
+#define ORBFE_PIPE_MAX_QUEUES 32       // more queues than this count as this many
+#define ORBFE_PIPE_COPY_STREAMS 2      // H2D and D2H stream of the host entry point (orbfe_pipeline_extract_match)
+
+struct OrbPipePlan {
+    int32_t P, Q, copies;   // the inputs: pipes asked for, hardware queues (clamped to 1..ORBFE_PIPE_MAX_QUEUES), copy streams in use
+    int32_t S;              // kernel streams
+    int32_t P_eff;          // pipes that get work = min(P, S): sub-batch j of a call runs on pipe (rot + j) mod P_eff
+    int32_t side;           // 1: one side stream, shared by the pipes' blur; 0: every pipe's blur runs in the pipe's own stream
+    // the pipeline's streams in creation order: [0, first) the copy streams, [first, first + S) the kernel streams, then the side stream
+    int32_t first, side_index /* -1: none */, nstreams;
+    int32_t stream_of_pipe[ORBFE_PIPE_MAX_PIPES];   // kernel stream (0 .. S - 1) of pipe i < P; pipes beyond P_eff double up on them
+};
+
+// The value of GPU_MAX_HW_QUEUES as the runtime will take it, from the variable's text: null, empty, not a number or below 1 is
+// the default, anything above ORBFE_PIPE_MAX_QUEUES counts as ORBFE_PIPE_MAX_QUEUES.
+static inline int32_t orb_pipe_parse_queues(const char *text)
+{
+    if (!text || !*text) return ORBFE_PIPE_DEFAULT_QUEUES;
+    char *end = nullptr;
+    errno = 0;
+    const long long v = strtoll(text, &end, 10);
+    if (end == text) return ORBFE_PIPE_DEFAULT_QUEUES;
+    while (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r') ++end;
+    if (*end) return ORBFE_PIPE_DEFAULT_QUEUES;   // trailing text: not a number
+    if (errno == ERANGE) return v > 0 ? ORBFE_PIPE_MAX_QUEUES : ORBFE_PIPE_DEFAULT_QUEUES;
+    if (v < 1) return ORBFE_PIPE_DEFAULT_QUEUES;
+    return v > ORBFE_PIPE_MAX_QUEUES ? ORBFE_PIPE_MAX_QUEUES : (int32_t)v;
+}
+
+// the process's hardware queues: the environment is read once, here and nowhere else (the runtime reads it once as well)
+static inline int32_t orb_pipe_env_queues()
+{
+    static const int32_t q = orb_pipe_parse_queues(getenv("GPU_MAX_HW_QUEUES"));
+    return q;
+}
+
+// The plan of P pipes on Q queues.  The copy streams, where in use, come first: they take their queues off the top.  If what is
+// left holds P kernel streams and a side stream the plan is the one the pipeline was tuned with on 16 queues (P + 1 streams);
+// otherwise the last queue that is left goes to the side stream and every other one to a kernel stream -- with a single queue
+// left there is one kernel stream and the blur runs in it.  False (and *out untouched) for a P outside
+// 1 .. ORBFE_PIPE_MAX_PIPES; any Q is clamped.
+static inline bool orb_pipe_plan(int32_t P, int32_t Q, bool copies, OrbPipePlan *out)
+{
+    if (!out || P < 1 || P > ORBFE_PIPE_MAX_PIPES) return false;
+    OrbPipePlan pl;
+    pl.P = P;
+    pl.Q = Q < 1 ? 1 : (Q > ORBFE_PIPE_MAX_QUEUES ? ORBFE_PIPE_MAX_QUEUES : Q);
+    pl.copies = copies ? 1 : 0;
+    pl.first = copies ? ORBFE_PIPE_COPY_STREAMS : 0;
+    const int32_t left = pl.Q - pl.first < 1 ? 1 : pl.Q - pl.first;   // queues for kernel-carrying streams
+    pl.side = left >= 2 ? 1 : 0;
+    pl.S = left >= P + 1 ? P : (pl.side ? left - 1 : 1);
+    pl.P_eff = P < pl.S ? P : pl.S;
+    pl.side_index = pl.side ? pl.first + pl.S : -1;
+    pl.nstreams = pl.first + pl.S + pl.side;
+    for (int32_t i = 0; i < ORBFE_PIPE_MAX_PIPES; ++i) pl.stream_of_pipe[i] = i < P ? i % pl.S : -1;
+    *out = pl;
+    return true;
+}

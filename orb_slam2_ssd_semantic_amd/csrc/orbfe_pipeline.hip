@@ -2,33 +2,59 @@
 //
 // What it stands for in the reference: the frame loop of perfect/Examples/RGB-D/rgbd_tum.cc:77-119 -- one frame after the
 // other through ORBextractor::operator() (Frame constructor) and a match against the previous frame.  Here a whole resident
-// SEQUENCE goes through in one call: it is cut into sub-batches of `max_batch` frames, sub-batch j runs on pipe j mod P -- a
+// SEQUENCE goes through in one call: it is cut into sub-batches of `max_batch` frames, sub-batch j runs on pipe j mod P_eff -- a
 // pipe = one extractor handle + one matcher handle + one stream, so that the VALU-bound FAST pass of one sub-batch shares the
 // chip with the HBM / LDS-bound stages of its neighbours -- and frame k is matched against frame k - 1 ACROSS sub-batch
-// boundaries and across calls (the last frame of a call is carried over), i.e. a real sequence.
+// boundaries and across calls (the last frame of a call is carried over), i.e. a real sequence.  How many streams there are, and
+// with them P_eff, follows from the hardware queues of the process (orbfe_pipe_plan.h).
 //
 // Host code only: every kernel is launched through the extractor / matcher entry points of this library.
+#include <mutex>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "orbfe_common.h"
 #include "orbfe_kernels.h"
 #include "orbfe_matcher.h"
+#include "orbfe_pipe_plan.h"
 
-#ifndef ORBFE_PIPE_SIDE_STREAMS
-#define ORBFE_PIPE_SIDE_STREAMS 1   // side streams of a pipeline, shared by its pipes (A/B -DORBFE_PIPE_SIDE_STREAMS=n, 12 pipes: 1: 314-315 k frames/s resident and 0.91 of the PCIe link through the host entry point; 2: 312-313 k / 0.87; 4: 299-301 k; one per pipe: 310 k / 0.90)
-#endif
+// Streams outlive their pipeline.  Which hardware queue the runtime gives a new stream depends on every stream the process has
+// made and destroyed before, and a pipeline whose copy, kernel and side streams landed on queues of their own runs its host
+// entry point at 0.95 of the PCIe link where one that shares queues among them reaches 0.68 (profiles/pipe_queues.md).  A
+// destroyed pipeline therefore hands its streams, drained, to the next one of the same device, in the same roles.
+static std::mutex g_spare_mu;
+static std::vector<std::pair<int, hipStream_t>> g_spare;   // (device, stream); taken from the back
+
+static hipStream_t take_spare_stream(int device)
+{
+    std::lock_guard<std::mutex> lk(g_spare_mu);
+    for (size_t i = g_spare.size(); i-- > 0;)
+        if (g_spare[i].first == device) {
+            hipStream_t s = g_spare[i].second;
+            g_spare.erase(g_spare.begin() + (ptrdiff_t)i);
+            return s;
+        }
+    return nullptr;
+}
 
 struct orbfe_pipeline {
     orbfe_params prm;
     int device = 0;
-    int P = 1;     // pipes
+    int P = 1;     // pipes (handles); cur.P_eff of them take sub-batches
+    int Q = ORBFE_PIPE_DEFAULT_QUEUES;   // hardware queues the streams are fitted to
+    OrbPipePlan cur;   // the plan of the call in flight or last made: the device entry point's or the host entry point's
+    bool cur_valid = false;
     int F = 1;     // frames per sub-batch (prm.max_batch)
     int cap = 0;   // keypoint slots per frame
     std::vector<orbfe_handle *> ext;
     std::vector<orbfe_matcher *> mat;
-    std::vector<hipStream_t> st;
-    std::vector<hipStream_t> side;     // side streams (the extractors' blur), shared: pipe i uses side[i % side.size()]
+    // Every stream of the pipeline, created as a plan first asks for it.  A plan deals the roles in this order: the host entry
+    // point's copy streams (s_in, s_out), the kernel streams, the side stream (the extractors' blur, shared by the pipes).
+    std::vector<hipStream_t> pool;
+    hipStream_t stream_of(int pipe) const { return pool[(size_t)(cur.first + cur.stream_of_pipe[pipe])]; }
+    hipStream_t side() const { return cur.side ? pool[(size_t)cur.side_index] : nullptr; }
+    std::vector<char> ev_end_valid;
     std::vector<hipEvent_t> ev_end;    // per pipe: behind the pipe's last launch of the most recent call
     std::vector<hipEvent_t> ev_ext;    // per sub-batch index: extraction finished (most recent call)
     std::vector<hipEvent_t> ev_match;  // per sub-batch index: matcher finished (most recent call)
@@ -67,7 +93,8 @@ struct orbfe_pipeline {
     int32_t *d_on[NSETS] = {nullptr, nullptr, nullptr}, *d_om[NSETS] = {nullptr, nullptr, nullptr}, *d_onm[NSETS] = {nullptr, nullptr, nullptr};
     size_t in_bytes = 0;
     int out_frames = 0;
-    hipStream_t s_in = nullptr, s_out = nullptr;
+    hipStream_t s_in() const { return pool[0]; }   // (with a plan that has copy streams)
+    hipStream_t s_out() const { return pool[1]; }
     hipEvent_t ev_out[NSETS] = {nullptr, nullptr, nullptr};
 };
 
@@ -90,7 +117,7 @@ static orbfe_status ensure_seq(orbfe_pipeline *pl, int nframes)
 {
     if (nframes + 1 <= pl->seq_len) return ORBFE_OK;
     // the index table is about to be replaced: no launch of an earlier call may still read it
-    for (hipStream_t s : pl->st) ORBFE_HIP(hipStreamSynchronize(s));
+    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
     if (pl->d_seq) ORBFE_HIP(hipFree(pl->d_seq));
     pl->d_seq = nullptr;
     pl->seq_len = 0;
@@ -107,7 +134,7 @@ extern "C" void orbfe_pipeline_destroy(orbfe_pipeline *pl)
 {
     if (!pl) return;
     DeviceGuard g(pl->device);
-    for (hipStream_t s : pl->st)
+    for (hipStream_t s : pl->pool)
         if (s) (void)hipStreamSynchronize(s);
     for (orbfe_handle *h : pl->ext) orbfe_destroy(h);
     for (orbfe_matcher *m : pl->mat) orbfe_matcher_destroy(m);
@@ -126,26 +153,49 @@ extern "C" void orbfe_pipeline_destroy(orbfe_pipeline *pl)
         if (pl->d_cn[k]) (void)hipFree(pl->d_cn[k]);
     }
     if (pl->d_seq) (void)hipFree(pl->d_seq);
-    if (pl->s_in) (void)hipStreamSynchronize(pl->s_in);
-    if (pl->s_out) (void)hipStreamSynchronize(pl->s_out);
     for (int k = 0; k < orbfe_pipeline::NSETS; ++k) {
         void *bufs[] = {pl->d_in[k], pl->d_okps[k], pl->d_odesc[k], pl->d_on[k], pl->d_om[k], pl->d_onm[k]};
         for (void *b : bufs)
             if (b) (void)hipFree(b);
         if (pl->ev_out[k]) (void)hipEventDestroy(pl->ev_out[k]);
     }
-    if (pl->s_in) (void)hipStreamDestroy(pl->s_in);
-    if (pl->s_out) (void)hipStreamDestroy(pl->s_out);
-    for (hipStream_t s : pl->st)
-        if (s) (void)hipStreamDestroy(s);
-    for (hipStream_t s : pl->side)
-        if (s) (void)hipStreamDestroy(s);
+    {   // (drained above) last stream first, so that the next pipeline's stream i is this one's stream i
+        std::lock_guard<std::mutex> lk(g_spare_mu);
+        for (size_t i = pl->pool.size(); i-- > 0;)
+            if (pl->pool[i]) g_spare.push_back(std::make_pair(pl->device, pl->pool[i]));
+    }
     delete pl;
 }
 
-extern "C" orbfe_status orbfe_pipeline_create(const orbfe_params *p, int32_t npipes, orbfe_pipeline **out)
+// Makes `plan` the pipeline's current one.  A change of plan (the device entry point after the host entry point or the other way
+// round, another orbfe_pipeline_set_host_pipes) moves handles to other streams and streams to other roles: everything in flight
+// is drained first, which no sequence of calls of one kind ever pays.
+static orbfe_status apply_plan(orbfe_pipeline *pl, const OrbPipePlan &plan)
 {
-    if (!p || !out || npipes < 1 || npipes > 64) {
+    const bool same = pl->cur_valid && pl->cur.copies == plan.copies && pl->cur.S == plan.S && pl->cur.side == plan.side &&
+                      pl->cur.P_eff == plan.P_eff;
+    if (same) return ORBFE_OK;
+    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
+    while ((int)pl->pool.size() < plan.nstreams) {
+        hipStream_t st = take_spare_stream(pl->device);
+        if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { orbfe_set_error("pipeline stream creation failed"); return ORBFE_ERR_HIP; }
+        pl->pool.push_back(st);
+    }
+    pl->cur = plan;
+    pl->cur_valid = true;
+    pl->rot %= plan.P_eff;
+    for (int i = 0; i < pl->P && i < (int)pl->ext.size(); ++i) {
+        const orbfe_status s = orbfe_internal_set_side_stream(pl->ext[(size_t)i], (void *)pl->side());
+        if (s != ORBFE_OK) return s;
+    }
+    return ORBFE_OK;
+}
+
+// orbfe_pipeline_create for a process with `queues` hardware queues (not in include/orbfe.h: the tests walk the queue counts
+// with it, whatever the environment says)
+extern "C" orbfe_status orbfe_internal_pipeline_create_queues(const orbfe_params *p, int32_t npipes, int32_t queues, orbfe_pipeline **out)
+{
+    if (!p || !out || npipes < 1 || npipes > ORBFE_PIPE_MAX_PIPES) {
         orbfe_set_error("bad argument to orbfe_pipeline_create (1..64 pipes)");
         return ORBFE_ERR_ARG;
     }
@@ -154,6 +204,7 @@ extern "C" orbfe_status orbfe_pipeline_create(const orbfe_params *p, int32_t npi
     if (!pl) return ORBFE_ERR_NOMEM;
     pl->prm = *p;
     pl->P = npipes;
+    pl->Q = std::min(std::max(queues, 1), ORBFE_PIPE_MAX_QUEUES);
     pl->F = p->max_batch;
     auto fail = [&](orbfe_status s) {
         orbfe_pipeline_destroy(pl);
@@ -167,29 +218,31 @@ extern "C" orbfe_status orbfe_pipeline_create(const orbfe_params *p, int32_t npi
         pl->prm.device = dev;
     }
     DeviceGuard g(pl->device);
-    // One stream per pipe, shared by the pipe's extractor and matcher handles (which then create none of their own but the
-    // extractor's side stream): the runtime multiplexes all streams of a process onto a few hardware queues, and every idle
-    // stream less is a copy stream that does not have to share its queue with a kernel stream.
+    // The streams follow the plan of orbfe_pipe_plan.h: the runtime gives every stream one hardware queue for life, packets of a
+    // queue run in submission order, and a cross-stream wait holds everything behind it in its queue, other streams' kernels
+    // included -- so the pipeline creates no more kernel-carrying streams than the process has queues, the side stream for the
+    // blur among them.  Each of the kernel streams is shared by the extractor and matcher handles of its pipes
+    // (which create none of their own); the handles beyond P_eff stay valid for orbfe_pipeline_extractor / _matcher and get
+    // no sub-batches.
+    {
+        OrbPipePlan plan;
+        if (!orb_pipe_plan(npipes, pl->Q, false, &plan)) return fail(ORBFE_ERR_ARG);
+        const orbfe_status s = apply_plan(pl, plan);
+        if (s != ORBFE_OK) return fail(s);
+    }
     for (int i = 0; i < npipes; ++i) {
-        hipStream_t st = nullptr;
         hipEvent_t e = nullptr;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { orbfe_set_error("pipeline stream creation failed"); return fail(ORBFE_ERR_HIP); }
-        pl->st.push_back(st);
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { orbfe_set_error("pipeline event creation failed"); return fail(ORBFE_ERR_HIP); }
         pl->ev_end.push_back(e);
-    }
-    for (int i = 0; i < std::min(npipes, ORBFE_PIPE_SIDE_STREAMS); ++i) {
-        hipStream_t st = nullptr;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { orbfe_set_error("pipeline stream creation failed"); return fail(ORBFE_ERR_HIP); }
-        pl->side.push_back(st);
+        pl->ev_end_valid.push_back(0);
     }
     for (int i = 0; i < npipes; ++i) {
         orbfe_handle *h = nullptr;
-        orbfe_status s = orbfe_internal_create_on_stream(&pl->prm, (void *)pl->st[(size_t)i], (void *)pl->side[(size_t)i % pl->side.size()], &h);
+        orbfe_status s = orbfe_internal_create_on_stream(&pl->prm, (void *)pl->stream_of(i), (void *)pl->side(), &h);
         if (s != ORBFE_OK) return fail(s);
         pl->ext.push_back(h);
         orbfe_matcher *m = nullptr;
-        s = orbfe_internal_matcher_create_on_stream(pl->device, (void *)pl->st[(size_t)i], &m);
+        s = orbfe_internal_matcher_create_on_stream(pl->device, (void *)pl->stream_of(i), &m);
         if (s != ORBFE_OK) return fail(s);
         pl->mat.push_back(m);
     }
@@ -221,6 +274,35 @@ extern "C" orbfe_status orbfe_pipeline_create(const orbfe_params *p, int32_t npi
     return ORBFE_OK;
 }
 
+extern "C" orbfe_status orbfe_pipeline_create(const orbfe_params *p, int32_t npipes, orbfe_pipeline **out)
+{
+    return orbfe_internal_pipeline_create_queues(p, npipes, orb_pipe_env_queues(), out);
+}
+
+// test hooks (not in include/orbfe.h; no device): the plan of `npipes` pipes on `queues` queues as 9 + ORBFE_PIPE_MAX_PIPES
+// int32 -- P, Q, copies, S, P_eff, side, first, side_index, nstreams, stream of every pipe -- and the queue count the
+// library makes of a GPU_MAX_HW_QUEUES text / of the environment
+extern "C" int32_t orbfe_internal_pipe_plan(int32_t npipes, int32_t queues, int32_t copies, int32_t *out)
+{
+    OrbPipePlan plan;
+    if (!out || !orb_pipe_plan(npipes, queues, copies != 0, &plan)) return ORBFE_ERR_ARG;
+    const int32_t head[9] = {plan.P, plan.Q, plan.copies, plan.S, plan.P_eff, plan.side, plan.first, plan.side_index, plan.nstreams};
+    for (int i = 0; i < 9; ++i) out[i] = head[i];
+    for (int i = 0; i < ORBFE_PIPE_MAX_PIPES; ++i) out[9 + i] = plan.stream_of_pipe[i];
+    return ORBFE_OK;
+}
+extern "C" int32_t orbfe_internal_pipe_parse_queues(const char *text) { return orb_pipe_parse_queues(text); }
+extern "C" int32_t orbfe_internal_pipe_env_queues(void) { return orb_pipe_env_queues(); }
+// the plan in force: kernel streams, pipes that take sub-batches, side stream or not
+extern "C" orbfe_status orbfe_internal_pipeline_streams(const orbfe_pipeline *pl, int32_t *streams, int32_t *eff_pipes, int32_t *side)
+{
+    if (!pl || !pl->cur_valid) return ORBFE_ERR_ARG;
+    if (streams) *streams = pl->cur.S;
+    if (eff_pipes) *eff_pipes = pl->cur.P_eff;
+    if (side) *side = pl->cur.side;
+    return ORBFE_OK;
+}
+
 extern "C" int32_t orbfe_pipeline_pipes(const orbfe_pipeline *pl) { return pl ? pl->P : 0; }
 extern "C" int32_t orbfe_pipeline_capacity(const orbfe_pipeline *pl) { return pl ? pl->cap : 0; }
 extern "C" int32_t orbfe_pipeline_sub_batch(const orbfe_pipeline *pl) { return pl ? pl->F : 0; }
@@ -236,7 +318,7 @@ extern "C" orbfe_matcher *orbfe_pipeline_matcher(orbfe_pipeline *pl, int32_t pip
 extern "C" orbfe_status orbfe_pipeline_set_host_pipes(orbfe_pipeline *pl, int32_t n)
 {
     if (!pl || n < 1) return ORBFE_ERR_ARG;
-    pl->host_pipes = std::min(n, pl->P);
+    pl->host_pipes = std::min(n, pl->P);   // (the host entry point plans its streams for this many pipes)
     return ORBFE_OK;
 }
 
@@ -251,7 +333,8 @@ extern "C" orbfe_status orbfe_pipeline_join(orbfe_pipeline *pl, void *stream)
 {
     if (!pl) return ORBFE_ERR_ARG;
     DeviceGuard g(pl->device);
-    for (int p = 0; p < pl->P; ++p) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, pl->ev_end[(size_t)p], 0));
+    for (int p = 0; p < pl->P; ++p)
+        if (pl->ev_end_valid[(size_t)p]) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, pl->ev_end[(size_t)p], 0));
     pl->joined = true;
     return ORBFE_OK;
 }
@@ -260,7 +343,7 @@ extern "C" orbfe_status orbfe_pipeline_synchronize(orbfe_pipeline *pl)
 {
     if (!pl) return ORBFE_ERR_ARG;
     DeviceGuard g(pl->device);
-    for (hipStream_t s : pl->st) ORBFE_HIP(hipStreamSynchronize(s));
+    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
     return ORBFE_OK;
 }
 
@@ -277,18 +360,12 @@ extern "C" orbfe_status orbfe_pipeline_get_overflow(orbfe_pipeline *pl, int32_t 
     return ORBFE_OK;
 }
 
-extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_t nframes, int32_t w,
-                                                            int32_t ht, int32_t stride, size_t frame_stride, orbfe_keypoint *d_kps,
-                                                            uint8_t *d_desc, int32_t cap, int32_t *d_n_out, int32_t *d_match,
-                                                            int32_t *d_nmatches, float nnratio, int32_t th, int32_t check_ori,
-                                                            int32_t flags, void *stream)
+// one call on the pipeline's current plan (apply_plan): the device entry point's, or the host entry point's with its copy streams
+static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t ht, int32_t stride,
+                               size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc, int32_t cap, int32_t *d_n_out, int32_t *d_match,
+                               int32_t *d_nmatches, float nnratio, int32_t th, int32_t check_ori, int32_t flags, void *stream)
 {
-    if (!pl || !d_gray || !d_kps || !d_desc || !d_n_out || nframes < 1 || cap < 1 || (d_match && !d_nmatches)) {
-        orbfe_set_error("bad argument to orbfe_pipeline_extract_match_device");
-        return ORBFE_ERR_ARG;
-    }
-    DeviceGuard g(pl->device);
-    const int F = pl->F, P = pl->P;
+    const int F = pl->F, P = pl->cur.P_eff;   // sub-batch j runs on pipe (rot + j) mod P_eff: every kernel stream gets its share
     const int nsub = (nframes + F - 1) / F;
     orbfe_status s = ensure_events(pl, nsub + 1);
     if (s != ORBFE_OK) return s;
@@ -302,11 +379,11 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
     // fork: the pipes start behind whatever the caller's stream holds (the producer of d_gray, the consumer of the output
     // blocks of an earlier call)
     ORBFE_HIP(hipEventRecord(pl->ev_fork, cs));
-    for (int p = 0; p < P; ++p) ORBFE_HIP(hipStreamWaitEvent(pl->st[(size_t)p], pl->ev_fork, 0));
+    for (int p = 0; p < P; ++p) ORBFE_HIP(hipStreamWaitEvent(pl->stream_of(p), pl->ev_fork, 0));
     // An error in the middle of the loop leaves launches of this call in flight and the event / carry bookkeeping half
     // updated: drain the pipes and start the sequence over (the next call has no predecessor frame), then report.
     auto bail = [&](orbfe_status e) {
-        for (hipStream_t x : pl->st) (void)hipStreamSynchronize(x);
+        for (hipStream_t x : pl->pool) (void)hipStreamSynchronize(x);
         pl->have_carry = false;
         pl->m0_valid[0] = pl->m0_valid[1] = false;
         pl->joined = true;
@@ -319,7 +396,7 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
 
     for (int j = 0; j < nsub; ++j) {
         const int p = (pl->rot + j) % P;
-        hipStream_t st = pl->st[(size_t)p];
+        hipStream_t st = pl->stream_of(p);
         const int lo = j * F, nf = std::min(F, nframes - lo);
         // The output blocks may be the ones of the previous call (a host that re-uses its buffers), and the pipes take turns: what
         // the PREVIOUS call did with slices j happened on other pipes' streams.  This sub-batch overwrites them only after that
@@ -397,7 +474,7 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
     // event.
     {
         const int jl = nsub - 1;
-        hipStream_t st = pl->st[(size_t)((pl->rot + jl) % P)];
+        hipStream_t st = pl->stream_of((pl->rot + jl) % P);
         const size_t last = (size_t)nframes - 1;
         if (pl->m0_valid[wr]) {
             ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_m0[wr], 0));
@@ -421,11 +498,33 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
         pl->carry_src[2] = d_n_out + last;
         pl->carry_src_bytes[2] = sizeof(int32_t);
     }
-    for (int p = 0; p < P; ++p) ORBFE_HIP(hipEventRecord(pl->ev_end[(size_t)p], pl->st[(size_t)p]));
+    for (int p = 0; p < P; ++p) {
+        ORBFE_HIP(hipEventRecord(pl->ev_end[(size_t)p], pl->stream_of(p)));
+        pl->ev_end_valid[(size_t)p] = 1;
+    }
     pl->joined = false;
     pl->rot = (pl->rot + nsub) % P;
     if (!(flags & ORBFE_PIPE_NO_JOIN)) return orbfe_pipeline_join(pl, stream);
     return ORBFE_OK;
+}
+
+extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_t nframes, int32_t w,
+                                                            int32_t ht, int32_t stride, size_t frame_stride, orbfe_keypoint *d_kps,
+                                                            uint8_t *d_desc, int32_t cap, int32_t *d_n_out, int32_t *d_match,
+                                                            int32_t *d_nmatches, float nnratio, int32_t th, int32_t check_ori,
+                                                            int32_t flags, void *stream)
+{
+    if (!pl || !d_gray || !d_kps || !d_desc || !d_n_out || nframes < 1 || cap < 1 || (d_match && !d_nmatches)) {
+        orbfe_set_error("bad argument to orbfe_pipeline_extract_match_device");
+        return ORBFE_ERR_ARG;
+    }
+    DeviceGuard g(pl->device);
+    OrbPipePlan plan;
+    if (!orb_pipe_plan(pl->P, pl->Q, false, &plan)) return ORBFE_ERR_ARG;
+    const orbfe_status s = apply_plan(pl, plan);
+    if (s != ORBFE_OK) return s;
+    return run_device(pl, d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out, d_match, d_nmatches, nnratio, th, check_ori,
+                      flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -436,11 +535,7 @@ static orbfe_status ensure_host_sets(orbfe_pipeline *pl, int w, int ht)
     const size_t need = (size_t)pl->F * w * ht;
     if (need <= pl->in_bytes && pl->out_frames == pl->F) return ORBFE_OK;
     // (measured and rejected: copy streams at the highest stream priority -- 159 k frames/s with 3 pipes, 41 k with 12)
-    if (!pl->s_in) ORBFE_HIP(hipStreamCreateWithFlags(&pl->s_in, hipStreamNonBlocking));
-    if (!pl->s_out) ORBFE_HIP(hipStreamCreateWithFlags(&pl->s_out, hipStreamNonBlocking));
-    ORBFE_HIP(hipStreamSynchronize(pl->s_in));
-    ORBFE_HIP(hipStreamSynchronize(pl->s_out));
-    for (hipStream_t st : pl->st) ORBFE_HIP(hipStreamSynchronize(st));
+    for (hipStream_t st : pl->pool) ORBFE_HIP(hipStreamSynchronize(st));
     const size_t F = (size_t)pl->F, cap = (size_t)pl->cap;
     for (int k = 0; k < orbfe_pipeline::NSETS; ++k) {
         if (pl->d_in[k]) ORBFE_HIP(hipFree(pl->d_in[k]));
@@ -474,7 +569,12 @@ extern "C" orbfe_status orbfe_pipeline_extract_match(orbfe_pipeline *pl, const u
         return ORBFE_ERR_CAP;
     }
     DeviceGuard g(pl->device);
-    orbfe_status s = ensure_host_sets(pl, w, ht);
+    // the same planner with the copy streams first: the chunks go to min(host_pipes, P) pipes, which is what the plan is asked for
+    OrbPipePlan plan;
+    if (!orb_pipe_plan(std::max(1, std::min(pl->host_pipes, pl->P)), pl->Q, true, &plan)) return ORBFE_ERR_ARG;
+    orbfe_status s = apply_plan(pl, plan);
+    if (s != ORBFE_OK) return s;
+    s = ensure_host_sets(pl, w, ht);
     if (s != ORBFE_OK) return s;
     const int F = pl->F, pc = pl->cap;
     const size_t fbytes = (size_t)w * ht;
@@ -485,48 +585,45 @@ extern "C" orbfe_status orbfe_pipeline_extract_match(orbfe_pipeline *pl, const u
         orbfe_pipeline *pl;
         ~Drain()
         {
-            if (pl->s_in) (void)hipStreamSynchronize(pl->s_in);
-            for (hipStream_t st : pl->st) (void)hipStreamSynchronize(st);
-            if (pl->s_out) (void)hipStreamSynchronize(pl->s_out);
+            for (hipStream_t st : pl->pool) (void)hipStreamSynchronize(st);
         }
     } drain{pl};
     for (int c = 0; c < nchunks; ++c) {
         const int k = c % orbfe_pipeline::NSETS, lo = c * F, nf = std::min(F, nframes - lo);
         // set k is free once the results of chunk c - NSETS have left it
-        if (c >= orbfe_pipeline::NSETS) ORBFE_HIP(hipStreamWaitEvent(pl->s_in, pl->ev_out[k], 0));
+        if (c >= orbfe_pipeline::NSETS) ORBFE_HIP(hipStreamWaitEvent(pl->s_in(), pl->ev_out[k], 0));
         bool contiguous = stride == w;
         for (int f = 1; f < nf && contiguous; ++f) contiguous = grays[lo + f] == grays[lo + f - 1] + fbytes;
         if (contiguous) {
-            ORBFE_HIP(hipMemcpyAsync(pl->d_in[k], grays[lo], fbytes * nf, hipMemcpyHostToDevice, pl->s_in));
+            ORBFE_HIP(hipMemcpyAsync(pl->d_in[k], grays[lo], fbytes * nf, hipMemcpyHostToDevice, pl->s_in()));
         } else {
             for (int f = 0; f < nf; ++f)
                 ORBFE_HIP(hipMemcpy2DAsync(pl->d_in[k] + fbytes * f, (size_t)w, grays[lo + f], (size_t)stride, (size_t)w, (size_t)ht,
-                                           hipMemcpyHostToDevice, pl->s_in));
+                                           hipMemcpyHostToDevice, pl->s_in()));
         }
         // the pipes start behind the copy (the call forks from s_in) and are not joined: the next chunk's copy and pipes follow at once
         const int fl = ((c > 0 || (flags & ORBFE_PIPE_CONTINUE)) ? ORBFE_PIPE_CONTINUE : 0) | ORBFE_PIPE_NO_JOIN;
-        pl->rot = c % std::max(1, std::min(pl->host_pipes, pl->P));   // the chunk is one sub-batch: this is its pipe
-        s = orbfe_pipeline_extract_match_device(pl, pl->d_in[k], nf, w, ht, w, fbytes, pl->d_okps[k], pl->d_odesc[k], pc, pl->d_on[k],
-                                                match ? pl->d_om[k] : nullptr, match ? pl->d_onm[k] : nullptr, nnratio, th, check_ori, fl,
-                                                (void *)pl->s_in);
+        pl->rot = c % pl->cur.P_eff;   // the chunk is one sub-batch: this is its pipe
+        s = run_device(pl, pl->d_in[k], nf, w, ht, w, fbytes, pl->d_okps[k], pl->d_odesc[k], pc, pl->d_on[k], match ? pl->d_om[k] : nullptr,
+                       match ? pl->d_onm[k] : nullptr, nnratio, th, check_ori, fl, (void *)pl->s_in());
         if (s != ORBFE_OK) return s;
-        s = orbfe_pipeline_join(pl, (void *)pl->s_out);   // everything submitted so far, i.e. this chunk and older ones
+        s = orbfe_pipeline_join(pl, (void *)pl->s_out());   // everything submitted so far, i.e. this chunk and older ones
         if (s != ORBFE_OK) return s;
         // padded blocks straight into the caller's arrays (row pitch cap >= pc)
-        ORBFE_HIP(hipMemcpyAsync(n_out + lo, pl->d_on[k], (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out));
+        ORBFE_HIP(hipMemcpyAsync(n_out + lo, pl->d_on[k], (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out()));
         auto rows_out = [&](void *dst, const void *src, size_t elem) -> hipError_t {   // nf rows of pc elements, host pitch cap
-            if (cap == pc) return hipMemcpyAsync(dst, src, (size_t)nf * pc * elem, hipMemcpyDeviceToHost, pl->s_out);   // one linear copy
-            return hipMemcpy2DAsync(dst, (size_t)cap * elem, src, (size_t)pc * elem, (size_t)pc * elem, (size_t)nf, hipMemcpyDeviceToHost, pl->s_out);
+            if (cap == pc) return hipMemcpyAsync(dst, src, (size_t)nf * pc * elem, hipMemcpyDeviceToHost, pl->s_out());   // one linear copy
+            return hipMemcpy2DAsync(dst, (size_t)cap * elem, src, (size_t)pc * elem, (size_t)pc * elem, (size_t)nf, hipMemcpyDeviceToHost, pl->s_out());
         };
         ORBFE_HIP(rows_out(kps + (size_t)lo * cap, pl->d_okps[k], sizeof(orbfe_keypoint)));
         ORBFE_HIP(rows_out(desc + (size_t)lo * cap * 32, pl->d_odesc[k], 32));
         if (match) {
             ORBFE_HIP(rows_out(match + (size_t)lo * cap, pl->d_om[k], sizeof(int32_t)));
-            ORBFE_HIP(hipMemcpyAsync(nmatches + lo, pl->d_onm[k], (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out));
+            ORBFE_HIP(hipMemcpyAsync(nmatches + lo, pl->d_onm[k], (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out()));
         }
-        ORBFE_HIP(hipEventRecord(pl->ev_out[k], pl->s_out));
+        ORBFE_HIP(hipEventRecord(pl->ev_out[k], pl->s_out()));
     }
-    ORBFE_HIP(hipStreamSynchronize(pl->s_out));
+    ORBFE_HIP(hipStreamSynchronize(pl->s_out()));
     int32_t ovf = 0;
     s = orbfe_pipeline_get_overflow(pl, &ovf);
     if (s != ORBFE_OK) return s;

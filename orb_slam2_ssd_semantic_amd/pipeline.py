@@ -15,12 +15,18 @@ class FramePipeline(Handle):
     CONTINUE, NO_JOIN = _ffi.PIPE_CONTINUE, _ffi.PIPE_NO_JOIN
 
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, *, max_width=640, max_height=480,
-                 sub_batch=1024, npipes=3, device=-1, blur_rounding=0, nnratio=0.9, th=100, check_ori=True):
+                 sub_batch=1024, npipes=3, device=-1, blur_rounding=0, nnratio=0.9, th=100, check_ori=True, _queues=None):
+        """_queues (tests): the hardware queues the pipeline fits its streams to, instead of what the process's environment says"""
         self._L = _ffi.lib()
         self._p = C.c_void_p()
         prm = OrbfeParams(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, max_width, max_height, sub_batch, device,
                           blur_rounding)
-        check(self._L.orbfe_pipeline_create(C.byref(prm), npipes, C.byref(self._p)), "orbfe_pipeline_create")
+        if _queues is None:
+            check(self._L.orbfe_pipeline_create(C.byref(prm), npipes, C.byref(self._p)), "orbfe_pipeline_create")
+        else:
+            f = self._L.orbfe_internal_pipeline_create_queues
+            f.argtypes = [C.POINTER(OrbfeParams), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+            check(f(C.byref(prm), npipes, int(_queues), C.byref(self._p)), "orbfe_internal_pipeline_create_queues")
         self.npipes, self.sub_batch, self.blur_rounding = npipes, sub_batch, blur_rounding
         self.cap = int(self._L.orbfe_pipeline_capacity(self._p))
         self.nnratio, self.th, self.check_ori = float(nnratio), int(th), bool(check_ori)
@@ -59,6 +65,14 @@ class FramePipeline(Handle):
 
     def set_host_pipes(self, n):
         check(self._L.orbfe_pipeline_set_host_pipes(self._p, int(n)), "orbfe_pipeline_set_host_pipes")
+
+    def streams(self):
+        """(kernel streams, pipes that take sub-batches, 1 if the blur has a side stream) of the plan in force"""
+        v = [C.c_int32(0) for _ in range(3)]
+        f = self._L.orbfe_internal_pipeline_streams
+        f.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
+        check(f(self._p, *[C.byref(x) for x in v]), "orbfe_internal_pipeline_streams")
+        return tuple(x.value for x in v)
 
     def join(self, stream=None):
         check(self._L.orbfe_pipeline_join(self._p, stream), "orbfe_pipeline_join")

@@ -1,6 +1,6 @@
 """GPU timeline of the bench command (GPU box): rocprofv3 --kernel-trace, then from the dispatch intervals
    - the share of the wall interval in which at least one kernel was running (idle gaps),
-   - the mean number of kernels in flight,
+   - the mean number of kernels in flight and the longest gaps with none,
    - per kernel: calls, sum of durations, share of the busy time.
 usage: python tools/timeline.py <tag> [bench args...]   -> gpurun_out/<tag>_timeline.json"""
 import csv
@@ -27,7 +27,7 @@ for row in csv.DictReader(open(f)):
     ev.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), row["Kernel_Name"].replace("void ", "").split("(")[0].split("<")[0]))
 ev.sort()
 # the timed region = the last steps*launches k_fast_map dispatches and everything between them
-fm = [e for e in ev if e[2] == "k_fast_map"]
+fm = [e for e in ev if e[2].startswith("k_fast_map")]   # dense or lane-compacting (k_fast_map_c): one launch per sub-batch
 nl = bench["config"]["frames_per_gpu_per_step"] // bench["config"]["frames_per_launch"] if bench else 24
 n_timed = (bench["steps"] if bench else 6) * nl
 n_warm = (bench["warmup"] if bench else 2) * nl
@@ -38,13 +38,26 @@ t1 = max(e[1] for e in sel)
 pts = sorted([(s, 1) for s, e, _ in sel] + [(e, -1) for s, e, _ in sel])
 busy = 0
 conc_time = {}
+gaps = []   # intervals with nothing in flight
 depth, last = 0, t0
 for t, dlt in pts:
     if depth > 0:
         busy += t - last
+    elif t > last:
+        gaps.append(t - last)
     conc_time[depth] = conc_time.get(depth, 0) + (t - last)
     depth += dlt
     last = t
+# FAST is the VALU-bound stage, the others are bound by HBM, LDS or latency: chains that march in phase show up as several FAST
+# launches in flight at once
+fpts = sorted([(s, 1) for s, e, k in sel if k.startswith("k_fast_map")] + [(e, -1) for s, e, k in sel if k.startswith("k_fast_map")])
+fast_time = {}
+depth, last = 0, t0
+for t, dlt in fpts:
+    fast_time[depth] = fast_time.get(depth, 0) + (t - last)
+    depth += dlt
+    last = t
+fast_time[0] = fast_time.get(0, 0) + (t1 - last)
 per = {}
 for s, e, k in sel:
     p = per.setdefault(k, [0, 0])
@@ -53,9 +66,11 @@ for s, e, k in sel:
 wall = t1 - t0
 res = {"wall_ms": wall / 1e6, "busy_frac": busy / wall, "mean_kernels_in_flight": sum(v[1] for v in per.values()) / wall,
        "time_share_by_kernels_in_flight": {str(k): round(v / wall, 4) for k, v in sorted(conc_time.items())},
+       "time_share_by_fast_launches_in_flight": {str(k): round(v / wall, 4) for k, v in sorted(fast_time.items())},
+       "idle_gaps": len(gaps), "longest_idle_gaps_us": [round(g / 1e3, 1) for g in sorted(gaps, reverse=True)[:5]],
        "per_kernel": {k: {"calls": v[0], "sum_ms": round(v[1] / 1e6, 3), "avg_us": round(v[1] / v[0] / 1e3, 1)} for k, v in sorted(per.items(), key=lambda x: -x[1][1])},
        "bench_value": bench["value"] if bench else None, "command": "python bench.py " + " ".join(args),
-       "env": {k: os.environ[k] for k in os.environ if k.startswith("ORBFE_")}}
+       "env": {k: os.environ[k] for k in os.environ if k.startswith("ORBFE_") or k == "GPU_MAX_HW_QUEUES"}}
 json.dump(res, open(os.path.join(OUT, tag + "_timeline.json"), "w"), indent=1)
 print(json.dumps(res, indent=1))
 shutil.rmtree(d, ignore_errors=True)
