@@ -13,10 +13,12 @@
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int grid_cell_of(float x, float y, float minx, float miny, float gwi, float ghi)
 {
-    const int px = (int)roundf(__fmul_rn(__fsub_rn(x, minx), gwi));  // :525 std::round(float)
-    const int py = (int)roundf(__fmul_rn(__fsub_rn(y, miny), ghi));
-    if (px < 0 || px >= ORBFE_GRID_COLS || py < 0 || py >= ORBFE_GRID_ROWS) return -1;
-    return px * ORBFE_GRID_ROWS + py;
+    const float rx = roundf(__fmul_rn(__fsub_rn(x, minx), gwi));  // :525 std::round(float)
+    const float ry = roundf(__fmul_rn(__fsub_rn(y, miny), ghi));
+    // the range is decided in float, as orbfe_assign_grid_host does: the reference converts first, and a NaN or a value that
+    // no int holds becomes INT_MIN on the CPU (out of the grid), while the device's conversion gives 0 for a NaN (cell 0)
+    if (!(rx >= 0.f && rx < (float)ORBFE_GRID_COLS && ry >= 0.f && ry < (float)ORBFE_GRID_ROWS)) return -1;
+    return (int)rx * ORBFE_GRID_ROWS + (int)ry;
 }
 
 // one workgroup: histogram over the 3072 cells (LDS), scan, placement, then each cell's short list is put into
