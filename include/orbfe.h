@@ -586,7 +586,10 @@ orbfe_status orbfe_search_by_bow_batch_device(orbfe_matcher *m, const orbfe_keyp
  * pipeline creates no more kernel streams than the process has hardware queues (GPU_MAX_HW_QUEUES, read once, default 4:
  * streams that share a queue cannot overlap and stall each other at every cross-stream wait): with queues >= npipes + 1 every
  * pipe has a stream and the pipes' blur a shared side stream, with fewer the side stream takes one queue and queues - 1 pipes
- * take work.  A call cuts its
+ * take work.  On exactly 3 kernel streams + side stream (the default 4 queues, more than 3 pipes) a device call of two or more
+ * sub-batches deals those four streams by STAGE instead -- pyramid | FAST | quadtree + descriptor + matcher | blur, min(npipes, 8)
+ * extractor handles as rotating buffer sets -- so that one FAST pass is in flight nearly all the time (DESIGN.md "Lanes");
+ * results, ordering guarantees and orbfe_pipeline_join / _synchronize are the same either way.  A call cuts its
  * nframes into sub-batches of p->max_batch frames (the last one may be shorter) and deals them round robin to those pipes,
  * so that the VALU-bound FAST pass of one sub-batch shares the chip with the HBM / LDS-bound stages of its neighbours
  * (one pipe 273 k, three pipes 302 k frames/s at 1024-frame sub-batches).  Frame k is matched against frame

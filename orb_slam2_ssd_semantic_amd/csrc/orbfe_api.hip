@@ -468,9 +468,12 @@ extern "C" orbfe_status orbfe_get_fast_stats(orbfe_handle *h, uint64_t out[3], i
 // ---------------------------------------------------------------------------------------------------
 // the batched device path (everything else funnels into this)
 // ---------------------------------------------------------------------------------------------------
+// `lane` (null: everything on `st`, the blur possibly on the handle's side stream): one stream per stage group --
+// {pyramid, FAST, quadtree + descriptor, blur} -- ordered by the handle's events; `st` is then the tail stream lane[2]
+// (orbfe_internal_extract_batch_lanes).
 static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframes, int w, int ht, int stride,
                               size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc, int cap,
-                              int32_t *d_n_out, hipStream_t st)
+                              int32_t *d_n_out, hipStream_t st, const hipStream_t *lane = nullptr)
 {
     if (w > h->prm.max_width || ht > h->prm.max_height) {
         orbfe_set_error("frame %dx%d larger than planned %dx%d", w, ht, h->prm.max_width, h->prm.max_height);
@@ -563,8 +566,10 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
     a.d_fstat = (h->fast_stats || auto_probe) ? (unsigned long long *)((char *)h->d_misc.p + 16) : nullptr;
     // every call of a handle uses the same scratch blocks (pyramid, blur, survivor lists, selections): a call on another
     // stream than its predecessor's waits, at stream level, for that predecessor to finish
-    if (h->last_stream_valid && h->last_stream != st) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_last, 0));
-    hipEvent_t *ev = h->profiling ? h->ev[h->prof_calls % ORBFE_PROF_RING] : nullptr;
+    hipStream_t first = lane ? lane[0] : st;   // the stream of the first launch, the pyramid's
+    if (h->last_stream_valid && h->last_stream != first) ORBFE_HIP(hipStreamWaitEvent(first, h->ev_last, 0));
+    // (a call in lanes is not profiled: the marks of one call would lie on four streams, between other sub-batches' kernels)
+    hipEvent_t *ev = (h->profiling && !lane) ? h->ev[h->prof_calls % ORBFE_PROF_RING] : nullptr;
     if (ev) ORBFE_HIP(hipEventRecord(ev[0], st));
     auto finish = [&]() -> orbfe_status {   // common tail: profiling bookkeeping, the "last call" state of the handle
         if (ev) {
@@ -580,6 +585,34 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
         h->last_nframes = nframes;
         return ORBFE_OK;
     };
+    if (lane) {
+        // pyramid -> FAST and pyramid -> blur (ev_fork), FAST -> quadtree (ev_fork2), blur -> descriptor (ev_join); ev_last behind
+        // the descriptor on the tail stream, so that the next call of this handle starts its pyramid behind everything of this one
+        if (h->pin.fuse_blur_pyr || h->fuse_fast_pyr) {
+            orbfe_set_error("the fused pyramid options have no stage streams");
+            return ORBFE_ERR_STATE;
+        }
+        hipStream_t sf = lane[1], sb = lane[3];
+        ORBFE_HIP(orbk_launch_pyramid(a, first));
+        ORBFE_HIP(hipEventRecord(h->ev_fork, first));
+        ORBFE_HIP(hipStreamWaitEvent(sf, h->ev_fork, 0));
+        if (sb != first) ORBFE_HIP(hipStreamWaitEvent(sb, h->ev_fork, 0));
+        ORBFE_HIP(orbk_launch_fast(a, sf));
+        if (auto_probe) {
+            ORBFE_HIP(hipMemcpyAsync(h->h_auto.p, (char *)h->d_misc.p + 16, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, sf));
+            ORBFE_HIP(hipMemsetAsync((char *)h->d_misc.p + 16, 0, 3 * sizeof(uint64_t), sf));
+            ORBFE_HIP(hipEventRecord(h->ev_auto, sf));
+            h->auto_pending = true;
+        }
+        ORBFE_HIP(hipEventRecord(h->ev_fork2, sf));
+        ORBFE_HIP(orbk_launch_blur(a, sb));
+        ORBFE_HIP(hipEventRecord(h->ev_join, sb));
+        ORBFE_HIP(hipStreamWaitEvent(st, h->ev_fork2, 0));
+        ORBFE_HIP(orbk_launch_octree(a, st));
+        if (sb != st) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+        ORBFE_HIP(orbk_launch_describe(a, st));
+        return finish();
+    }
     int ov = h->overlap >= 0 ? h->overlap : (nframes >= 128 ? 2 : 0);
     if (!h->side) ov = 0;   // a pipe of a pipeline that fits its streams to the hardware queues and has none left for the blur
 #ifdef ORBFE_DEVELOPER
@@ -676,6 +709,23 @@ extern "C" orbfe_status orbfe_extract_batch_device(orbfe_handle *h, const uint8_
     DeviceGuard g(h->device);
     return run_batch(h, d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out,
                      (hipStream_t)stream);
+}
+
+// orbfe_extract_batch_device with a stream per stage group, for the pipeline's lanes (orbfe_pipe_plan.h): lane[0] pyramid,
+// lane[1] FAST, lane[2] quadtree + descriptor, lane[3] blur (may be lane[0] or lane[2]).  The call has finished when lane[2] has.
+orbfe_status orbfe_internal_extract_batch_lanes(orbfe_handle *h, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t ht,
+                                                int32_t stride, size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc,
+                                                int32_t cap, int32_t *d_n_out, void *const lane[4])
+{
+    if (!h || !d_gray || !d_kps || !d_desc || !d_n_out || nframes < 1 || w < 1 || ht < 1 || stride < w || cap < 1 ||
+        frame_stride < (size_t)stride * (size_t)(ht - 1) + (size_t)w || !lane || lane[0] == lane[1] || lane[1] == lane[2] ||
+        lane[0] == lane[2] || lane[3] == lane[1]) {
+        orbfe_set_error("bad argument to orbfe_internal_extract_batch_lanes");
+        return ORBFE_ERR_ARG;
+    }
+    DeviceGuard g(h->device);
+    const hipStream_t ls[4] = {(hipStream_t)lane[0], (hipStream_t)lane[1], (hipStream_t)lane[2], (hipStream_t)lane[3]};
+    return run_batch(h, d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out, ls[2], ls);
 }
 
 // host buffers, in chunks of max_batch frames.  A single chunk (the online case: one frame) is a plain H2D -> kernels ->

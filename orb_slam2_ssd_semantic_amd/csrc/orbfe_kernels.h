@@ -107,3 +107,8 @@ int32_t orbfe_internal_order_after_last_call(orbfe_handle *h, void *stream);
 // runs in the stream of the call); orbfe_internal_set_side_stream changes `side` between two calls
 orbfe_status orbfe_internal_create_on_stream(const orbfe_params *p, void *st, void *side, orbfe_handle **out);
 orbfe_status orbfe_internal_set_side_stream(orbfe_handle *h, void *side);
+// orbfe_extract_batch_device of a pipe's handle with a stream per stage group (the pipeline's lanes, orbfe_pipe_plan.h):
+// lane[0] pyramid, lane[1] FAST, lane[2] quadtree + descriptor, lane[3] blur (lane[0], lane[2] or a fourth stream)
+orbfe_status orbfe_internal_extract_batch_lanes(orbfe_handle *h, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t ht,
+                                                int32_t stride, size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc,
+                                                int32_t cap, int32_t *d_n_out, void *const lane[4]);

@@ -77,3 +77,33 @@ static inline bool orb_pipe_plan(int32_t P, int32_t Q, bool copies, OrbPipePlan 
     *out = pl;
     return true;
 }
+
+// Lanes: the other way to cut a device-entry call over the same four streams.  A chain (above) runs a whole sub-batch on one
+// kernel stream; with 3 chains the VALU-bound FAST pass of some sub-batch is in flight only 59 % of the time and two of them
+// compete for the same issue slots a third of it (profiles/pipe_queues.md).  In lanes the streams are dealt by STAGE: one kernel
+// stream carries nothing but FAST, back to back, and the other three feed it the pyramid, the blur and the quadtree / descriptor /
+// matcher of neighbouring sub-batches; `sets` extractor handles serve as rotating buffer sets, sub-batch j on set
+// (rot + j) mod sets.  profiles/pipe_lanes.md has the measurements.
+#define ORBFE_PIPE_LANE_SETS 8         // buffer sets of a lane call (at most P): 3, 4, 6, 8 measured, each a little faster than the last
+#define ORBFE_PIPE_LANE_PLACE 1        // 1: blur on the side stream, matcher behind the descriptor (where chains have both); 0: blur
+                                       // behind the pyramid on kernel stream 0, matcher on the side stream (a tie at 4 sets)
+#define ORBFE_PIPE_LANES_AUTO 1        // what a pipeline left to itself does where the rule allows lanes: 1 lanes, 0 chains
+#define ORBFE_PIPE_LANE_STREAMS 3      // the kernel streams lanes are defined for; with the side stream: four stage streams
+
+struct OrbPipeLanes {
+    int32_t lanes;   // 1: the call runs in lanes; 0: in chains, as orb_pipe_plan lays them out
+    int32_t sets;    // lanes: extractor handles in rotation; chains: the plan's P_eff
+};
+
+// Whether a call of `nsub` sub-batches on `plan` can run in lanes: the plan has no copy streams (the device entry point), is
+// short of queues (S < P: with P + 1 streams every sub-batch has a queue of its own and chains are the faster cut), has exactly
+// the 3 kernel streams + side stream that the stages are dealt to, and the call has at least two sub-batches (one sub-batch
+// has no neighbour to overlap with).  `want_sets` < 1: ORBFE_PIPE_LANE_SETS.
+static inline OrbPipeLanes orb_pipe_lanes(const OrbPipePlan &plan, int32_t nsub, int32_t want_sets = 0)
+{
+    OrbPipeLanes r;
+    r.lanes = (plan.copies == 0 && plan.S < plan.P && plan.S == ORBFE_PIPE_LANE_STREAMS && plan.side == 1 && nsub >= 2) ? 1 : 0;
+    const int32_t n = want_sets < 1 ? ORBFE_PIPE_LANE_SETS : want_sets;
+    r.sets = r.lanes ? (plan.P < n ? plan.P : n) : plan.P_eff;
+    return r;
+}

@@ -6,7 +6,9 @@
 // pipe = one extractor handle + one matcher handle + one stream, so that the VALU-bound FAST pass of one sub-batch shares the
 // chip with the HBM / LDS-bound stages of its neighbours -- and frame k is matched against frame k - 1 ACROSS sub-batch
 // boundaries and across calls (the last frame of a call is carried over), i.e. a real sequence.  How many streams there are, and
-// with them P_eff, follows from the hardware queues of the process (orbfe_pipe_plan.h).
+// with them P_eff, follows from the hardware queues of the process (orbfe_pipe_plan.h).  The same header has the second way to
+// cut a call over the streams, by stage instead of by sub-batch (lanes), which run_device takes where its rule and the
+// pipeline's lane mode say so.
 //
 // Host code only: every kernel is launched through the extractor / matcher entry points of this library.
 #include <mutex>
@@ -85,6 +87,13 @@ struct orbfe_pipeline {
     bool joined = true;
     int rot = 0;                // pipe of sub-batch 0 of the next call: consecutive short calls take turns on the pipes
     int host_pipes = 1;         // pipes the host entry point deals its chunks to (orbfe_pipeline_set_host_pipes)
+    // lanes (orbfe_pipe_plan.h): -1 automatic, 0 never, 1 wherever the rule allows them (orbfe_internal_pipeline_set_lanes)
+    int lane_mode = -1;
+    int lane_sets = 0;          // buffer sets of a lane call; 0: ORBFE_PIPE_LANE_SETS
+    int lane_place = -1;        // 0: blur behind the pyramid on kernel stream 0, matcher on the side stream; 1: blur on the side
+                                // stream, matcher behind the descriptor on kernel stream 2 (where chains have both); -1: ORBFE_PIPE_LANE_PLACE
+    int lane_rot = 0;           // buffer set of sub-batch 0 of the next lane call
+    hipStream_t kernel_stream(int i) const { return pool[(size_t)(cur.first + i)]; }
     // host entry point (orbfe_pipeline_extract_match): device input / output sets, copy streams
     static const int NSETS = 3;
     uint8_t *d_in[NSETS] = {nullptr, nullptr, nullptr};
@@ -303,6 +312,40 @@ extern "C" orbfe_status orbfe_internal_pipeline_streams(const orbfe_pipeline *pl
     return ORBFE_OK;
 }
 
+// the lane rule (orb_pipe_lanes) for a call of `nsub` sub-batches on the plan of (npipes, queues, copies): out = {lanes, sets}
+extern "C" int32_t orbfe_internal_pipe_lanes(int32_t npipes, int32_t queues, int32_t copies, int32_t nsub, int32_t *out)
+{
+    OrbPipePlan plan;
+    if (!out || !orb_pipe_plan(npipes, queues, copies != 0, &plan)) return ORBFE_ERR_ARG;
+    const OrbPipeLanes r = orb_pipe_lanes(plan, nsub);
+    out[0] = r.lanes;
+    out[1] = r.sets;
+    return ORBFE_OK;
+}
+// -1: lanes where the library chooses them, 0: never, 1: wherever the rule allows them; "on" is an error for a pipeline whose
+// device plan lacks the 3 kernel streams + side stream short of its pipes
+extern "C" orbfe_status orbfe_internal_pipeline_set_lanes(orbfe_pipeline *pl, int32_t mode)
+{
+    OrbPipePlan plan;
+    if (!pl || mode < -1 || mode > 1 || !orb_pipe_plan(pl->P, pl->Q, false, &plan)) return ORBFE_ERR_ARG;
+    if (mode == 1 && !orb_pipe_lanes(plan, 2).lanes) {
+        orbfe_set_error("lanes need 3 kernel streams and the side stream for more than 3 pipes: %d pipes on %d queues have %d + %d", pl->P, pl->Q,
+                        plan.S, plan.side);
+        return ORBFE_ERR_ARG;
+    }
+    pl->lane_mode = mode;
+    return ORBFE_OK;
+}
+// the A/B knobs of a lane call: buffer sets (0: ORBFE_PIPE_LANE_SETS; at most the pipes) and the placement of blur and matcher
+// (0: blur on kernel stream 0, matcher on the side stream; 1: blur on the side stream, matcher on kernel stream 2; -1: ORBFE_PIPE_LANE_PLACE)
+extern "C" orbfe_status orbfe_internal_pipeline_set_lane_options(orbfe_pipeline *pl, int32_t sets, int32_t place)
+{
+    if (!pl || sets < 0 || sets > ORBFE_PIPE_MAX_PIPES || place < -1 || place > 1) return ORBFE_ERR_ARG;
+    pl->lane_sets = sets;
+    pl->lane_place = place;
+    return ORBFE_OK;
+}
+
 extern "C" int32_t orbfe_pipeline_pipes(const orbfe_pipeline *pl) { return pl ? pl->P : 0; }
 extern "C" int32_t orbfe_pipeline_capacity(const orbfe_pipeline *pl) { return pl ? pl->cap : 0; }
 extern "C" int32_t orbfe_pipeline_sub_batch(const orbfe_pipeline *pl) { return pl ? pl->F : 0; }
@@ -365,8 +408,27 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
                                size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc, int32_t cap, int32_t *d_n_out, int32_t *d_match,
                                int32_t *d_nmatches, float nnratio, int32_t th, int32_t check_ori, int32_t flags, void *stream)
 {
-    const int F = pl->F, P = pl->cur.P_eff;   // sub-batch j runs on pipe (rot + j) mod P_eff: every kernel stream gets its share
+    const int F = pl->F;
     const int nsub = (nframes + F - 1) / F;
+    // Chains: sub-batch j runs on pipe (rot + j) mod P_eff, every kernel stream gets its share.  Lanes: the streams carry one stage
+    // group each and sub-batch j takes buffer set (handle) (lane_rot + j) mod sets.
+    const OrbPipeLanes lr = orb_pipe_lanes(pl->cur, nsub, pl->lane_sets);
+    const bool lanes = lr.lanes && (pl->lane_mode < 0 ? ORBFE_PIPE_LANES_AUTO != 0 : pl->lane_mode != 0);
+    const int P = lanes ? lr.sets : pl->cur.P_eff;
+    const int rot0 = lanes ? pl->lane_rot % P : pl->rot;
+    // the streams of a lane call: pyramid, FAST, quadtree + descriptor, blur; and the matcher's
+    void *lane[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t lane_match = nullptr;
+    if (lanes) {
+        const int place = pl->lane_place < 0 ? ORBFE_PIPE_LANE_PLACE : pl->lane_place;
+        lane[0] = (void *)pl->kernel_stream(0);
+        lane[1] = (void *)pl->kernel_stream(1);
+        lane[2] = (void *)pl->kernel_stream(2);
+        lane[3] = place ? (void *)pl->side() : lane[0];
+        lane_match = place ? pl->kernel_stream(2) : pl->side();
+    }
+    const int nend = lanes ? ORBFE_PIPE_LANE_STREAMS + 1 : P;   // streams that carry work of this call, the side stream last
+    auto end_stream = [&](int i) { return !lanes ? pl->stream_of(i) : (i < ORBFE_PIPE_LANE_STREAMS ? pl->kernel_stream(i) : pl->side()); };
     orbfe_status s = ensure_events(pl, nsub + 1);
     if (s != ORBFE_OK) return s;
     s = ensure_seq(pl, nframes);
@@ -379,7 +441,7 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
     // fork: the pipes start behind whatever the caller's stream holds (the producer of d_gray, the consumer of the output
     // blocks of an earlier call)
     ORBFE_HIP(hipEventRecord(pl->ev_fork, cs));
-    for (int p = 0; p < P; ++p) ORBFE_HIP(hipStreamWaitEvent(pl->stream_of(p), pl->ev_fork, 0));
+    for (int i = 0; i < nend; ++i) ORBFE_HIP(hipStreamWaitEvent(end_stream(i), pl->ev_fork, 0));
     // An error in the middle of the loop leaves launches of this call in flight and the event / carry bookkeeping half
     // updated: drain the pipes and start the sequence over (the next call has no predecessor frame), then report.
     auto bail = [&](orbfe_status e) {
@@ -395,8 +457,10 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
     };
 
     for (int j = 0; j < nsub; ++j) {
-        const int p = (pl->rot + j) % P;
-        hipStream_t st = pl->stream_of(p);
+        const int p = (rot0 + j) % P;
+        // st: where the extraction starts (what orders it is waited for there), sx: where it ends, sm: the matcher's stream
+        hipStream_t st = lanes ? (hipStream_t)lane[0] : pl->stream_of(p);
+        hipStream_t sx = lanes ? (hipStream_t)lane[2] : st, sm = lanes ? lane_match : st;
         const int lo = j * F, nf = std::min(F, nframes - lo);
         // The output blocks may be the ones of the previous call (a host that re-uses its buffers), and the pipes take turns: what
         // the PREVIOUS call did with slices j happened on other pipes' streams.  This sub-batch overwrites them only after that
@@ -428,10 +492,14 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
              overlaps(pl->carry_src[1], pl->carry_src_bytes[1], d_desc + (size_t)lo * cap * 32, (size_t)nf * cap * 32) ||
              overlaps(pl->carry_src[2], pl->carry_src_bytes[2], d_n_out + lo, (size_t)nf * sizeof(int32_t))))
             ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_carry[rd], 0));
-        s = orbfe_extract_batch_device(pl->ext[(size_t)p], d_gray + (size_t)lo * frame_stride, nf, w, ht, stride, frame_stride,
-                                       d_kps + (size_t)lo * cap, d_desc + (size_t)lo * cap * 32, cap, d_n_out + lo, (void *)st);
+        if (lanes)
+            s = orbfe_internal_extract_batch_lanes(pl->ext[(size_t)p], d_gray + (size_t)lo * frame_stride, nf, w, ht, stride, frame_stride,
+                                                   d_kps + (size_t)lo * cap, d_desc + (size_t)lo * cap * 32, cap, d_n_out + lo, lane);
+        else
+            s = orbfe_extract_batch_device(pl->ext[(size_t)p], d_gray + (size_t)lo * frame_stride, nf, w, ht, stride, frame_stride,
+                                           d_kps + (size_t)lo * cap, d_desc + (size_t)lo * cap * 32, cap, d_n_out + lo, (void *)st);
         if (s != ORBFE_OK) return bail(s);
-        ORBFE_HIP(hipEventRecord(pl->ev_ext[(size_t)j], st));
+        ORBFE_HIP(hipEventRecord(pl->ev_ext[(size_t)j], sx));
         pl->ev_ext_valid[(size_t)j] = 1;
         {
             orbfe_pipeline::Slice &sj = pl->ev_slice[(size_t)j];
@@ -440,30 +508,33 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
             sj.n = (const char *)(d_n_out + lo); sj.nb = (size_t)nf * sizeof(int32_t);
         }
         if (!match) continue;
-        if (j > 0) ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_ext[(size_t)j - 1], 0));   // frame lo - 1 comes from the neighbour pipe
+        // (lanes: the matcher's writes into the match rows follow the previous call's through this sub-batch's extraction, which
+        // waited for them above)
+        if (sm != sx) ORBFE_HIP(hipStreamWaitEvent(sm, pl->ev_ext[(size_t)j], 0));
+        if (j > 0) ORBFE_HIP(hipStreamWaitEvent(sm, pl->ev_ext[(size_t)j - 1], 0));   // frame lo - 1 comes from the neighbour pipe
         const int q0 = lo == 0 ? 1 : lo;
         const int np = lo + nf - q0;
         if (np > 0) {
             s = orbfe_match_bf_blocks_device(pl->mat[(size_t)p], d_kps, d_desc, d_n_out, d_kps, d_desc, d_n_out, cap, pl->d_seq + q0 + 1,
                                              pl->d_seq + q0, np, nnratio, th, check_ori, d_match + (size_t)q0 * cap, d_nmatches + q0,
-                                             (void *)st);
+                                             (void *)sm);
             if (s != ORBFE_OK) return bail(s);
         }
         if (lo == 0) {
             if (cont) {
-                ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_carry[rd], 0));
+                ORBFE_HIP(hipStreamWaitEvent(sm, pl->ev_carry[rd], 0));
                 // query = frame 0 of this call, train = the carried frame (frame 0 of the carry block)
                 s = orbfe_match_bf_blocks_device(pl->mat[(size_t)p], d_kps, d_desc, d_n_out, pl->d_ckps[rd], pl->d_cdesc[rd], pl->d_cn[rd], cap,
-                                                 pl->d_seq + 1, pl->d_seq + 1, 1, nnratio, th, check_ori, d_match, d_nmatches, (void *)st);
+                                                 pl->d_seq + 1, pl->d_seq + 1, 1, nnratio, th, check_ori, d_match, d_nmatches, (void *)sm);
                 if (s != ORBFE_OK) return bail(s);
-                ORBFE_HIP(hipEventRecord(pl->ev_m0[rd], st));   // slot rd has been read: the NEXT call may write it
+                ORBFE_HIP(hipEventRecord(pl->ev_m0[rd], sm));   // slot rd has been read: the NEXT call may write it
                 pl->m0_valid[rd] = true;
             } else {  // the first frame of a sequence has no predecessor
-                ORBFE_HIP(hipMemsetAsync(d_match, 0xFF, (size_t)cap * sizeof(int32_t), st));
-                ORBFE_HIP(hipMemsetAsync(d_nmatches, 0, sizeof(int32_t), st));
+                ORBFE_HIP(hipMemsetAsync(d_match, 0xFF, (size_t)cap * sizeof(int32_t), sm));
+                ORBFE_HIP(hipMemsetAsync(d_nmatches, 0, sizeof(int32_t), sm));
             }
         }
-        ORBFE_HIP(hipEventRecord(pl->ev_match[(size_t)j], st));
+        ORBFE_HIP(hipEventRecord(pl->ev_match[(size_t)j], sm));
         pl->ev_match_valid[(size_t)j] = 1;
     }
     // (the events of sub-batch indices this call did not use keep their last record: a later, longer call still orders itself
@@ -474,7 +545,9 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
     // event.
     {
         const int jl = nsub - 1;
-        hipStream_t st = pl->stream_of((pl->rot + jl) % P);
+        // (lanes: on the matcher's stream, behind the last sub-batch's extraction on the tail stream)
+        hipStream_t st = lanes ? lane_match : pl->stream_of((rot0 + jl) % P);
+        if (lanes && st != (hipStream_t)lane[2]) ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_ext[(size_t)jl], 0));
         const size_t last = (size_t)nframes - 1;
         if (pl->m0_valid[wr]) {
             ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_m0[wr], 0));
@@ -498,12 +571,14 @@ static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_
         pl->carry_src[2] = d_n_out + last;
         pl->carry_src_bytes[2] = sizeof(int32_t);
     }
-    for (int p = 0; p < P; ++p) {
-        ORBFE_HIP(hipEventRecord(pl->ev_end[(size_t)p], pl->stream_of(p)));
-        pl->ev_end_valid[(size_t)p] = 1;
+    // every stream that carried work of this call (lanes: the side stream too; the rule has P > 3, so there is a fourth event)
+    for (int i = 0; i < nend; ++i) {
+        ORBFE_HIP(hipEventRecord(pl->ev_end[(size_t)i], end_stream(i)));
+        pl->ev_end_valid[(size_t)i] = 1;
     }
     pl->joined = false;
-    pl->rot = (pl->rot + nsub) % P;
+    if (lanes) pl->lane_rot = (rot0 + nsub) % P;
+    else pl->rot = (pl->rot + nsub) % P;
     if (!(flags & ORBFE_PIPE_NO_JOIN)) return orbfe_pipeline_join(pl, stream);
     return ORBFE_OK;
 }
