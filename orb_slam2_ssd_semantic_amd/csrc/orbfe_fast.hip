@@ -140,6 +140,17 @@ __device__ __forceinline__ uint32_t fast_compass_pair(const uint32_t (&rm3)[FM_N
     return fast_compass_from(rp3[3 + J], rm3[3 + J], r0[6 + J], r0[0 + J], r0[3 + J], t);
 }
 
+// Rows the dense walk (orbfe_fast_body.inc) keeps in flight: the raw row of step s + FM_PF is fetched in step s.  The FM_PF + 1
+// live 12-byte buffers sit in a ring of FM_RAW slots, the next power of two, so that the slot of a step is a compile-time
+// constant under the 8-fold unroll at every depth (a slot that is never live costs no register).
+// Depth 4 measured best beside the other stages' kernels (profiles/r07_ab_fast_prefetch.json); each row in flight costs three
+// registers, and k_fast_map<1> stands at 167 of the 168 that three waves per SIMD allow.
+#ifndef FM_PF
+#define FM_PF 4
+#endif
+static_assert(FM_PF >= 1 && FM_PF <= 4, "FM_PF: 1 .. 4 rows in flight");
+#define FM_RAW (FM_PF < 2 ? 2 : FM_PF < 4 ? 4 : 8)
+
 #define FM_BUF 384       // per-wave LDS staging of survivors before one atomic reserves their run in the level's list
 #define FM_ROW_MAX 140   // a row adds at most 2 per lane + 1 per lane that straddles a cell seam (<= 9 of them)
 
@@ -279,7 +290,7 @@ __global__ __launch_bounds__(256) FC_OCC void k_fast_map_c(const OrbPlan *__rest
 
 #ifdef ORBFE_DEVELOPER   // measured slower than the default chain; compiled only into developer builds
 // FAST on level l and cv::resize l -> l + 1 in ONE launch, the launches chained over the levels ("pyramid inside
-// the FAST pass").  FAST's live set leaves no register for a second job in its lanes (157 of the 168 that three waves per SIMD
+// the FAST pass").  FAST's live set leaves no register for a second job in its lanes (165 of the 168 that three waves per SIMD
 // allow), so the fusion is by WORKGROUP ROLE: `npyr` of the launch's workgroups per frame are resize workgroups
 // (k_pyr_walk's walk, unchanged), the others FAST workgroups over the wave range [wave_lo, wave_lo + nwaves) of the lane list.
 // Both read level l, FAST is VALU-bound and the walk HBM-bound, and the two kinds are dealt out proportionally over the block

@@ -15,6 +15,11 @@
 //     neighbours valid), the row part of the candidate order key `ord` and of the key's y coordinate, the loop bounds; every row
 //     of the run is a detectable row, so the threshold needs no per-row validity select.
 // Per row step that is ~20 vector instructions fewer of ~214, and 2 arc evaluations fewer per run.
+//
+// The row walk, both forms: blocks of eight steps under an 8-fold unroll (ring slots are compile-time constants), FM_PF raw rows
+// in flight (orbfe_fast.hip; the row of step s + FM_PF is fetched in step s), no exit inside a block -- the steps a run lacks to
+// a multiple of eight are padding steps in front of step 0 (below, at the loop).  tests/test_gpu_fast_prefetch.py walks every
+// `nsteps mod 8` of both forms.
 // Only the places that differ branch on CELLROWS; FM_LDS_CONSTS (orbfe_fast_colmask.inc) is an A/B path of the generic form.
     uint32_t *lflag = s_cf + wv * cf_words;
     for (int i = lane; i < cf_words; i += 64) lflag[i] = 0u;  // wave-private: its own DS operations execute in order
@@ -78,9 +83,9 @@
     // is ys - 8 + s, cell rows ys - 7 + s
     const uint32_t key00 = (uint32_t)(x - ORBFE_MINB) + ((uint32_t)(ys - (CELLROWS ? 7 : 8) - ORBFE_MINB) << 12);
 
-    // 8-slot ring of unpacked rows (7 live), statically indexed under the 8-fold unroll; the raw row of the next step is
-    // fetched one step ahead into one of two 12-byte buffers
-    uint32_t R[8][FM_NE], Raw[2][3];
+    // 8-slot ring of unpacked rows (7 live), statically indexed under the 8-fold unroll; the raw row of step s + FM_PF is
+    // fetched in step s: FM_PF rows in flight, FM_PF + 1 live 12-byte buffers in a ring of FM_RAW slots
+    uint32_t R[8][FM_NE], Raw[FM_RAW][3];
     uint32_t S01[8], S23[8];  // S of the pixel pairs (0,1), (2,3) for the strength row computed in ring slot k
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -107,18 +112,29 @@
             dst3[2] = *(const uint32_t *)(row + 4);
         }
     };
-    fetch(0, Raw[0]);
+    // The walk is whole blocks of eight steps and no step of a block leaves the loop: the waitcnt pass merges conservatively where
+    // control flow joins, and with a per-step exit (`if (s >= nsteps) break`) the wait in front of the unpack came out as
+    // vmcnt(1) in steady state whatever the ring depth -- one row in flight.  So the steps a run lacks to a multiple of eight
+    // come FIRST, as padding steps s = -pad .. -1: a padding step issues its fetch like any other step (the step is clamped on the
+    // scalar side, so it asks for row 0 again) and does nothing else -- every path through a block has issued the same number of
+    // loads, and the wait of every step is vmcnt(FM_PF).  The slot k of step s is (s + pad) % 8; only ring positions depend on it.
+    // No fetch asks for a row past step nsteps (row ys + nrows + 4, what the one-row-ahead walk read last): the resource has no
+    // bound of its own.
+    const int pad = (8 - (nsteps & 7)) & 7;
+    auto fetch_step = [&](int s, uint32_t (&dst3)[3]) { fetch(min(max(s, 0), nsteps), dst3); };   // rows of steps 0 .. nsteps, as before
+#pragma unroll
+    for (int i = 0; i < FM_PF; ++i) fetch_step(i - pad, Raw[i]);
 
-    for (int s0 = 0; s0 < nsteps; s0 += 8) {
+    for (int s0 = -pad; s0 < nsteps; s0 += 8) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int s = s0 + k;
-            if (s >= nsteps) break;    // wave-uniform
+            const int s = s0 + k;   // wave-uniform
             const bool have_row = !CELLROWS || s < nrows + 6;   // cell rows, scalar: the last step only suppresses
-            // (fetch and unpack are unconditional -- a conditional load is waited for where the branches join, i.e. at once; the rows
-            // past the run that the last two steps read, ys + nrows + 3 and + 4, still lie inside the level: iy1 + 4 <= h - 15)
-            fetch(s + 1, Raw[(k + 1) % 2]);
-            fast_unpack_row(Raw[k % 2], R[k]);
+            // (the fetch is unconditional -- a conditional load is waited for where the branches join, i.e. at once; the rows past
+            // the run that the last steps ask for, ys + nrows + 3 and + 4, still lie inside the level: iy1 + 4 <= h - 15)
+            fetch_step(s + FM_PF, Raw[(k + FM_PF) % FM_RAW]);
+            if (s < 0) continue;       // a padding step: nothing waits for its fetch
+            fast_unpack_row(Raw[k % FM_RAW], R[k]);
             if (s < 6) continue;
             // ---- strength row rc = r - 3 (newest ring slot k is row rc+3, slot (k+2)%8 is row rc-3) ----
             if (have_row) {
