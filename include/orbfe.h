@@ -520,7 +520,12 @@ orbfe_status orbfe_stereo_matches_batch_device(orbfe_matcher *m, orbfe_handle *l
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:553, src/KeyFrame.cc:82; levelsup = 4).  DBoW2 is not vendored
  * by the reference; the algorithm is restated from the published one.  The tree is handed over as arrays:
  * children of node i = child_idx[child_off[i] .. child_off[i+1]) in stored order (node 0 = root; child ids must exceed
- * their parent's id), node_desc[nnodes*32], word_id / weight (TF-IDF) meaningful for leaves, L = tree depth. */
+ * their parent's id), node_desc[nnodes*32], word_id / weight (TF-IDF) meaningful for leaves, L = tree depth.
+ * A leaf's word_id must be below 2^31 (f_word is int32, -1 = no word): ORBFE_ERR_ARG otherwise.
+ * A root without children (child_off[1] == child_off[0]; a vocabulary file that holds the header only) is DBoW2's empty()
+ * vocabulary: it is accepted, and every transform through it gives "no word" for every feature -- f_word = f_node = -1,
+ * f_weight = 0, empty BowVector and FeatureVector (counts 0 / 0 / 0, fv_off[0] = 0) -- in orbfe_bow_transform and in
+ * orbfe_bow_transform_batch_device alike; child_idx may then be NULL and is never read. */
 typedef struct orbfe_vocabulary orbfe_vocabulary;
 orbfe_status orbfe_vocabulary_create(int32_t device, int32_t nnodes, const uint32_t *child_off, const uint32_t *child_idx,
                                      const uint8_t *node_desc, const uint32_t *word_id, const double *weight, int32_t L,
@@ -773,6 +778,7 @@ orbfe_status orbfe_vocfile_arrays(const orbfe_vocfile *v, const uint32_t **child
                                   const uint8_t **node_desc, const uint32_t **word_id, const double **weight,
                                   const uint32_t **parent, const uint8_t **is_leaf);
 orbfe_status orbfe_vocfile_save_binary(const orbfe_vocfile *v, const char *path);
+/* orbfe_vocabulary_create on the parsed tree; a file that holds the header only gives the empty vocabulary described there */
 orbfe_status orbfe_vocabulary_create_from_file(int32_t device, const orbfe_vocfile *v, orbfe_vocabulary **out);
 
 /* ---- the fork's optical-flow dynamic-point mask (csrc/orbfe_flow.hip, DESIGN.md "Optical-flow mask") ----------------------

@@ -236,6 +236,12 @@ __global__ __launch_bounds__(256) void k_bow_descend(const uint32_t *__restrict_
     uint32_t fin = 0, nid = 0;
     int level = 0;
     uint32_t c0 = child_off[0], c1 = child_off[1];
+    if (c1 == c0) {  // a root without children is DBoW2's empty() vocabulary: no feature has a word, child_idx has no entry
+        f_word[i] = -1;
+        f_node[i] = -1;
+        f_weight[i] = 0.0;
+        return;
+    }
     do {  // child ids are larger than their parent's (checked at creation): the walk ends
         ++level;
         fin = child_idx[c0];
@@ -392,6 +398,10 @@ extern "C" orbfe_status orbfe_vocabulary_create(int32_t device, int32_t nnodes, 
     if (child_off[0] != 0 || (nc > 0 && !child_idx)) { orbfe_set_error("vocabulary: bad child CSR"); return ORBFE_ERR_ARG; }
     for (int i = 0; i < nnodes; ++i) {
         if (child_off[i + 1] < child_off[i]) { orbfe_set_error("vocabulary: child offsets must not decrease"); return ORBFE_ERR_ARG; }
+        if (child_off[i + 1] == child_off[i] && word_id[i] > 0x7FFFFFFFu) {  // f_word is int32 and -1 means "no word"
+            orbfe_set_error("vocabulary: leaf %d has word id %u, word ids must be below 2^31", i, word_id[i]);
+            return ORBFE_ERR_ARG;
+        }
         for (uint32_t c = child_off[i]; c < child_off[i + 1]; ++c)
             if (child_idx[c] <= (uint32_t)i || child_idx[c] >= (uint32_t)nnodes) {
                 orbfe_set_error("vocabulary: child ids must be larger than their parent's id and < nnodes");
