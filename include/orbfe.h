@@ -820,7 +820,12 @@ orbfe_status orbfe_flow_compute_masks_homo_device(orbfe_flow *f, const uint8_t *
                                                   void *stream);
 /* perfect/src/Frame.cc:360-377 on the padded device blocks of orbfe_extract_batch_device, in place: frame i keeps only the
  * keypoints with mask[(int)y][(int)x] == 1 when d_mask_ones[i] > w*h*0.65, in order, descriptors following; slots >= the new
- * d_n[i] are zero-filled again (the all-gather invariant).  Enqueued on `stream`. */
+ * d_n[i] are zero-filled again (the all-gather invariant).  Enqueued on `stream`.
+ * d_mask_ones[i] is the SUM of mask i's values (cv::sum), as orbfe_flow_compute_masks*_device write it; for a 0 / 1 mask, its
+ * count of ones.  A mask value other than 1 under a keypoint drops it.  The reference reads the plane unchecked; here a
+ * keypoint is in the plane iff x > -1 && x < w && y > -1 && y < h, decided in float before the truncation (so a NaN or an
+ * infinity is out, and (-1, 0) truncates to column / row 0), and a keypoint outside the plane is dropped.  d_n[i] > cap
+ * counts as cap. */
 orbfe_status orbfe_mask_keypoints_device(const uint8_t *d_mask, int32_t w, int32_t h, int32_t mask_stride, size_t mask_frame_stride,
                                          const int32_t *d_mask_ones, int32_t nframes, orbfe_keypoint *d_kps, uint8_t *d_desc,
                                          int32_t *d_n, int32_t cap, void *stream);

@@ -673,8 +673,10 @@ __global__ __launch_bounds__(MK_T) void k_mask_keypoints(const uint8_t *mask, in
             k = K[i];
             d0 = D[i * 2];
             d1 = D[i * 2 + 1];
-            int xi = (int)k.x, yi = (int)k.y;
-            keep = (xi >= 0 && xi < w && yi >= 0 && yi < h) && mk[(size_t)yi * mstride + xi] == 1;
+            // the range is decided in float, as grid_cell_of does: the reference reads the plane unchecked, and the device's
+            // conversion gives 0 for a NaN (column / row 0 of the mask); (int) truncates towards zero, so (-1, 0) is column 0
+            if (k.x > -1.f && k.x < (float)w && k.y > -1.f && k.y < (float)h)
+                keep = mk[(size_t)(int)k.y * mstride + (int)k.x] == 1;
         }
         scan[threadIdx.x] = keep;
         __syncthreads();

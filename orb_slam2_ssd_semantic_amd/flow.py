@@ -113,9 +113,13 @@ class Flow(Handle):
 
 def mask_keypoints(masks, ones, kps, desc, n, cap, stream=None):
     """perfect/src/Frame.cc:360-377 in place on device blocks: masks uint8 [b, h, w], ones int32 [b], kps [b*cap*28] bytes
-    (orbfe_keypoint), desc uint8 [b*cap*32], n int32 [b] -- all torch tensors on the device."""
+    (orbfe_keypoint), desc uint8 [b*cap*32], n int32 [b] -- all torch tensors on the device.  masks may be pitched
+    (stride(1) >= w, stride(2) == 1).  ones[i] is the sum of mask i's values (what compute_masks returns); frame i is filtered
+    when it exceeds h*w*0.65.  A keypoint is in the plane iff x > -1 and x < w and y > -1 and y < h, decided in float before
+    the truncation (a NaN is out); a keypoint outside the plane, or on a mask value other than 1, is dropped."""
     import torch
     b, h, w = masks.shape
+    assert masks.dtype == torch.uint8 and masks.stride(2) == 1
     st = stream_arg(masks.device, stream)
-    _ffi.check(_ffi.lib().orbfe_mask_keypoints_device(tensor_ptr(masks), w, h, w, masks.stride(0), tensor_ptr(ones), b, tensor_ptr(kps), tensor_ptr(desc),
+    _ffi.check(_ffi.lib().orbfe_mask_keypoints_device(tensor_ptr(masks), w, h, masks.stride(1), masks.stride(0), tensor_ptr(ones), b, tensor_ptr(kps), tensor_ptr(desc),
                                                       tensor_ptr(n), cap, st), "orbfe_mask_keypoints_device")

@@ -508,9 +508,16 @@ class Flow:
 
 def mask_rule(mask, kps, desc):
     """perfect/src/Frame.cc:360-377: when sum(mask) > rows*cols*0.65, keep the keypoints with mask[int(y)][int(x)] == 1
-    (descriptors follow, order kept); otherwise keep all."""
+    (descriptors follow, order kept); otherwise keep all.  The reference reads the mask unchecked, so outside the plane it
+    has no defined result; the project's rule: a keypoint is in the plane iff x > -1 and x < w and y > -1 and y < h, decided in
+    float before the truncation (a NaN is out), and a keypoint outside the plane is dropped."""
     h, w = mask.shape
     if float(mask.astype(np.float64).sum()) > h * w * 0.65:
-        keep = mask[kps["y"].astype(np.int32), kps["x"].astype(np.int32)] == 1
+        x, y = kps["x"].astype(F32), kps["y"].astype(F32)
+        with np.errstate(invalid="ignore"):
+            inside = (x > F32(-1)) & (x < F32(w)) & (y > F32(-1)) & (y < F32(h))
+        xi = np.where(inside, x, F32(0)).astype(np.int32)   # C's (int): towards zero
+        yi = np.where(inside, y, F32(0)).astype(np.int32)
+        keep = inside & (mask[yi, xi] == 1)
         return kps[keep], desc[keep]
     return kps, desc

@@ -8,6 +8,7 @@ import pytest
 import scipy.ndimage as ndi
 
 import flow_oracle as FO
+from flow_checks import check_stages
 from orb_slam2_ssd_semantic_amd import KP_DTYPE, Flow, _ffi
 from orb_slam2_ssd_semantic_amd import flow as FL
 from orb_slam2_ssd_semantic_amd.synth import synth_frame
@@ -65,24 +66,6 @@ CASES = {
 }
 THS = {"patch_static_bg": [0.0, 64.0], "patch_moving_bg": [40.0, 400.0], "photo_shift": [64.0], "photo_affine": [0.0],
        "odd_641x481": [40.0], "hd_1280x720": [64.0, 400.0], "small_128x96": [0.0]}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def check_stages(fl, of, a_shape, label):
-    """every tap of the GPU's last call (frame 0) against the oracle Flow's taps"""
-    h, w = a_shape
-    assert np.array_equal(fl.tap(0, FL.TAP_HALF), of.taps["half"]), label + ": half"
-    for lv, ofl in enumerate(of.taps["flow_levels"][::-1]):
-        got = fl.tap(0, FL.TAP_FLOW, lv)
-        assert got.shape == ofl.shape, (label, lv)
-        bad = np.count_nonzero(_bits(got) != _bits(ofl))
-        assert bad == 0, f"{label}: flow level {lv}: {bad} of {ofl.size} words differ"
-    assert np.array_equal(_bits(fl.tap(0, FL.TAP_FLOW2)), _bits(of.taps["flow2"])), label + ": flow2"
-    assert np.array_equal(fl.tap(0, FL.TAP_PRE), of.taps["mask_pre"]), label + ": pre-morphology mask"
-    assert np.array_equal(fl.tap(0, FL.TAP_MASK), of.taps["mask"]), label + ": mask"
 
 
 @pytest.mark.gpu
