@@ -154,11 +154,10 @@ orbfe_status orbfe_get_work_counts(const orbfe_handle *h, int64_t out[2]);
  * knob from the process environment (a library inside a SLAM process must not change algorithm because of the host's
  * environment).  Every setting gives byte-identical results (ORBFE_OPT_BLUR_ROUNDING excepted).  Built-in choices, i.e. the value that
  * restores the default: OVERLAP -1; ROWS / ROWS_FAST / ROWS_BLUR / PYR_ROWS / QT_THREADS_* 0; BLUR_PIECES 1 (0 = the older packing, an
- * A/B variant); BLUR_UPDOWN 1 (0 = never, 2 = always); DEBUG 0; the [dev] fusions 0; FUSE_FAST_PYR_LEVELS 0 (= all levels; 1..8 = that
- * many); REUSE_IDENTICAL_INPUT 0.
- * Options marked [dev] select kernel variants that were measured slower than the default and are compiled only into a
- * developer build (-DORBFE_DEVELOPER, tools/ab_build.sh; such a build also honours $ORBFE_<NAME> at orbfe_create): a
- * release build answers ORBFE_ERR_STATE to a non-zero value.  Call between extract calls, not concurrently with one. */
+ * A/B variant); BLUR_UPDOWN 1 (0 = never, 2 = always); DEBUG 0; REUSE_IDENTICAL_INPUT 0.
+ * A developer build (-DORBFE_DEVELOPER, tools/ab_build.sh) also honours $ORBFE_<NAME> at orbfe_create.  The numbers 12 .. 15
+ * belonged to kernel variants that were measured slower than the default and have been removed; they stay reserved: value 0
+ * is accepted, anything else answers ORBFE_ERR_ARG.  Call between extract calls, not concurrently with one. */
 enum {
     ORBFE_OPT_OVERLAP = 1,        /* blur on the side stream: 0 never, 1 from before FAST, 2 beside the quadtree, -1 by batch size */
     ORBFE_OPT_ROWS = 2,           /* rows a FAST / blur wave walks (8..512) */
@@ -172,10 +171,7 @@ enum {
     ORBFE_OPT_QT_THREADS_2 = 10,
     ORBFE_OPT_DEBUG = 11,         /* forces production code paths that ordinary frames rarely take (tests): 50 = quadtree by
                                    * streaming key passes only (the deep-tree path), 51 = generic node passes only */
-    ORBFE_OPT_PYR_FUSE = 12,      /* [dev] 1: two pyramid levels per launch */
-    ORBFE_OPT_FUSE_BLUR_PYR = 13, /* [dev] 1 / 2: blur + resize in one chained pass */
-    ORBFE_OPT_FUSE_FAST_PYR = 14, /* [dev] 1 / 2: FAST + resize in one launch per level, 3: FAST of level 0 beside the pyramid */
-    ORBFE_OPT_FUSE_FAST_PYR_LEVELS = 15,
+    /* 12 .. 15: retired, reserved */
     ORBFE_OPT_BLUR_ROUNDING = 16, /* orbfe_params.blur_rounding of an existing handle (0 / 1); this one changes RESULTS */
     ORBFE_OPT_REUSE_IDENTICAL_INPUT = 17 /* single-frame host calls (orbfe_extract; orbfe_extract_batch with one frame), default 0.  1: a call whose
                                    * pixels equal those of the previous such call of this handle (same w, ht, cap; compared on the host against the pinned

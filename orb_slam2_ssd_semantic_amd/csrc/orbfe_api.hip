@@ -74,7 +74,7 @@ static std::vector<OwnedStream> handle_streams(orbfe_handle *h)
 static std::vector<hipEvent_t *> handle_events(orbfe_handle *h)
 {
     return {&h->ev_last, &h->ev_fork, &h->ev_join, &h->ev_in[0], &h->ev_cmp[0], &h->ev_out[0], &h->ev_in[1], &h->ev_cmp[1], &h->ev_out[1],
-            &h->ev_fork2, &h->ev_auto, &h->ev_join2};
+            &h->ev_fork2, &h->ev_auto};
 }
 
 // The plan of a w x ht frame (orbfe_plan.hip builds it on the host), uploaded and committed to the handle.
@@ -89,8 +89,7 @@ static orbfe_status build_plan(orbfe_handle *h, int w, int ht)
         {&h->d_tabs, T.tabs.data(), T.tabs.size(), sizeof(OrbTab)},
         {&h->d_flanes, T.flanes.data(), T.flanes.size(), sizeof(OrbLane)},
         {&h->d_flanes_c, T.clanes.data(), T.clanes.size(), sizeof(OrbLane)},
-        {&h->d_blanes, T.blanes.data(), T.blanes.size(), sizeof(OrbLane)},
-        {&h->d_blanesR, T.blanesR.data(), T.blanesR.size(), sizeof(OrbLaneR)}};
+        {&h->d_blanes, T.blanes.data(), T.blanes.size(), sizeof(OrbLane)}};
     for (const auto &u : up) ORBFE_HIP(u.buf->ensure(std::max<size_t>(u.count, 1) * u.elem));
     // synchronous copies: plans change rarely (frame size change), never inside the timed region.  Earlier batches may
     // still be in flight on the handle's stream or on the caller's stream of the previous device call: both are drained
@@ -130,8 +129,8 @@ static orbfe_status ensure_batch_buffers(orbfe_handle *h, int nframes)
     ORBFE_HIP(h->d_nsel.ensure(B * P.nlevels * sizeof(int32_t)));
     ORBFE_HIP(h->d_nkeys.ensure(B * P.nlevels * ORBFE_NK_STRIDE * sizeof(int32_t)));
     if (!h->d_misc.p) {
-        ORBFE_HIP(h->d_misc.ensure(1024));
-        ORBFE_HIP(hipMemset(h->d_misc.p, 0, 1024));
+        ORBFE_HIP(h->d_misc.ensure(sizeof(OrbMisc)));
+        ORBFE_HIP(hipMemset(h->d_misc.p, 0, sizeof(OrbMisc)));
     }
     return ORBFE_OK;
 }
@@ -142,8 +141,8 @@ static orbfe_status read_overflow(orbfe_handle *h, int32_t *flags)
     *flags = 0;
     if (!h->d_misc.p) return ORBFE_OK;
     ORBFE_HIP(wait_last_call(h));
-    ORBFE_HIP(hipMemcpy(flags, h->d_misc.p, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (*flags) ORBFE_HIP(hipMemset(h->d_misc.p, 0, sizeof(int32_t)));
+    ORBFE_HIP(hipMemcpy(flags, &misc_block(h)->overflow, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*flags) ORBFE_HIP(hipMemset(&misc_block(h)->overflow, 0, sizeof(int32_t)));
     return ORBFE_OK;
 }
 
@@ -221,9 +220,8 @@ static orbfe_status create_impl(const orbfe_params *p, hipStream_t borrowed, hip
         static const struct { const char *env; int opt; } kEnv[] = {
             {"ORBFE_OVERLAP", ORBFE_OPT_OVERLAP}, {"ORBFE_ROWS", ORBFE_OPT_ROWS}, {"ORBFE_ROWS_FAST", ORBFE_OPT_ROWS_FAST},
             {"ORBFE_ROWS_BLUR", ORBFE_OPT_ROWS_BLUR}, {"ORBFE_BLUR_PIECES", ORBFE_OPT_BLUR_PIECES},
-            {"ORBFE_BLUR_UPDOWN", ORBFE_OPT_BLUR_UPDOWN}, {"ORBFE_PW_ROWS", ORBFE_OPT_PYR_ROWS}, {"ORBFE_PYR_FUSE", ORBFE_OPT_PYR_FUSE},
-            {"ORBFE_DEBUG", ORBFE_OPT_DEBUG}, {"ORBFE_FUSE_BLUR_PYR", ORBFE_OPT_FUSE_BLUR_PYR},
-            {"ORBFE_FUSE_FAST_PYR", ORBFE_OPT_FUSE_FAST_PYR}, {"ORBFE_FUSE_FAST_PYR_LEVELS", ORBFE_OPT_FUSE_FAST_PYR_LEVELS}};
+            {"ORBFE_BLUR_UPDOWN", ORBFE_OPT_BLUR_UPDOWN}, {"ORBFE_PW_ROWS", ORBFE_OPT_PYR_ROWS},
+            {"ORBFE_DEBUG", ORBFE_OPT_DEBUG}};
         for (const auto &k : kEnv)
             if (const char *e = getenv(k.env)) (void)orbfe_set_option(h, k.opt, atoi(e));
         if (const char *e = getenv("ORBFE_QT")) {
@@ -256,7 +254,7 @@ extern "C" void orbfe_destroy(orbfe_handle *h)
     if (h->last_stream_valid && h->ev_last) (void)hipEventSynchronize(h->ev_last);
     for (const OwnedStream &s : handle_streams(h))
         if (*s.s) (void)hipStreamSynchronize(*s.s);
-    DevBuf *bufs[] = {&h->d_plan, &h->d_tabs, &h->d_flanes, &h->d_flanes_c, &h->d_blanes, &h->d_blanesR, &h->d_pyr, &h->d_blur, &h->d_skeys, &h->d_scount, &h->d_knode, &h->d_qtbox, &h->d_qtnodes, &h->d_sel, &h->d_nsel, &h->d_nkeys, &h->d_pad,
+    DevBuf *bufs[] = {&h->d_plan, &h->d_tabs, &h->d_flanes, &h->d_flanes_c, &h->d_blanes, &h->d_pyr, &h->d_blur, &h->d_skeys, &h->d_scount, &h->d_knode, &h->d_qtbox, &h->d_qtnodes, &h->d_sel, &h->d_nsel, &h->d_nkeys, &h->d_pad,
                       &h->d_stage[0], &h->d_okps[0], &h->d_odesc[0], &h->d_on[0], &h->d_stage[1], &h->d_okps[1], &h->d_odesc[1], &h->d_on[1]};
     for (DevBuf *b : bufs) b->release();
     h->d_misc.release();
@@ -358,14 +356,14 @@ extern "C" orbfe_status orbfe_get_overflow(orbfe_handle *h, int32_t *flags)
     return read_overflow(h, flags);
 }
 
-// developer builds (-DQT_PROFILE): the 1024-byte block behind the overflow word; reset != 0 clears everything but the word
+// developer builds (-DQT_PROFILE): the whole OrbMisc block (1024 bytes); reset != 0 clears the quadtree's phase sums
 extern "C" orbfe_status orbfe_internal_read_misc(orbfe_handle *h, void *out, int32_t reset)
 {
     if (!h || !out || !h->d_misc.p) return ORBFE_ERR_ARG;
     DeviceGuard g(h->device);
     ORBFE_HIP(wait_last_call(h));
-    ORBFE_HIP(hipMemcpy(out, h->d_misc.p, 1024, hipMemcpyDeviceToHost));
-    if (reset) ORBFE_HIP(hipMemset((char *)h->d_misc.p + 64, 0, 960));
+    ORBFE_HIP(hipMemcpy(out, h->d_misc.p, sizeof(OrbMisc), hipMemcpyDeviceToHost));
+    if (reset) ORBFE_HIP(hipMemset(misc_block(h)->qt_phase, 0, sizeof(OrbMisc::qt_phase)));
     return ORBFE_OK;
 }
 
@@ -373,15 +371,6 @@ extern "C" orbfe_status orbfe_set_option(orbfe_handle *h, int32_t option, int32_
 {
     if (!h) return ORBFE_ERR_ARG;
     auto in = [&](int lo, int hi) { return value >= lo && value <= hi; };
-    auto developer_only = [&]() {
-#ifdef ORBFE_DEVELOPER
-        return false;
-#else
-        if (value == 0) return false;   // "off" is always accepted
-        orbfe_set_error("option %d selects a kernel variant that is compiled into developer builds (-DORBFE_DEVELOPER) only", option);
-        return true;
-#endif
-    };
     bool replan = false;
     switch (option) {
     case ORBFE_OPT_OVERLAP: if (!in(-1, 2)) return ORBFE_ERR_ARG; h->overlap = value; break;
@@ -406,27 +395,12 @@ extern "C" orbfe_status orbfe_set_option(orbfe_handle *h, int32_t option, int32_
         h->pin.opt_debug = value;
         replan = true;
         break;
-    case ORBFE_OPT_PYR_FUSE: if (!in(0, 1)) return ORBFE_ERR_ARG; if (developer_only()) return ORBFE_ERR_STATE; h->kopts.pyr_fuse = value; break;
-    case ORBFE_OPT_FUSE_BLUR_PYR:
-        if (!in(0, 2)) return ORBFE_ERR_ARG;
-        if (developer_only()) return ORBFE_ERR_STATE;
-        h->pin.fuse_blur_pyr = value;
-        if (value) h->fuse_fast_pyr = 0;   // one fusion at a time
-        replan = true;
-        break;
-    case ORBFE_OPT_FUSE_FAST_PYR:
-        if (!in(0, 3)) return ORBFE_ERR_ARG;
-        if (developer_only()) return ORBFE_ERR_STATE;
-        h->fuse_fast_pyr = value;
-        if (value && h->pin.fuse_blur_pyr) { h->pin.fuse_blur_pyr = 0; replan = true; }
-        break;
-    case ORBFE_OPT_FUSE_FAST_PYR_LEVELS:   // matters for the developer-only variant ORBFE_OPT_FUSE_FAST_PYR alone; 0 = all levels (the default)
-        if (!in(0, ORBFE_MAX_LEVELS)) return ORBFE_ERR_ARG;
-        if (developer_only()) return ORBFE_ERR_STATE;
-        h->fuse_fast_pyr_levels = value ? value : ORBFE_MAX_LEVELS;
-        break;
     case ORBFE_OPT_BLUR_ROUNDING: if (!in(0, 1)) return ORBFE_ERR_ARG; h->pin.blur_rounding = value; replan = true; break;
     case ORBFE_OPT_REUSE_IDENTICAL_INPUT: if (!in(0, 1)) return ORBFE_ERR_ARG; h->opt_reuse = value; break;
+    case 12: case 13: case 14: case 15:   // the numbers of four retired kernel variants (profiles/HISTORY.md); "off" is still accepted
+        if (value == 0) break;
+        orbfe_set_error("option %d is retired: the kernel variant it selected has been removed", option);
+        return ORBFE_ERR_ARG;
     default: orbfe_set_error("unknown option %d", option); return ORBFE_ERR_ARG;
     }
     if (replan) h->plan_valid = false;   // rebuilt (behind the handle's outstanding work) by the next call
@@ -441,10 +415,7 @@ extern "C" orbfe_status orbfe_set_fast_mode(orbfe_handle *h, int32_t mode, int32
     if (!h || mode < 0 || mode > 3) return ORBFE_ERR_ARG;
     h->fast_mode = mode;
     h->fast_stats = collect_stats != 0;
-    h->auto_dense_left = 0;
-    h->auto_hold = ORBFE_AUTO_HOLD_MIN;
-    h->auto_since = 0;
-    h->auto_form = 2;
+    h->fauto = OrbFastAuto();
     return ORBFE_OK;
 }
 
@@ -460,31 +431,29 @@ extern "C" orbfe_status orbfe_get_fast_stats(orbfe_handle *h, uint64_t out[3], i
         for (int i = 0; i < 3; ++i) out[i] = h->auto_last[i];
         return ORBFE_OK;
     }
-    ORBFE_HIP(hipMemcpy(out, (char *)h->d_misc.p + 16, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reset) ORBFE_HIP(hipMemset((char *)h->d_misc.p + 16, 0, 3 * sizeof(uint64_t)));
+    ORBFE_HIP(hipMemcpy(out, misc_block(h)->fast_stat, sizeof(OrbMisc::fast_stat), hipMemcpyDeviceToHost));
+    if (reset) ORBFE_HIP(hipMemset(misc_block(h)->fast_stat, 0, sizeof(OrbMisc::fast_stat)));
     return ORBFE_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
 // the batched device path (everything else funnels into this)
 // ---------------------------------------------------------------------------------------------------
-// `lane` (null: everything on `st`, the blur possibly on the handle's side stream): one stream per stage group --
-// {pyramid, FAST, quadtree + descriptor, blur} -- ordered by the handle's events; `st` is then the tail stream lane[2]
-// (orbfe_internal_extract_batch_lanes).
-static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframes, int w, int ht, int stride,
-                              size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc, int cap,
-                              int32_t *d_n_out, hipStream_t st, const hipStream_t *lane = nullptr)
+// what the caller of a batched call hands in (orbfe_extract_batch_device's arguments)
+struct BatchCall {
+    const uint8_t *d_gray;
+    int nframes, w, ht, stride;
+    size_t frame_stride;
+    orbfe_keypoint *d_kps;
+    uint8_t *d_desc;
+    int cap;
+    int32_t *d_n_out;
+};
+
+// the launchers' view of a call: the handle's plan tables and scratch blocks, the caller's frames and output arrays
+static OrbLaunch launch_args(orbfe_handle *h, const BatchCall &c)
 {
-    if (w > h->prm.max_width || ht > h->prm.max_height) {
-        orbfe_set_error("frame %dx%d larger than planned %dx%d", w, ht, h->prm.max_width, h->prm.max_height);
-        return ORBFE_ERR_SIZE;
-    }
-    h->reuse_valid = false;   // the scratch blocks and taps belong to this call from here on
-    h->last_reused = false;
-    orbfe_status s = build_plan(h, w, ht);
-    if (s != ORBFE_OK) return s;
-    s = ensure_batch_buffers(h, nframes);
-    if (s != ORBFE_OK) return s;
+    const OrbPlan &P = h->plan;
     OrbLaunch a;
     a.opts = h->kopts;
     a.h_plan = &h->plan;
@@ -493,169 +462,78 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
     a.d_flanes = (const OrbLane *)h->d_flanes.p;
     a.d_flanes_c = (const OrbLane *)h->d_flanes_c.p;
     a.d_blanes = (const OrbLane *)h->d_blanes.p;
-    a.d_blanesR = (const OrbLaneR *)h->d_blanesR.p;
-    a.nframes = nframes;
-    a.d_gray = d_gray;
-    a.gray_fstride = (int64_t)frame_stride;
-    a.gray_pitch = stride;
+    a.nframes = c.nframes;
+    a.d_gray = c.d_gray;
+    a.gray_fstride = (int64_t)c.frame_stride;
+    a.gray_pitch = c.stride;
     a.d_pyr = (uint8_t *)h->d_pyr.p;
     a.d_blur = (uint8_t *)h->d_blur.p;
-    a.pyr_fstride = h->plan.pyr_frame_bytes;
+    a.pyr_fstride = P.pyr_frame_bytes;
     a.d_skeys = (uint2 *)h->d_skeys.p;
     a.d_scount = (int32_t *)h->d_scount.p;
-    a.d_cflag = (uint32_t *)(a.d_scount + (size_t)nframes * h->plan.nlevels * ORBFE_NK_STRIDE);  // right behind this call's counts
-    a.cf_words = (h->plan.max_ncells + 31) / 32;
+    a.d_cflag = (uint32_t *)(a.d_scount + (size_t)c.nframes * P.nlevels * ORBFE_NK_STRIDE);  // right behind this call's counts
+    a.cf_words = (P.max_ncells + 31) / 32;
     a.d_knode = (uint16_t *)h->d_knode.p;
     a.d_qtbox = (int16_t *)h->d_qtbox.p;
-    a.qtbox_stride = (int32_t)(orbk_octree_box_bytes(h->plan.node_cap) / sizeof(int16_t));
+    a.qtbox_stride = (int32_t)(orbk_octree_box_bytes(P.node_cap) / sizeof(int16_t));
     a.d_qtnodes = (char *)h->d_qtnodes.p;
-    a.qtnodes_stride = (int64_t)orbk_octree_node_bytes(h->plan.node_cap);
+    a.qtnodes_stride = (int64_t)orbk_octree_node_bytes(P.node_cap);
     a.d_sel = (uint32_t *)h->d_sel.p;
     a.d_nsel = (int32_t *)h->d_nsel.p;
     a.d_nkeys = (int32_t *)h->d_nkeys.p;
-    a.d_kps = d_kps;
-    a.d_desc = d_desc;
-    a.cap = cap;
-    a.d_n_out = d_n_out;
-    a.d_ovf = (int32_t *)h->d_misc.p;
-    // FAST form of this call.  Auto (3, the default): dense for calls of fewer than ORBFE_AUTO_MIN_ROW_STEPS wave row steps (about 29
-    // VGA frames); otherwise
-    // lane-compacting unless the last probe found more than ORBFE_AUTO_DENSE_RATE of the pixel pairs passing the necessary test --
-    // then dense for the next auto_hold calls (16, doubling up to 256 while the probes keep saying so), after which one compacting
-    // call probes again.
-    int fmode = h->fast_mode;
-    bool auto_probe = false;
-    if (fmode == 3 && (int64_t)nframes * h->fast_row_steps < ORBFE_AUTO_MIN_ROW_STEPS) {
-        fmode = 0;
-    } else if (fmode == 3) {
-        if (collect_auto_probe(h)) {
-            if (h->auto_last[0] > 0 && (double)h->auto_last[2] > ORBFE_AUTO_DENSE_RATE * 128.0 * (double)h->auto_last[0]) {
-                h->auto_form = 0;
-                h->auto_dense_left = h->auto_hold;
-                h->auto_hold = std::min(2 * h->auto_hold, ORBFE_AUTO_HOLD_MAX);
-            } else {
-                h->auto_form = 2;
-                h->auto_hold = ORBFE_AUTO_HOLD_MIN;
-                h->auto_since = 1;
-            }
-        }
-        // A host that runs ahead of the GPU enqueues many calls before a probe's answer arrives: those follow the LAST answer
-        // (auto_form), only the probe call itself is compacting when that answer was "dense".
-        if (h->auto_form == 0) {
-            if (h->auto_dense_left > 0) {
-                h->auto_dense_left--;
-                fmode = 0;
-            } else if (!h->auto_pending) {
-                fmode = 2;
-                auto_probe = true;
-            } else {
-                fmode = 0;
-            }
-        } else {
-            fmode = 2;
-            auto_probe = !h->auto_pending && (h->auto_since++ % ORBFE_AUTO_PROBE_EVERY) == 0;
-        }
+    a.d_kps = c.d_kps;
+    a.d_desc = c.d_desc;
+    a.cap = c.cap;
+    a.d_n_out = c.d_n_out;
+    a.d_ovf = &misc_block(h)->overflow;
+    a.fast_sparse = 0;     // the FAST form and its counters: run_batch
+    a.d_fstat = nullptr;
+    return a;
+}
+
+// Behind the FAST launch of a probing call, on its stream: the sampled counters -> pinned host memory, cleared for the next
+// probe; a later call looks at them (collect_auto_probe).
+static orbfe_status hand_off_auto_probe(orbfe_handle *h, hipStream_t st)
+{
+    ORBFE_HIP(hipMemcpyAsync(h->h_auto.p, misc_block(h)->fast_stat, sizeof(OrbMisc::fast_stat), hipMemcpyDeviceToHost, st));
+    ORBFE_HIP(hipMemsetAsync(misc_block(h)->fast_stat, 0, sizeof(OrbMisc::fast_stat), st));
+    ORBFE_HIP(hipEventRecord(h->ev_auto, st));
+    h->auto_pending = true;
+    return ORBFE_OK;
+}
+
+// The stages of a call on a stream per stage group (orbfe_internal_extract_batch_lanes): lane[0] pyramid, lane[1] FAST, lane[2]
+// quadtree + descriptor, lane[3] blur.  pyramid -> FAST and pyramid -> blur (ev_fork), FAST -> quadtree (ev_fork2), blur ->
+// descriptor (ev_join); the descriptor is the last launch on the tail stream lane[2], so that the next call of this handle starts
+// its pyramid behind everything of this one.
+static orbfe_status enqueue_lanes(orbfe_handle *h, const OrbLaunch &a, bool auto_probe, const hipStream_t *lane)
+{
+    const hipStream_t sp = lane[0], sf = lane[1], st = lane[2], sb = lane[3];
+    ORBFE_HIP(orbk_launch_pyramid(a, sp));
+    ORBFE_HIP(hipEventRecord(h->ev_fork, sp));
+    ORBFE_HIP(hipStreamWaitEvent(sf, h->ev_fork, 0));
+    if (sb != sp) ORBFE_HIP(hipStreamWaitEvent(sb, h->ev_fork, 0));
+    ORBFE_HIP(orbk_launch_fast(a, sf));
+    if (auto_probe) {
+        const orbfe_status s = hand_off_auto_probe(h, sf);
+        if (s != ORBFE_OK) return s;
     }
-#ifdef ORBFE_DEVELOPER
-    if (h->fuse_fast_pyr && fmode >= 2) {   // the fused FAST + pyramid kernels exist in the dense forms only
-        fmode = 0;
-        auto_probe = false;
-    }
-#endif
-    a.fast_sparse = fmode;
-    a.d_fstat = (h->fast_stats || auto_probe) ? (unsigned long long *)((char *)h->d_misc.p + 16) : nullptr;
-    // every call of a handle uses the same scratch blocks (pyramid, blur, survivor lists, selections): a call on another
-    // stream than its predecessor's waits, at stream level, for that predecessor to finish
-    hipStream_t first = lane ? lane[0] : st;   // the stream of the first launch, the pyramid's
-    if (h->last_stream_valid && h->last_stream != first) ORBFE_HIP(hipStreamWaitEvent(first, h->ev_last, 0));
-    // (a call in lanes is not profiled: the marks of one call would lie on four streams, between other sub-batches' kernels)
-    hipEvent_t *ev = (h->profiling && !lane) ? h->ev[h->prof_calls % ORBFE_PROF_RING] : nullptr;
-    if (ev) ORBFE_HIP(hipEventRecord(ev[0], st));
-    auto finish = [&]() -> orbfe_status {   // common tail: profiling bookkeeping, the "last call" state of the handle
-        if (ev) {
-            ORBFE_HIP(hipEventRecord(ev[5], st));
-            h->prof_calls++;
-        }
-        ORBFE_HIP(hipEventRecord(h->ev_last, st));
-        h->last_stream = st;
-        h->last_stream_valid = true;
-        h->last_gray = d_gray;
-        h->last_gray_fstride = (int64_t)frame_stride;
-        h->last_gray_pitch = stride;
-        h->last_nframes = nframes;
-        return ORBFE_OK;
-    };
-    if (lane) {
-        // pyramid -> FAST and pyramid -> blur (ev_fork), FAST -> quadtree (ev_fork2), blur -> descriptor (ev_join); ev_last behind
-        // the descriptor on the tail stream, so that the next call of this handle starts its pyramid behind everything of this one
-        if (h->pin.fuse_blur_pyr || h->fuse_fast_pyr) {
-            orbfe_set_error("the fused pyramid options have no stage streams");
-            return ORBFE_ERR_STATE;
-        }
-        hipStream_t sf = lane[1], sb = lane[3];
-        ORBFE_HIP(orbk_launch_pyramid(a, first));
-        ORBFE_HIP(hipEventRecord(h->ev_fork, first));
-        ORBFE_HIP(hipStreamWaitEvent(sf, h->ev_fork, 0));
-        if (sb != first) ORBFE_HIP(hipStreamWaitEvent(sb, h->ev_fork, 0));
-        ORBFE_HIP(orbk_launch_fast(a, sf));
-        if (auto_probe) {
-            ORBFE_HIP(hipMemcpyAsync(h->h_auto.p, (char *)h->d_misc.p + 16, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, sf));
-            ORBFE_HIP(hipMemsetAsync((char *)h->d_misc.p + 16, 0, 3 * sizeof(uint64_t), sf));
-            ORBFE_HIP(hipEventRecord(h->ev_auto, sf));
-            h->auto_pending = true;
-        }
-        ORBFE_HIP(hipEventRecord(h->ev_fork2, sf));
-        ORBFE_HIP(orbk_launch_blur(a, sb));
-        ORBFE_HIP(hipEventRecord(h->ev_join, sb));
-        ORBFE_HIP(hipStreamWaitEvent(st, h->ev_fork2, 0));
-        ORBFE_HIP(orbk_launch_octree(a, st));
-        if (sb != st) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-        ORBFE_HIP(orbk_launch_describe(a, st));
-        return finish();
-    }
-    int ov = h->overlap >= 0 ? h->overlap : (nframes >= 128 ? 2 : 0);
+    ORBFE_HIP(hipEventRecord(h->ev_fork2, sf));
+    ORBFE_HIP(orbk_launch_blur(a, sb));
+    ORBFE_HIP(hipEventRecord(h->ev_join, sb));
+    ORBFE_HIP(hipStreamWaitEvent(st, h->ev_fork2, 0));
+    ORBFE_HIP(orbk_launch_octree(a, st));
+    if (sb != st) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+    ORBFE_HIP(orbk_launch_describe(a, st));
+    return ORBFE_OK;
+}
+
+// The stages of a call on one stream, the blur possibly on the handle's side stream (handle.overlap: 1 from before FAST, 2 beside
+// the quadtree, 0 in line); ev (null: not profiled): the marks 1 .. 4, 6, 7 of ORBFE_EV_N.
+static orbfe_status enqueue_single_stream(orbfe_handle *h, const OrbLaunch &a, bool auto_probe, hipStream_t st, hipEvent_t *ev)
+{
+    int ov = h->overlap >= 0 ? h->overlap : (a.nframes >= 128 ? 2 : 0);
     if (!h->side) ov = 0;   // a pipe of a pipeline that fits its streams to the hardware queues and has none left for the blur
-#ifdef ORBFE_DEVELOPER
-    if (h->pin.fuse_blur_pyr) {
-        // blur(l) and resize(l -> l + 1) in one pass over level l, chained over the levels: level l is read from HBM once for
-        // both.  The stage table then shows the fused chain under "pyramid" and nothing under "blur"; `overlap` does not apply
-        // (there is no separate blur to put beside anything).
-        ORBFE_HIP(orbk_launch_blur_pyr(a, st));
-        if (ev) {
-            ORBFE_HIP(hipEventRecord(ev[1], st));
-            ORBFE_HIP(hipEventRecord(ev[6], st));
-            ORBFE_HIP(hipEventRecord(ev[7], st));
-        }
-        ORBFE_HIP(orbk_launch_fast(a, st));
-        if (ev) ORBFE_HIP(hipEventRecord(ev[2], st));
-        ORBFE_HIP(orbk_launch_octree(a, st));
-        if (ev) {
-            ORBFE_HIP(hipEventRecord(ev[3], st));
-            ORBFE_HIP(hipEventRecord(ev[4], st));
-        }
-        ORBFE_HIP(orbk_launch_describe(a, st));
-        return finish();
-    }
-    // ORBFE_OPT_FUSE_FAST_PYR 1 / 2: FAST(l) and resize(l -> l + 1) in one launch per level (k_fast_pyr); the stage table then
-    // shows the whole chain under "fast" and nothing under "pyramid".  3: no fused kernel -- FAST of level 0, which needs no
-    // pyramid, runs on the side stream BESIDE the pyramid chain (two FAST waves leave room for four resize waves on a SIMD),
-    // FAST of the other levels after both; it has its own event pair (ev_fork2 / ev_join2), the blur fork keeps ev_fork / ev_join
-    const bool ffp = h->fuse_fast_pyr == 1 || h->fuse_fast_pyr == 2;
-    const bool fside = h->fuse_fast_pyr == 3 && h->side;
-    if (fside) {
-        ORBFE_HIP(orbk_launch_fast_levels(a, 0, 0, 1, st));   // the clear only
-        ORBFE_HIP(hipEventRecord(h->ev_fork2, st));
-        ORBFE_HIP(hipStreamWaitEvent(h->side, h->ev_fork2, 0));
-        ORBFE_HIP(orbk_launch_fast_levels(a, 0, 1, 0, h->side));
-        ORBFE_HIP(hipEventRecord(h->ev_join2, h->side));
-    }
-    if ((ffp || fside) && ov == 1) ov = 2;   // the blur needs the whole pyramid, which the fused chain finishes last
-#else
-    const bool ffp = false, fside = false;
-    (void)fside;
-#endif
-    if (!ffp) ORBFE_HIP(orbk_launch_pyramid(a, st));
-    if (ev) ORBFE_HIP(hipEventRecord(ev[1], st));
     auto fork_blur = [&]() -> hipError_t {
         hipError_t e = hipEventRecord(h->ev_fork, st);
         if (e == hipSuccess) e = hipStreamWaitEvent(h->side, h->ev_fork, 0);
@@ -665,20 +543,13 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
         if (e == hipSuccess) e = hipEventRecord(h->ev_join, h->side);
         return e;
     };
+    ORBFE_HIP(orbk_launch_pyramid(a, st));
+    if (ev) ORBFE_HIP(hipEventRecord(ev[1], st));
     if (ov == 1) ORBFE_HIP(fork_blur());
-#ifdef ORBFE_DEVELOPER
-    if (ffp) ORBFE_HIP(orbk_launch_fast_pyr(a, h->fuse_fast_pyr_levels, h->fuse_fast_pyr == 2, st));
-    else if (fside) {
-        ORBFE_HIP(orbk_launch_fast_levels(a, 1, h->plan.nlevels, 0, st));
-        ORBFE_HIP(hipStreamWaitEvent(st, h->ev_join2, 0));
-    } else
-#endif
-        ORBFE_HIP(orbk_launch_fast(a, st));
-    if (auto_probe) {   // the sampled counters of this launch -> pinned host memory; a later call looks at them
-        ORBFE_HIP(hipMemcpyAsync(h->h_auto.p, (char *)h->d_misc.p + 16, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        ORBFE_HIP(hipMemsetAsync((char *)h->d_misc.p + 16, 0, 3 * sizeof(uint64_t), st));
-        ORBFE_HIP(hipEventRecord(h->ev_auto, st));
-        h->auto_pending = true;
+    ORBFE_HIP(orbk_launch_fast(a, st));
+    if (auto_probe) {
+        const orbfe_status s = hand_off_auto_probe(h, st);
+        if (s != ORBFE_OK) return s;
     }
     if (ev) ORBFE_HIP(hipEventRecord(ev[2], st));
     if (ov == 2) ORBFE_HIP(fork_blur());
@@ -693,7 +564,78 @@ static orbfe_status run_batch(orbfe_handle *h, const uint8_t *d_gray, int nframe
     }
     if (ev) ORBFE_HIP(hipEventRecord(ev[4], st));
     ORBFE_HIP(orbk_launch_describe(a, st));
-    return finish();
+    return ORBFE_OK;
+}
+
+// `lane` (null: everything on `st`, the blur possibly on the handle's side stream): one stream per stage group; `st` is then the
+// tail stream lane[2].
+static orbfe_status run_batch(orbfe_handle *h, const BatchCall &c, hipStream_t st, const hipStream_t *lane = nullptr)
+{
+    if (c.w > h->prm.max_width || c.ht > h->prm.max_height) {
+        orbfe_set_error("frame %dx%d larger than planned %dx%d", c.w, c.ht, h->prm.max_width, h->prm.max_height);
+        return ORBFE_ERR_SIZE;
+    }
+    h->reuse_valid = false;   // the scratch blocks and taps belong to this call from here on
+    h->last_reused = false;
+    orbfe_status s = build_plan(h, c.w, c.ht);
+    if (s != ORBFE_OK) return s;
+    s = ensure_batch_buffers(h, c.nframes);
+    if (s != ORBFE_OK) return s;
+    OrbLaunch a = launch_args(h, c);
+    // FAST form of this call; auto (3, the default): orbfe_fast_auto.h, fed with the probe answers that have arrived
+    OrbFastChoice fast = {h->fast_mode, false};
+    if (h->fast_mode == 3) {
+        const int64_t row_steps = (int64_t)c.nframes * h->fast_row_steps;
+        if (!orb_fast_auto_small(row_steps) && collect_auto_probe(h)) orb_fast_auto_answer(h->fauto, h->auto_last);
+        fast = orb_fast_auto_choose(h->fauto, row_steps, h->auto_pending);
+    }
+    a.fast_sparse = fast.form;
+    a.d_fstat = (h->fast_stats || fast.probe) ? (unsigned long long *)misc_block(h)->fast_stat : nullptr;
+    // every call of a handle uses the same scratch blocks (pyramid, blur, survivor lists, selections): a call on another
+    // stream than its predecessor's waits, at stream level, for that predecessor to finish
+    const hipStream_t first = lane ? lane[0] : st;   // the stream of the first launch, the pyramid's
+    if (h->last_stream_valid && h->last_stream != first) ORBFE_HIP(hipStreamWaitEvent(first, h->ev_last, 0));
+    // (a call in lanes is not profiled: the marks of one call would lie on four streams, between other sub-batches' kernels)
+    hipEvent_t *ev = (h->profiling && !lane) ? h->ev[h->prof_calls % ORBFE_PROF_RING] : nullptr;
+    if (ev) ORBFE_HIP(hipEventRecord(ev[0], st));
+    s = lane ? enqueue_lanes(h, a, fast.probe, lane) : enqueue_single_stream(h, a, fast.probe, st, ev);
+    if (s != ORBFE_OK) return s;
+    // common tail: profiling bookkeeping, the "last call" state of the handle
+    if (ev) {
+        ORBFE_HIP(hipEventRecord(ev[5], st));
+        h->prof_calls++;
+    }
+    ORBFE_HIP(hipEventRecord(h->ev_last, st));
+    h->last_stream = st;
+    h->last_stream_valid = true;
+    h->last_gray = c.d_gray;
+    h->last_gray_fstride = (int64_t)c.frame_stride;
+    h->last_gray_pitch = c.stride;
+    h->last_nframes = c.nframes;
+    return ORBFE_OK;
+}
+
+// Test hook (not in include/orbfe.h; tests/test_fast_auto.py): the automatic FAST mode of a fresh handle over n calls, without a
+// device.  Call i has row_steps[i] wave row steps and sees a probe outstanding iff pending[i]; has_answer[i] != 0: the counters
+// answer[3 * i ..] of a probe arrived before it (a small call leaves them for the next large one, as collect_auto_probe is not
+// asked then).  Out: form[i] (0 dense, 2 lane-compacting) and probe[i].
+extern "C" orbfe_status orbfe_internal_fast_auto(int32_t n, const int64_t *row_steps, const uint8_t *pending, const uint8_t *has_answer,
+                                                 const uint64_t *answer, int32_t *form, uint8_t *probe)
+{
+    if (n < 0 || !row_steps || !pending || !form || !probe || (has_answer && !answer)) return ORBFE_ERR_ARG;
+    OrbFastAuto st;
+    const uint64_t *waiting = nullptr;
+    for (int i = 0; i < n; ++i) {
+        if (has_answer && has_answer[i]) waiting = answer + 3 * (size_t)i;
+        if (waiting && !orb_fast_auto_small(row_steps[i])) {
+            orb_fast_auto_answer(st, waiting);
+            waiting = nullptr;
+        }
+        const OrbFastChoice c = orb_fast_auto_choose(st, row_steps[i], pending[i] != 0);
+        form[i] = c.form;
+        probe[i] = c.probe ? 1 : 0;
+    }
+    return ORBFE_OK;
 }
 
 extern "C" orbfe_status orbfe_extract_batch_device(orbfe_handle *h, const uint8_t *d_gray, int32_t nframes,
@@ -707,8 +649,7 @@ extern "C" orbfe_status orbfe_extract_batch_device(orbfe_handle *h, const uint8_
         return ORBFE_ERR_ARG;
     }
     DeviceGuard g(h->device);
-    return run_batch(h, d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out,
-                     (hipStream_t)stream);
+    return run_batch(h, BatchCall{d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out}, (hipStream_t)stream);
 }
 
 // orbfe_extract_batch_device with a stream per stage group, for the pipeline's lanes (orbfe_pipe_plan.h): lane[0] pyramid,
@@ -725,7 +666,7 @@ orbfe_status orbfe_internal_extract_batch_lanes(orbfe_handle *h, const uint8_t *
     }
     DeviceGuard g(h->device);
     const hipStream_t ls[4] = {(hipStream_t)lane[0], (hipStream_t)lane[1], (hipStream_t)lane[2], (hipStream_t)lane[3]};
-    return run_batch(h, d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out, ls[2], ls);
+    return run_batch(h, BatchCall{d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out}, ls[2], ls);
 }
 
 // host buffers, in chunks of max_batch frames.  A single chunk (the online case: one frame) is a plain H2D -> kernels ->
@@ -853,7 +794,7 @@ static orbfe_status extract_host(orbfe_handle *h, const uint8_t *const *grays, i
         const int k = c & (nset - 1), f0 = c * chunk_max, nb = std::min(chunk_max, nframes - f0);
         if (c >= 2) {  // set k was last used by chunk c-2: collect its results before its buffers are reused
             orbfe_status su = unpack(c - 2);
-            if (su != ORBFE_OK) { drain(); return su; }
+            if (su != ORBFE_OK) return su;
         }
         // ---- in ----
         if (piped && c >= 2) ORBFE_HIP(hipStreamWaitEvent(s_in, h->ev_cmp[k], 0));  // kernels of chunk c-2 read d_stage[k]
@@ -884,9 +825,9 @@ static orbfe_status extract_host(orbfe_handle *h, const uint8_t *const *grays, i
             if (c >= 2) ORBFE_HIP(hipStreamWaitEvent(s_cmp, h->ev_out[k], 0));  // D2H of chunk c-2 read the output set k
         }
         // ---- kernels ----
-        orbfe_status s = run_batch(h, (const uint8_t *)h->d_stage[k].p, nb, w, ht, pitch, fbytes, (orbfe_keypoint *)d_ok[k], d_od[k], cap,
-                                   (int32_t *)d_oc[k], s_cmp);
-        if (s != ORBFE_OK) { drain(); return s; }
+        orbfe_status s = run_batch(h, BatchCall{(const uint8_t *)h->d_stage[k].p, nb, w, ht, pitch, fbytes, (orbfe_keypoint *)d_ok[k], d_od[k], cap,
+                                                (int32_t *)d_oc[k]}, s_cmp);
+        if (s != ORBFE_OK) return s;
         if (piped) {
             ORBFE_HIP(hipEventRecord(h->ev_cmp[k], s_cmp));
             ORBFE_HIP(hipStreamWaitEvent(s_out, h->ev_cmp[k], 0));
@@ -903,19 +844,19 @@ static orbfe_status extract_host(orbfe_handle *h, const uint8_t *const *grays, i
             // the sticky overflow word travels with the results of the last chunk: an asynchronous 4-byte copy into pinned
             // memory behind the last kernels, in flight BEFORE the host starts waiting for results
             ORBFE_HIP(h->h_ovf.ensure(sizeof(int32_t)));
-            ORBFE_HIP(hipMemcpyAsync(h->h_ovf.p, h->d_misc.p, sizeof(int32_t), hipMemcpyDeviceToHost, s_cmp));
+            ORBFE_HIP(hipMemcpyAsync(h->h_ovf.p, &misc_block(h)->overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s_cmp));
         }
         ORBFE_HIP(hipEventRecord(h->ev_out[k], s_out));
     }
     for (int c = std::max(0, nchunks - 2); c < nchunks; ++c) {
         orbfe_status su = unpack(c);
-        if (su != ORBFE_OK) { drain(); return su; }
+        if (su != ORBFE_OK) return su;
     }
     ORBFE_HIP(hipStreamSynchronize(s_cmp));   // the overflow word (enqueued with the last chunk) has landed
     drain_guard.armed = false;  // everything has been waited for (unpack() synchronised the output events)
     {
         const int32_t ovf = *(const int32_t *)h->h_ovf.p;
-        if (ovf) ORBFE_HIP(hipMemset(h->d_misc.p, 0, sizeof(int32_t)));
+        if (ovf) ORBFE_HIP(hipMemset(&misc_block(h)->overflow, 0, sizeof(int32_t)));
         if (ovf & 3) {
             orbfe_set_error("internal capacity exceeded (flags %d: 1 = FAST survivor list, 2 = quadtree selection); "
                             "results of this batch are incomplete", ovf);

@@ -58,11 +58,6 @@ struct OrbLevel {
     float patch_size;      // (float)(int)(PATCH_SIZE * scale)  (:846)
     int32_t root_x[ORBFE_MAX_ROOTS + 1];  // root box x boundaries, nini+1 entries
     int32_t ix1, iy1;      // end of the union of the cells' detectable interiors ([19,ix1) x [19,iy1))
-    // two pyramid levels per launch (k_pyr_walk2): this level (B) is produced tile by tile from level l-1 and level l+1 (C)
-    // from the tile while it is in LDS.  Tile = p2_gx column groups (4 px) x p2_gy row runs; tiles overlap by one column
-    // group and one row; p2_cxs / p2_cys: first column / row of level l+1 each tile column / row owns (int32 tables inside
-    // the tap-table block, offsets in OrbTab entries).  p2_tx == 0: not fused.
-    int32_t p2_gx, p2_gy, p2_tx, p2_ty, p2_cxs, p2_cys;
 };
 
 // one FAST cell = one cv::FAST call of the reference (:798-838)
@@ -88,13 +83,6 @@ struct OrbLane {
     uint16_t flags;  // bit 0: halo (computes, does not output); bits 8..15: level
 };
 
-// the resize job a blur lane carries in the fused blur + pyramid pass: one destination dword of the next level
-struct OrbLaneR {
-    uint16_t dj;      // destination dword (4 pixels) of level l + 1
-    uint16_t d0, nd;  // destination rows [d0, d0 + nd): those whose upper source row lies in the lane's row block; nd = 0: none
-    uint16_t pad;
-};
-
 struct OrbPlan {
     int32_t nlevels;
     int32_t w, h;              // level-0 size this plan was built for
@@ -114,7 +102,6 @@ struct OrbPlan {
     int32_t fwave_off[ORBFE_MAX_LEVELS + 1];  // first FAST wave of every level (waves are single-level, levels in order)
     int32_t nbwaves;           // blur waves per frame (64 lane descriptors each)
     int32_t bwave_off[ORBFE_MAX_LEVELS + 1];  // first blur wave of every level (the lanes of a level are contiguous)
-    int32_t blur_split;        // the blur lane list also holds resize waves (flag bit 2): k_blur_pyr<., 1>; the plain k_blur7 launch skips them
     int64_t pyr_frame_bytes;   // bytes of one frame's pyramid slice (levels 1..n-1; level 0 kept too when owned)
     OrbLevel lv[ORBFE_MAX_LEVELS];
     // k_blur7, border waves: the horizontal taps of a lane with BORDER_REFLECT_101 folded into them.  [level][lane type][3 * j + d] =

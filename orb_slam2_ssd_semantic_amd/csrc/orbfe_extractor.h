@@ -2,7 +2,10 @@
 // (create / destroy, options, the batched call) and orbfe_taps.hip (the pyramid read-back and the stage taps).
 #pragma once
 
+#include <stddef.h>
+
 #include "orbfe_common.h"
+#include "orbfe_fast_auto.h"
 #include "orbfe_host.h"
 #include "orbfe_kernels.h"
 #include "orbfe_plan.h"
@@ -11,18 +14,18 @@
 // event marks of one profiled call: 0 start, 1 pyramid done, 2 FAST done, 3 quadtree done, 4 describe start, 5 end (launch
 // stream); 6 / 7 around the blur (on whichever stream it ran)
 #define ORBFE_EV_N 8
-// auto FAST mode: above this share of pixel pairs passing the necessary test the dense form is the cheaper one.  Measured per
-// 1024 frames of 640x480 (tools/compact_ab.py, profiles/r05_compact_ab.json; dense / lane-compacting, ms): pass rate 0.84 (S)
-// 1.47 / 2.14; 0.43 1.40 / 1.62; 0.38 1.42 / 1.55; 0.29 1.36 / 1.39; 0.18 (S_tum) 1.33 / 1.12; 0.076 1.26 / 0.92;
-// 0.02 1.22 / 0.74 -- break-even near 0.27
-#define ORBFE_AUTO_DENSE_RATE 0.25
-// ... and a launch that does not fill the GPU is bound by its longest wave, not by issue slots, and the dense form has the shorter
-// wave (FAST stage of ONE 640x480 frame: 18 us dense / 21 us compacting on S_tum, 20 / 26 on S; 8 frames: 29 / 34 and 31 / 44 --
-// tools/fast_mode_latency.py): below this many wave row steps per call (about 29 frames of 640x480 with 8 levels: 4 890 each) auto is dense
-#define ORBFE_AUTO_MIN_ROW_STEPS 140000
-#define ORBFE_AUTO_HOLD_MIN 16    // dense calls after a probe above the rate; doubles with every such probe in a row ...
-#define ORBFE_AUTO_HOLD_MAX 256   // ... up to this (a probe call on corner-saturated frames costs +45 % of its FAST stage)
-#define ORBFE_AUTO_PROBE_EVERY 8  // compacting calls between two looks at the pass rate
+
+// The handle's block of sticky device words (d_misc), zeroed when it is made.
+struct OrbMisc {
+    int32_t overflow;          // byte 0: sticky overflow bits (OrbLaunch::d_ovf; orbfe_get_overflow reads and clears them)
+    int32_t pad0[3];
+    uint64_t fast_stat[3];     // byte 16: counters of the FAST kernel (OrbLaunch::d_fstat): orbfe_set_fast_mode's statistics, or the
+                               // sample an automatic-mode probe takes
+    uint64_t pad1[3];
+    uint64_t qt_phase[120];    // byte 64: k_octree's per-phase clock sums, [level][8] (-DQT_PROFILE builds; orbfe_internal_read_misc)
+};
+static_assert(sizeof(OrbMisc) == 1024 && offsetof(OrbMisc, fast_stat) == 16 && offsetof(OrbMisc, qt_phase) == 64,
+              "k_octree's QT_STAMP and tools/octree_phases.py address the block by these offsets");
 
 struct orbfe_handle {
     orbfe_params prm;
@@ -37,11 +40,10 @@ struct orbfe_handle {
     // plan for the current frame size
     OrbPlan plan;
     bool plan_valid = false;
-    DevBuf d_plan, d_tabs, d_flanes, d_flanes_c, d_blanes, d_blanesR;
+    DevBuf d_plan, d_tabs, d_flanes, d_flanes_c, d_blanes;
     // per-batch blocks
     DevBuf d_pyr, d_blur, d_skeys, d_scount, d_knode, d_qtbox, d_qtnodes, d_sel, d_nsel, d_nkeys, d_pad;
-    // sticky overflow word + FAST sparse-variant statistics: [0] int32 overflow bits, [2..7] 3 x uint64 counters
-    DevBuf d_misc;
+    DevBuf d_misc;                // one OrbMisc
     int fast_mode = 3;            // 0 dense, 1 sparse shortcuts, 2 lane-compacting, 3 auto (default): 2 or 0 by batch size and observed pass rate (orbfe_set_fast_mode)
     bool fast_stats = false;
     // auto mode: the lane-compacting kernel reports {row steps, batches, parked pairs} of a sample of its waves; the counters are
@@ -49,10 +51,7 @@ struct orbfe_handle {
     PinBuf h_auto;                // 3 x uint64
     hipEvent_t ev_auto = nullptr;
     bool auto_pending = false;
-    int auto_dense_left = 0;      // calls still to run dense before the pass rate is probed again
-    int auto_hold = ORBFE_AUTO_HOLD_MIN;   // length of the next dense run
-    int auto_since = 0;           // compacting calls since the last probe
-    int auto_form = 2;            // the form the last probe chose (before the first answer: compacting, the probe's own form)
+    OrbFastAuto fauto;            // what the probes said so far (orbfe_fast_auto.h)
     uint64_t auto_last[3] = {0, 0, 0};
     int64_t fast_row_steps = 0;
     // The most recent batched call: its stream (only compared, never dereferenced: the caller may have destroyed it) and an
@@ -83,14 +82,11 @@ struct orbfe_handle {
     // batches that fill the chip (>= 128 frames: 3.71 -> 3.62 ms per 1024 frames, the HBM-bound blur fills the
     // quadtree's idle VALU / memory slots; next to the VALU-bound FAST pass it gains nothing), 0 for small ones
     int overlap = -1;
-    int fuse_fast_pyr = 0;   // 1 / 2: FAST(l) + resize(l -> l + 1) in one launch per level (ORBFE_FUSE_FAST_PYR; 2 = the two kinds of
-                             // workgroups dealt out proportionally over the grid, 1 = resize workgroups first)
-    int fuse_fast_pyr_levels = ORBFE_MAX_LEVELS;   // levels fused that way; the rest: plain resizes + one FAST launch
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;   // the side-stream FAST of ORBFE_OPT_FUSE_FAST_PYR = 3 (developer builds)
+    hipEvent_t ev_fork2 = nullptr;   // FAST -> quadtree, when the stages of a call run on streams of their own
     // tuning options that shape launches, not the plan (orbfe_set_option; 0 = built-in choice)
-    OrbOpts kopts = {0, 0, {0, 0, 0}};
+    OrbOpts kopts = {0, {0, 0, 0}};
     // ORBFE_OPT_REUSE_IDENTICAL_INPUT (orbfe_extract only): the frame of the last single-frame host call is still in the pinned
     // staging block h_stage[0] and its results in h_okps[0]; a call that brings the same pixels gets those results back without
     // touching the GPU.  reuse_valid is dropped by every other use of the handle (run_batch) and by every option change.
@@ -99,6 +95,8 @@ struct orbfe_handle {
     int reuse_w = 0, reuse_h = 0, reuse_cap = 0;
     int64_t reuse_hits = 0;
 };
+
+static inline OrbMisc *misc_block(orbfe_handle *h) { return (OrbMisc *)h->d_misc.p; }   // device pointer: for addresses only
 
 // waits until the last batched call of the handle has finished, on whichever stream it ran
 static inline hipError_t wait_last_call(orbfe_handle *h)

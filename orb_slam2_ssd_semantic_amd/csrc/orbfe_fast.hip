@@ -1,6 +1,6 @@
-// orbfe_fast.hip -- K2, FAST-9/16 with the reference's per-cell semantics: the dense forms (k_fast_map, k_fast_map_u), the
-// lane-compacting form (k_fast_map_c) and the developer kernel fused with the resize (k_fast_pyr).
-#include "orbfe_pyramid_dev.h"
+// orbfe_fast.hip -- K2, FAST-9/16 with the reference's per-cell semantics: the dense forms (k_fast_map, k_fast_map_u) and the
+// lane-compacting form (k_fast_map_c).
+#include "orbfe_kernels_dev.h"
 
 // ---------------------------------------------------------------------------------------------------
 // K2  FAST-9/16 with the reference's per-cell semantics: corner at t <=> A > t for the arc strength
@@ -27,7 +27,7 @@
 //              a cell), which is all DistributeOctTree's tie-break needs.  The fallback rule (a cell whose iniTh
 //              list is empty contributes its minTh list) is applied per cell in k_octree's prologue.
 
-// (the packed 16-bit helpers, two pixels per VALU instruction: orbfe_kernels_dev.h -- k_blur_pyr uses them too)
+// (the packed 16-bit helpers, two pixels per VALU instruction: orbfe_kernels_dev.h)
 
 // pixels (IDX, IDX+1) of a 12-byte row window as a u16 pair
 template <int IDX>
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) FM_OCC void k_fast_map(const OrbPlan *__restri
 #include "orbfe_fast_body.inc"
 }
 
-// FM_LDS_CONSTS is an A/B path of the generic dense form only (k_fast_map above, k_fast_pyr below): the cell-row and the
+// FM_LDS_CONSTS is an A/B path of the generic dense form only (k_fast_map above): the cell-row and the
 // lane-compacting kernel share text with it (orbfe_fast_body.inc, orbfe_fast_colmask.inc) and are compiled with the macro undefined.
 #pragma push_macro("FM_LDS_CONSTS")
 #undef FM_LDS_CONSTS
@@ -288,46 +288,6 @@ __global__ __launch_bounds__(256) FC_OCC void k_fast_map_c(const OrbPlan *__rest
 }
 #pragma pop_macro("FM_LDS_CONSTS")
 
-#ifdef ORBFE_DEVELOPER   // measured slower than the default chain; compiled only into developer builds
-// FAST on level l and cv::resize l -> l + 1 in ONE launch, the launches chained over the levels ("pyramid inside
-// the FAST pass").  FAST's live set leaves no register for a second job in its lanes (165 of the 168 that three waves per SIMD
-// allow), so the fusion is by WORKGROUP ROLE: `npyr` of the launch's workgroups per frame are resize workgroups
-// (k_pyr_walk's walk, unchanged), the others FAST workgroups over the wave range [wave_lo, wave_lo + nwaves) of the lane list.
-// Both read level l, FAST is VALU-bound and the walk HBM-bound, and the two kinds are dealt out proportionally over the block
-// index (spread = 1), so a CU holds both at any time and the second reader of a row finds it in L2; spread = 0 puts the resize
-// workgroups first.  npyr = 0 on the last level.
-template <int SPARSE>
-__global__ __launch_bounds__(256) void k_fast_pyr(const OrbPlan *__restrict__ plan, FrameSrc fs, const OrbLane *__restrict__ lanes,
-                                                  int wave_lo, int nwaves, uint2 *__restrict__ skeys, int32_t *__restrict__ scount,
-                                                  uint32_t *__restrict__ cflags, int32_t cf_words,
-                                                  unsigned long long *__restrict__ fstat, PyrArgs pa, int npyr, int spread)
-{
-    FM_SHARED_DECLS
-    FM_LDS_DECLS
-    int b = blockIdx.y, bx = blockIdx.x;
-    xcd_frame_remap(bx, b);
-    int before = min(bx, npyr);              // resize workgroups in front of this one
-    bool is_pyr = bx < npyr;
-    if (spread) {
-        const int T = (int)gridDim.x;
-        before = (int)(((uint32_t)bx * (uint32_t)npyr) / (uint32_t)T);
-        is_pyr = (int)(((uint32_t)(bx + 1) * (uint32_t)npyr) / (uint32_t)T) > before;
-    }
-    if (is_pyr) {
-        const PyrArgs &a = pa;
-        const uint32_t bxi = (uint32_t)before;
-#include "orbfe_pyr_body.inc"
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    if ((bx - before) * 4 + wv >= nwaves) return;
-    const int t = wave_lo + (bx - before) * 4 + wv;
-    constexpr bool CELLROWS = false;
-#include "orbfe_fast_body.inc"
-}
-#endif  // ORBFE_DEVELOPER
-
 // ---------------------------------------------------------------------------------------------------
 // launchers (host)
 // ---------------------------------------------------------------------------------------------------
@@ -366,60 +326,3 @@ hipError_t orbk_launch_fast(const OrbLaunch &a, hipStream_t st)
         fast_launch_dense(k_fast_map<0>, a, nostat, st);
     return hipGetLastError();
 }
-
-#ifdef ORBFE_DEVELOPER
-// one k_fast_pyr launch: FAST waves [w0, w1) of the lane list + the resize to level lpyr (0: none)
-static void fast_pyr_one(const OrbLaunch &a, int w0, int w1, int lpyr, int spread, hipStream_t st)
-{
-    const FrameSrc fs = make_src(a);
-    const OrbPlan &P = *a.h_plan;
-    unsigned long long *fstat = a.fast_sparse ? a.d_fstat : (unsigned long long *)nullptr;
-    PyrArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    int npyr = 0;
-    size_t lds = (size_t)a.cf_words * 16;
-    if (lpyr > 0) {
-        pyr_args(a, lpyr, pa);
-        npyr = (((P.lv[lpyr].w + 3) / 4) * pa.nrblk + 255) / 256;
-        lds = std::max(lds, orbk_pyramid_lds_bytes(P.lv[lpyr].h));
-    }
-    dim3 grid((w1 - w0 + 3) / 4 + npyr, a.nframes);
-    if (grid.x == 0) return;
-    if (a.fast_sparse)
-        hipLaunchKernelGGL(k_fast_pyr<1>, grid, dim3(256), lds, st, a.d_plan, fs, a.d_flanes, w0, w1 - w0, a.d_skeys, a.d_scount,
-                           a.d_cflag, a.cf_words, fstat, pa, npyr, spread);
-    else
-        hipLaunchKernelGGL(k_fast_pyr<0>, grid, dim3(256), lds, st, a.d_plan, fs, a.d_flanes, w0, w1 - w0, a.d_skeys, a.d_scount,
-                           a.d_cflag, a.cf_words, fstat, pa, npyr, spread);
-}
-
-hipError_t orbk_launch_fast_pyr(const OrbLaunch &a, int nfused, int spread, hipStream_t st)
-{
-    const OrbPlan &P = *a.h_plan;
-    const int nl = P.nlevels;
-    hipError_t e = fast_clear(a, st);
-    if (e != hipSuccess) return e;
-    nfused = std::max(1, std::min(nfused, nl));
-    for (int l = 0; l < nfused; ++l) fast_pyr_one(a, P.fwave_off[l], P.fwave_off[l + 1], l + 1 < nl ? l + 1 : 0, spread, st);
-    if (nfused < nl) {
-        // levels nfused + 1 .. nl - 1 as plain resize launches, then FAST over all remaining levels in one launch
-        for (int l = nfused + 1; l < nl; ++l) pyr_launch_level(a, l, st);
-        fast_pyr_one(a, P.fwave_off[nfused], P.nfwaves, 0, 0, st);
-    }
-    return hipGetLastError();
-}
-
-// FAST over the levels [l0, l1) of the lane list (no resize workgroups); clear = zero the survivor counts / cell flags first
-hipError_t orbk_launch_fast_levels(const OrbLaunch &a, int l0, int l1, int clear, hipStream_t st)
-{
-    const OrbPlan &P = *a.h_plan;
-    if (clear) {
-        hipError_t e = fast_clear(a, st);
-        if (e != hipSuccess) return e;
-    }
-    l0 = std::max(0, std::min(l0, (int)P.nlevels));
-    l1 = std::max(l0, std::min(l1, (int)P.nlevels));
-    fast_pyr_one(a, P.fwave_off[l0], P.fwave_off[l1], 0, 0, st);
-    return hipGetLastError();
-}
-#endif  // ORBFE_DEVELOPER

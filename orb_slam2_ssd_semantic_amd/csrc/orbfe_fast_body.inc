@@ -1,5 +1,5 @@
-// orbfe_fast_body.inc -- the body of the dense FAST pass of one wave (K2, see orbfe_fast.hip), included TEXTUALLY by k_fast_map,
-// k_fast_map_u and k_fast_pyr so that each compiles it in its own context (a shared __device__ function changed k_fast_map's
+// orbfe_fast_body.inc -- the body of the dense FAST pass of one wave (K2, see orbfe_fast.hip), included TEXTUALLY by k_fast_map
+// and k_fast_map_u so that each compiles it in its own context (a shared __device__ function changed k_fast_map's
 // register allocation: +1 % instructions).  Expects in scope: SPARSE, CELLROWS (constexpr bool, below), plan, fs, lanes, skeys,
 // scount, cflags, cf_words, fstat, s_buf, s_cf and the wave-uniform t (index of the wave in the lane list), b (frame), lane, wv.
 //

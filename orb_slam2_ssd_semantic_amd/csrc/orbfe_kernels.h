@@ -16,7 +16,6 @@
 // launch-shape options of a handle (orbfe_set_option); 0 = the built-in choice
 struct OrbOpts {
     int32_t pw_rows;   // destination rows per lane run of the pyramid kernels (2..ORBFE_PW_ROWS)
-    int32_t pyr_fuse;  // 1: two pyramid levels per launch (k_pyr_walk2; developer builds)
     int32_t qt[3];     // threads per workgroup of the quadtree's three level groups
 };
 
@@ -29,7 +28,6 @@ struct OrbLaunch {
     const OrbLane *d_flanes;
     const OrbLane *d_flanes_c;   // lane list of k_fast_map_c
     const OrbLane *d_blanes;
-    const OrbLaneR *d_blanesR;   // the resize job of every blur lane (fused blur + pyramid pass)
     int32_t nframes;
     // input frames (level 0, read in place)
     const uint8_t *d_gray;
@@ -77,16 +75,6 @@ hipError_t orbk_launch_fast(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_octree(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_blur(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_describe(const OrbLaunch &a, hipStream_t st);
-#ifdef ORBFE_DEVELOPER   // the measured-slower variants, compiled only into developer builds
-// FAST(l) + resize(l -> l + 1) in one launch per level for the levels below `nfused`, the remaining pyramid levels and one
-// FAST launch over the remaining waves after them (replaces orbk_launch_pyramid + orbk_launch_fast); spread: see k_fast_pyr
-hipError_t orbk_launch_fast_pyr(const OrbLaunch &a, int nfused, int spread, hipStream_t st);
-hipError_t orbk_launch_fast_levels(const OrbLaunch &a, int l0, int l1, int clear, hipStream_t st);
-// blur of every level and the pyramid in one chained pass (replaces orbk_launch_pyramid + orbk_launch_blur)
-hipError_t orbk_launch_blur_pyr(const OrbLaunch &a, hipStream_t st);
-// dynamic LDS of the two-level pyramid kernel for a tile of gx column groups x gy runs
-inline size_t orbk_pyramid2_lds_bytes(int gx, int gy) { return (size_t)(gy * ORBFE_PW_ROWS + 8) * sizeof(uint2) + (size_t)gy * ORBFE_PW_ROWS * gx * 4; }
-#endif
 
 // device view of the pyramid the handle built in its last call (orbfe_taps.hip), for kernels outside the extractor
 struct OrbPyrView {

@@ -435,8 +435,8 @@ __device__ __forceinline__ void qt_node_phase(const QtShared &q, int N, int &S, 
     modeB = modeB2;
 }
 
-// -DQT_PROFILE: per-phase clock stamps of k_octree summed into the words behind the overflow word (developer builds only;
-// read with orbfe_internal_read_misc, tools/octree_phases.py)
+// -DQT_PROFILE: per-phase clock stamps of k_octree summed into OrbMisc::qt_phase (orbfe_extractor.h: 64 bytes behind the overflow
+// word, eight 64-bit sums per level; developer builds only; read with orbfe_internal_read_misc, tools/octree_phases.py)
 #ifdef QT_PROFILE
 #define QT_STAMP(p)                                                                                              \
     do {                                                                                                         \

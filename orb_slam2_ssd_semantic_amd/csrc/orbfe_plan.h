@@ -17,7 +17,6 @@ struct OrbPlanIn {
     // tuning options (orbfe_set_option; 0 = built-in choice)
     int32_t opt_rows, opt_rows_fast, opt_rows_blur;
     int32_t opt_blur_pieces, opt_blur_updown, opt_debug;
-    int32_t fuse_blur_pyr;   // 1: blur + pyramid in one chained pass over the levels (ORBFE_FUSE_BLUR_PYR), 2: resize jobs in waves of their own
 };
 
 // the plan and the tables behind it, as the kernels read them
@@ -26,7 +25,6 @@ struct OrbPlanTables {
     std::vector<OrbCell> cells;
     std::vector<OrbTab> tabs;
     std::vector<OrbLane> flanes, clanes, blanes;   // dense FAST, lane-compacting FAST, blur
-    std::vector<OrbLaneR> blanesR;                 // the resize job of every blur lane (fused blur + pyramid pass), same index
     int64_t fast_row_steps;                        // wave row steps one frame costs k_fast_map (VALU model of bench.py's roofline)
 };
 
@@ -40,8 +38,7 @@ void orb_host_umax(int umax[16]);   // src/ORBextractor.cc:449-465
 orbfe_status orb_plan_build(const OrbPlanIn &in, int w, int h, OrbPlanTables *out);
 
 // Test hook (not in include/orbfe.h): builds the plan on the host and copies out the raw bytes of table `which`: 0 OrbPlan,
-// 1 cells, 2 tabs, 3 flanes, 4 clanes, 5 blanes, 6 blanesR, 7 fast_row_steps.  knobs: opt_rows, opt_rows_fast, opt_rows_blur,
-// opt_blur_pieces, opt_blur_updown, opt_debug, fuse_blur_pyr, taken raw (orbfe_set_option's range checks and release-build
-// refusals are not repeated).  *bytes = the table's size; dst == NULL is the sizing call.  Touches no device.
-extern "C" orbfe_status orbfe_internal_plan_table(const orbfe_params *p, const int32_t knobs[7], int32_t w, int32_t h, int32_t which,
+// 1 cells, 2 tabs, 3 flanes, 4 clanes, 5 blanes, 6 fast_row_steps.  knobs: opt_rows, opt_rows_fast, opt_rows_blur,
+// opt_blur_pieces, opt_blur_updown, opt_debug, taken raw (orbfe_set_option's range checks are not repeated).  *bytes = the table's size; dst == NULL is the sizing call.  Touches no device.
+extern "C" orbfe_status orbfe_internal_plan_table(const orbfe_params *p, const int32_t knobs[6], int32_t w, int32_t h, int32_t which,
                                                   void *dst, size_t cap, size_t *bytes);

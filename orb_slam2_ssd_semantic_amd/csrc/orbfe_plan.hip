@@ -81,8 +81,6 @@ void orb_host_umax(int umax[16])
 
 namespace
 {
-const OrbLaneR kNoJob = {0, 0, 0, 0};   // a blur lane without a resize job
-
 // a lane that computes along with its wave and outputs nothing (flag bit 0)
 OrbLane dead_lane(int level, int x, int ys, int nrows, int flags = 0)
 {
@@ -261,52 +259,6 @@ orbfe_status level_taps(int l, OrbPlan &P, std::vector<OrbTab> &tabs)
     }
     return ORBFE_OK;
 }
-
-#ifdef ORBFE_DEVELOPER
-// ---------------------------------------------------------------------------------------------------
-// developer-only two-level tiling
-// ---------------------------------------------------------------------------------------------------
-// Two pyramid levels per launch (ORBFE_OPT_PYR_FUSE, developer builds): for B = 1, 3, 5, ... with a level C = B + 1 above
-// it, the tiling of B and the first C column / row every tile column / row owns (C pixel (x2, y2) belongs to the tile that
-// holds its top-left tap (sx(x2), sy(y2)) in its own -- non-overlap -- part).
-void plan_pyr2_tiling(OrbPlan &P, std::vector<OrbTab> &tabs)
-{
-    for (int l = 1; l + 1 < P.nlevels; l += 2) {
-        OrbLevel &B = P.lv[l];
-        const OrbLevel &C = P.lv[l + 1];
-        const int ngroups = (B.w + 3) / 4;
-        const int ntx0 = (ngroups + 63) / 64;
-        int gx = std::max(2, std::min(64, (ngroups + ntx0 - 1) / ntx0 + (ntx0 > 1 ? 1 : 0)));
-        int gy = std::max(1, 256 / gx);
-        const int trows = gy * ORBFE_PW_ROWS;
-        if (trows < 2 || orbk_pyramid2_lds_bytes(gx, gy) > 60 * 1024) continue;
-        const int tiles_x = ngroups <= gx ? 1 : (ngroups - 1 + gx - 2) / (gx - 1);
-        const int tiles_y = B.h <= trows ? 1 : (B.h - 1 + trows - 2) / (trows - 1);
-        auto add_i32 = [&](const std::vector<int32_t> &v) {
-            const int at = align_tabs(tabs);
-            tabs.resize(tabs.size() + (v.size() + 1) / 2 + 1);
-            memcpy(&tabs[(size_t)at], v.data(), v.size() * sizeof(int32_t));
-            return at;
-        };
-        // first entry of the tap table `tab` (n entries) whose source index reaches t * step, for t = 0 .. tiles
-        auto owned_from = [&](int tab, int n, int tiles, int step) {
-            std::vector<int32_t> first((size_t)tiles + 1);
-            for (int t = 0; t <= tiles; ++t) {
-                int d = 0;
-                if (t == tiles) d = n;
-                else
-                    while (d < n && tabs[(size_t)tab + d].s < t * step) ++d;
-                first[(size_t)t] = d;
-            }
-            return first;
-        };
-        const std::vector<int32_t> cxs = owned_from(C.xtab, C.w, tiles_x, (gx - 1) * 4), cys = owned_from(C.ytab, C.h, tiles_y, trows - 1);
-        B.p2_gx = gx; B.p2_gy = gy; B.p2_tx = tiles_x; B.p2_ty = tiles_y;
-        B.p2_cxs = add_i32(cxs);
-        B.p2_cys = add_i32(cys);
-    }
-}
-#endif
 
 // what the level loop adds up to: scratch sizes per frame and the quadtree's node capacity
 orbfe_status plan_totals(const LevelSums &S, OrbPlanTables &T)
@@ -522,12 +474,8 @@ struct BlurLevel {
     bool pieces;
     int ncol, nblk, rb;   // 4-px columns; row blocks and their (balanced) height
     int right0;           // first column of the 64-byte piece that holds the first column whose window reaches past the row's right end
-    // fused blur + pyramid pass: destination dword j of level l + 1 is carried by the blur lane of source column
-    // floor(j * ncol / ncolD) (injective: the level shrinks), i.e. by a lane whose blur window lies over its source pixels
-    std::vector<int> dword_of_col;
 
     const OrbLevel &L() const { return T.plan.lv[l]; }
-    bool has_next() const { return l + 1 < T.plan.nlevels; }
     int block_rows(int k) const { return std::min(rb, L().h - k * rb); }
     OrbLane lane(int c, int ys, int nr, bool interior, int flags = 0) const
     {
@@ -540,26 +488,11 @@ struct BlurLevel {
         const bool no_reflection = 4 * c >= 4 && 4 * c + 8 <= L().w;
         return pieces ? (no_reflection && c >= 16 && c < right0) : no_reflection;
     }
-    // the destination rows of level l + 1 whose upper source row lies in the row block [ys, ys + nr), for the dword column c carries
-    OrbLaneR resize_job(int c, int ys, int nr) const
-    {
-        OrbLaneR r = kNoJob;
-        if (!has_next() || c < 0 || dword_of_col[(size_t)c] < 0 || nr <= 0) return r;
-        const OrbLevel &D = T.plan.lv[l + 1];
-        int d0 = 0;
-        while (d0 < D.h && T.tabs[(size_t)D.ytab + d0].s < ys) ++d0;          // first destination row whose upper source row is in the block
-        int d1 = d0;
-        while (d1 < D.h && T.tabs[(size_t)D.ytab + d1].s < ys + nr) ++d1;
-        r.dj = (uint16_t)dword_of_col[(size_t)c];
-        r.d0 = (uint16_t)d0;
-        r.nd = (uint16_t)(d1 - d0);
-        return r;
-    }
 };
 
-// One pass (0: interior waves, 1: border waves) of the plain layout, appended to ol / orr.  nparity 2: the even row blocks'
-// lanes first, then the odd blocks' with flag bit 3; jobs: every lane carries its resize job (fuse_blur_pyr 1).
-void blur_pass(const BlurLevel &B, int pass, int nparity, bool jobs, std::vector<OrbLane> &ol, std::vector<OrbLaneR> &orr)
+// One pass (0: interior waves, 1: border waves) of the layout, appended to ol.  nparity 2: the even row blocks' lanes first,
+// then the odd blocks' with flag bit 3.
+void blur_pass(const BlurLevel &B, int pass, int nparity, std::vector<OrbLane> &ol)
 {
     for (int par = 0; par < nparity; ++par) {
         const int upflag = par ? 8 : 0;
@@ -571,13 +504,12 @@ void blur_pass(const BlurLevel &B, int pass, int nparity, bool jobs, std::vector
                 const bool interior = B.is_interior(c);
                 if (interior != (pass == 0)) continue;
                 ol.push_back(B.lane(c, ys, nr, interior, upflag));
-                orr.push_back(jobs ? B.resize_job(c, ys, nr) : kNoJob);
                 // the right piece is padded to its 16 slots, so that the next row block's left piece starts a piece again
                 if (B.pieces && pass == 1 && c == B.ncol - 1)
-                    while (ol.size() % 16) { ol.push_back(B.dead(false, upflag)); orr.push_back(kNoJob); }
+                    while (ol.size() % 16) ol.push_back(B.dead(false, upflag));
             }
         }
-        while (ol.size() % 64) { ol.push_back(B.dead(pass == 0, upflag)); orr.push_back(kNoJob); }
+        while (ol.size() % 64) ol.push_back(B.dead(pass == 0, upflag));
     }
 }
 
@@ -587,75 +519,21 @@ void blur_pass(const BlurLevel &B, int pass, int nparity, bool jobs, std::vector
 // the second reader finds the halo rows in L2 instead of HBM: FETCH_SIZE of the kernel -18 % when every level does it.
 // Keeping the two directions in waves of their own can cost a level one more (partly filled) wave, i.e. instructions,
 // which is what the pipeline as a whole is bound by: a (level, pass) is split only where the wave count stays the same
-// (ORBFE_OPT_BLUR_UPDOWN = 0: never, 2: always; the fused blur + pyramid passes walk downwards only).
+// (ORBFE_OPT_BLUR_UPDOWN = 0: never, 2: always).
 void blur_pass_updown(const BlurLevel &B, int pass, bool always, OrbPlanTables &T)
 {
     std::vector<OrbLane> l1, l2;
-    std::vector<OrbLaneR> r1, r2;
-    blur_pass(B, pass, 1, false, l1, r1);
-    blur_pass(B, pass, 2, false, l2, r2);
+    blur_pass(B, pass, 1, l1);
+    blur_pass(B, pass, 2, l2);
     const bool split = always || l2.size() == l1.size();
     T.blanes.insert(T.blanes.end(), (split ? l2 : l1).begin(), (split ? l2 : l1).end());
-    T.blanesR.insert(T.blanesR.end(), (split ? r2 : r1).begin(), (split ? r2 : r1).end());
 }
 
-// fuse_blur_pyr 2: interior blur waves and resize waves of the same row blocks side by side in the wave list (a workgroup is four
-// consecutive waves): whichever kind touches a source row second finds it in L1 / L2.  Two queues, whole waves of one
-// kind are emitted as soon as they fill, so neither kind runs more than a row block ahead of the other.
-void blur_resize_waves(const BlurLevel &B, OrbPlanTables &T)
-{
-    std::vector<OrbLane> &blanes = T.blanes;
-    std::vector<OrbLaneR> &blanesR = T.blanesR;
-    std::vector<OrbLane> qb, qr;
-    std::vector<OrbLaneR> qrr;
-    const int l = B.l, ncolD = (T.plan.lv[l + 1].w + 3) / 4;
-    // the first (at most 64) lanes of queue q, with their jobs (jobs null: none), as one wave padded with `pad`
-    auto emit_wave = [&](std::vector<OrbLane> &q, std::vector<OrbLaneR> *jobs, const OrbLane &pad) {
-        const size_t n = std::min<size_t>(64, q.size());
-        blanes.insert(blanes.end(), q.begin(), q.begin() + n);
-        if (jobs) {
-            blanesR.insert(blanesR.end(), jobs->begin(), jobs->begin() + n);
-            jobs->erase(jobs->begin(), jobs->begin() + n);
-        } else {
-            blanesR.insert(blanesR.end(), n, kNoJob);
-        }
-        q.erase(q.begin(), q.begin() + n);
-        while (blanes.size() % 64) { blanes.push_back(pad); blanesR.push_back(kNoJob); }
-    };
-    auto flush = [&](bool all) {
-        while (qb.size() >= 64 || qr.size() >= 64 || (all && (!qb.empty() || !qr.empty()))) {
-            if (qb.size() >= 64 || (all && !qb.empty())) emit_wave(qb, nullptr, B.dead(true));
-            if (qr.size() >= 64 || (all && !qr.empty())) emit_wave(qr, &qrr, dead_lane(l, 0, 0, 0, 4));
-        }
-    };
-    for (int k = 0; k < B.nblk; ++k) {
-        const int ys = k * B.rb, nr = B.block_rows(k);
-        if (nr <= 0) continue;
-        for (int c = 0; c < B.ncol; ++c)
-            if (B.is_interior(c)) qb.push_back(B.lane(c, ys, nr, true));
-        // the destination rows whose upper source row lies in this row block, for every destination dword
-        OrbLaneR rows = B.resize_job(0, ys, nr);
-        if (B.dword_of_col[0] < 0) {   // resize_job wants a column that carries a dword: take the row range from any such column
-            for (int c = 0; c < B.ncol; ++c)
-                if (B.dword_of_col[(size_t)c] >= 0) { rows = B.resize_job(c, ys, nr); break; }
-        }
-        for (int j = 0; j < ncolD && rows.nd; ++j) {
-            qr.push_back(OrbLane{0, (uint16_t)ys, 0, (uint16_t)((l << 8) | 4)});
-            qrr.push_back(OrbLaneR{(uint16_t)j, rows.d0, rows.nd, 0});
-        }
-        flush(false);
-    }
-    flush(true);
-    // border blur waves as in the plain layout
-    blur_pass(B, 1, 1, false, blanes, blanesR);
-}
-
-orbfe_status plan_blur_lanes(const OrbPlanIn &in, int rows_blur, OrbPlanTables &T)
+void plan_blur_lanes(const OrbPlanIn &in, int rows_blur, OrbPlanTables &T)
 {
     OrbPlan &P = T.plan;
     const int nl = P.nlevels;
     const int updown = std::max(0, std::min(2, in.opt_blur_updown));
-    const int fuse = in.fuse_blur_pyr;   // 0: blur only, 1: every blur lane carries a resize job, 2: resize jobs in waves of their own
     for (int l = 0; l < nl; ++l) {
         const OrbLevel &L = P.lv[l];
         BlurLevel B{T, l, in.opt_blur_pieces != 0};
@@ -663,29 +541,14 @@ orbfe_status plan_blur_lanes(const OrbPlanIn &in, int rows_blur, OrbPlanTables &
         B.nblk = (L.h + rows_blur - 1) / rows_blur;
         B.rb = (L.h + B.nblk - 1) / B.nblk;
         B.right0 = (std::min(B.ncol - 1, std::max(0, (L.w - 8) / 4 + 1)) / 16) * 16;
-        B.dword_of_col.assign((size_t)B.ncol, -1);
-        if (l + 1 < nl) {
-            const int ncolD = (P.lv[l + 1].w + 3) / 4;
-            for (int j = 0; j < ncolD; ++j) {
-                const int c = std::min(B.ncol - 1, (int)((int64_t)j * B.ncol / ncolD));
-                if (B.dword_of_col[(size_t)c] >= 0) { orbfe_set_error("level %d: two destination dwords on one blur column", l); return ORBFE_ERR_SIZE; }
-                B.dword_of_col[(size_t)c] = j;
-            }
-        }
         P.bwave_off[l] = (int)(T.blanes.size() / 64);
-        if (fuse == 2 && l + 1 < nl) {
-            blur_resize_waves(B, T);
-        } else {
-            for (int pass = 0; pass < 2; ++pass) {  // 0: interior waves, 1: border waves
-                if (fuse == 0 && updown) blur_pass_updown(B, pass, updown == 2, T);
-                else blur_pass(B, pass, 1, fuse == 1, T.blanes, T.blanesR);
-            }
+        for (int pass = 0; pass < 2; ++pass) {  // 0: interior waves, 1: border waves
+            if (updown) blur_pass_updown(B, pass, updown == 2, T);
+            else blur_pass(B, pass, 1, T.blanes);
         }
         P.bwave_off[l + 1] = (int)(T.blanes.size() / 64);
     }
     P.nbwaves = (int)(T.blanes.size() / 64);
-    P.blur_split = fuse == 2;
-    return ORBFE_OK;
 }
 }  // namespace
 
@@ -727,13 +590,10 @@ orbfe_status orb_plan_build(const OrbPlanIn &in, int w, int ht, OrbPlanTables *o
             return ORBFE_ERR_SIZE;
         }
     }
-#ifdef ORBFE_DEVELOPER
-    plan_pyr2_tiling(P, T.tabs);
-#endif
     if ((s = plan_totals(S, T)) != ORBFE_OK) return s;
     plan_fast_lanes(rows_fast, T);
     if ((s = plan_blur_weights(P)) != ORBFE_OK) return s;
-    if ((s = plan_blur_lanes(in, rows_blur, T)) != ORBFE_OK) return s;
+    plan_blur_lanes(in, rows_blur, T);
     if (P.ini_th < P.min_th) {
         orbfe_set_error("iniThFAST (%d) must be >= minThFAST (%d)", P.ini_th, P.min_th);
         return ORBFE_ERR_ARG;
@@ -741,10 +601,10 @@ orbfe_status orb_plan_build(const OrbPlanIn &in, int w, int ht, OrbPlanTables *o
     return ORBFE_OK;
 }
 
-extern "C" orbfe_status orbfe_internal_plan_table(const orbfe_params *p, const int32_t knobs[7], int32_t w, int32_t h, int32_t which,
+extern "C" orbfe_status orbfe_internal_plan_table(const orbfe_params *p, const int32_t knobs[6], int32_t w, int32_t h, int32_t which,
                                                   void *dst, size_t cap, size_t *bytes)
 {
-    if (!p || !knobs || !bytes || w < 1 || h < 1 || w > 4096 || h > 4096 || which < 0 || which > 7) {
+    if (!p || !knobs || !bytes || w < 1 || h < 1 || w > 4096 || h > 4096 || which < 0 || which > 6) {
         orbfe_set_error("bad argument to orbfe_internal_plan_table");
         return ORBFE_ERR_ARG;
     }
@@ -753,17 +613,15 @@ extern "C" orbfe_status orbfe_internal_plan_table(const orbfe_params *p, const i
     if (s != ORBFE_OK) return s;
     in.opt_rows = knobs[0]; in.opt_rows_fast = knobs[1]; in.opt_rows_blur = knobs[2];
     in.opt_blur_pieces = knobs[3]; in.opt_blur_updown = knobs[4]; in.opt_debug = knobs[5];
-    in.fuse_blur_pyr = knobs[6];
     OrbPlanTables T;
     if ((s = orb_plan_build(in, w, h, &T)) != ORBFE_OK) return s;
-    const struct { const void *p; size_t n; } tables[8] = {
+    const struct { const void *p; size_t n; } tables[7] = {
         {&T.plan, sizeof(OrbPlan)},
         {T.cells.data(), T.cells.size() * sizeof(OrbCell)},
         {T.tabs.data(), T.tabs.size() * sizeof(OrbTab)},
         {T.flanes.data(), T.flanes.size() * sizeof(OrbLane)},
         {T.clanes.data(), T.clanes.size() * sizeof(OrbLane)},
         {T.blanes.data(), T.blanes.size() * sizeof(OrbLane)},
-        {T.blanesR.data(), T.blanesR.size() * sizeof(OrbLaneR)},
         {&T.fast_row_steps, sizeof(T.fast_row_steps)}};
     *bytes = tables[which].n;
     if (!dst) return ORBFE_OK;   // sizing call

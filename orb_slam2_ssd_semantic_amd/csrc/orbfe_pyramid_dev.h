@@ -1,5 +1,5 @@
-// orbfe_pyramid_dev.h -- what K1 (orbfe_pyramid.hip) shares with the fused developer kernels k_fast_pyr (orbfe_fast.hip) and
-// k_blur_pyr (orbfe_blur.hip): the arguments of a resize launch, the walk of one lane and the host-side pyr_args.
+// orbfe_pyramid_dev.h -- the inside of K1 (orbfe_pyramid.hip): the arguments of a resize launch, the walk of one lane and the
+// host-side pyr_args.
 #pragma once
 #include "orbfe_kernels_dev.h"
 
@@ -219,6 +219,3 @@ static void pyr_args(const OrbLaunch &a, int l, PyrArgs &pa)
     pa.rb = (D.h + nb - 1) / nb;               // balanced run length
     pa.nrblk = (D.h + pa.rb - 1) / pa.rb;      // no empty run
 }
-
-// one k_pyr_walk launch, level l from level l - 1 (orbfe_pyramid.hip: a kernel is launched from the file that defines it)
-__attribute__((visibility("hidden"))) void pyr_launch_level(const OrbLaunch &a, int l, hipStream_t st);

@@ -20,7 +20,7 @@ class ORBextractor(Handle):
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, *,
                  max_width=640, max_height=480, max_batch=1, device=-1, blur_rounding=0, options=None, lib=None, _borrow=None):
         """options: {name: value} for orbfe_set_option (names: _ffi.OPTIONS), applied before the first call.  lib: another
-        build of liborbfe (_ffi.load_variant), e.g. the developer build that holds the measured-slower kernel variants."""
+        build of liborbfe (_ffi.load_variant), e.g. the developer build (-DORBFE_DEVELOPER)."""
         self._L = lib or _ffi.lib()
         self._h = C.c_void_p()
         self._owned = _borrow is None
@@ -43,7 +43,7 @@ class ORBextractor(Handle):
 
     def set_option(self, name, value):
         """orbfe_set_option by name (overlap, rows, rows_fast, rows_blur, blur_pieces, blur_updown, pyr_rows, qt_threads_0..2,
-        debug, and -- developer builds only -- pyr_fuse, fuse_blur_pyr, fuse_fast_pyr, fuse_fast_pyr_levels)"""
+        debug)"""
         check(self._L.orbfe_set_option(self._h, _ffi.OPTIONS[name], int(value)), f"orbfe_set_option({name}, {value})")
 
     def last_call_reused(self):

@@ -201,23 +201,6 @@ def test_large_nfeatures_node_arrays_beyond_the_lds(oracle, nf, h, w):
         assert_same_output(kps[b, :n[b]].copy().view(KP_DTYPE).reshape(-1), desc[b, :n[b]], *ref[b])
 
 
-def test_two_pyramid_levels_per_launch(oracle, dev_lib):
-    """ORBFE_OPT_PYR_FUSE = 1 (developer build): k_pyr_walk2 produces level l in LDS tiles and level l+1 from the tile (the odd levels are not
-    re-read from HBM).  Not the default (it is slower on this part, see the launcher), but byte-exact: every level of odd
-    and even sized frames, 8 and 5 levels, scale factors 1.2 and 1.35, against the oracle."""
-    from orb_slam2_ssd_semantic_amd import ORBextractor
-    for (h, w, nl, sf, seed) in ((480, 640, 8, 1.2, 1), (389, 517, 8, 1.2, 7), (1080, 1920, 8, 1.2, 3), (301, 1203, 5, 1.35, 9),
-                                 (600, 431, 7, 1.2, 4)):
-        img = synth_frame(seed, h, w)
-        oe = oracle.OracleExtractor(700, sf, nl, 20, 7)
-        ok, od = oe(img, cap=1200)
-        e = ORBextractor(700, sf, nl, 20, 7, max_width=w, max_height=h, lib=dev_lib, options={"pyr_fuse": 1})
-        gk, gd = e(img)
-        for l in range(nl):
-            assert np.array_equal(e.pyramid_level(l), oe.level(l)), (h, w, l)
-        assert_same_output(gk, gd, ok, od)
-
-
 def test_generic_quadtree_passes_only(oracle):
     """ORBFE_OPT_DEBUG = 51 disables the fused breadth-first pass of the histogram mode: every pass goes through the generic node
     phase (the one the largest-first passes and the deep trees use) and must give the same trees."""
@@ -499,61 +482,6 @@ def test_side_stream_blur_and_grouped_quadtree_equal_the_inline_single_launch_pa
     for i in (0, 67, 135):
         ok, od = oe(frames[i], cap=1200)
         assert_same_output(k0[i, :n0[i]].copy().view(KP_DTYPE).reshape(-1), d0[i, :n0[i]], ok, od)
-
-
-@pytest.mark.parametrize("fuse", ["1", "2"])
-def test_fused_blur_and_pyramid_pass_equals_the_separate_kernels(oracle, dev_lib, fuse):
-    """ORBFE_OPT_FUSE_BLUR_PYR (developer build): blur(l) and resize(l -> l + 1) in one chained pass over the levels (k_blur_pyr): 1 = every blur lane
-    carries a resize job, 2 = resize jobs in waves of their own beside the blur waves of the same rows.  Neither beats k_pyr_walk
-    + k_blur7 on time, so both are off by default -- same pyramid, same blurred levels, same output, in
-    both blur rounding modes and on odd sizes."""
-    from orb_slam2_ssd_semantic_amd import ORBextractor
-    for (w, h, nf, nlev, sf, mode) in ((640, 480, 1000, 8, 1.2, 0), (517, 389, 700, 6, 1.3, 1), (333, 271, 400, 4, 1.5, 0)):
-        e = ORBextractor(nf, sf, nlev, 20, 7, max_width=w, max_height=h, max_batch=3, blur_rounding=mode, lib=dev_lib,
-                         options={"fuse_blur_pyr": int(fuse)})
-        frames = [synth_frame(500 + i, h, w, sparse=(i == 1)) for i in range(3)]
-        oe = oracle.OracleExtractor(nf, sf, nlev, 20, 7)
-        oe.set_blur_mode(mode)
-        for img in frames:
-            ok, od = oe(img)
-            gk, gd = e(img)
-            for l in range(nlev):
-                assert np.array_equal(e.pyramid_level(l), oe.level(l)), (w, l)
-                if len(oe.selected(l)):
-                    assert np.array_equal(e.blurred_level(l), oe.blurred(l)), (w, l)
-            assert_same_output(gk, gd, ok, od)
-
-
-@pytest.mark.parametrize("fuse,levels", [("1", None), ("2", None), ("2", "3"), ("1", "1"), ("3", None)])
-def test_fused_fast_and_pyramid_pass_equals_the_separate_kernels(oracle, dev_lib, fuse, levels):
-    """ORBFE_OPT_FUSE_FAST_PYR (developer build; VERDICT r03 #3, "pyramid inside the FAST pass"): FAST(l) and resize(l -> l + 1) in ONE launch per
-    level (k_fast_pyr), the two jobs in workgroups of their own -- 1 = resize workgroups first, 2 = dealt out proportionally;
-    ORBFE_FUSE_FAST_PYR_LEVELS = k fuses the first k levels only (plain resizes + one FAST launch for the rest); 3 = no fused
-    kernel, FAST of level 0 on the side stream beside the pyramid chain.  Same pyramid,
-    same candidate lists, same output as k_pyr_walk x 7 + k_fast_map, single frames and batches, odd sizes, both FAST variants."""
-    from orb_slam2_ssd_semantic_amd import ORBextractor
-    opts = {"fuse_fast_pyr": int(fuse)}
-    if levels:
-        opts["fuse_fast_pyr_levels"] = int(levels)
-    for (w, h, nf, nlev, sf) in ((640, 480, 1000, 8, 1.2), (517, 389, 700, 6, 1.3), (333, 271, 400, 4, 1.5), (128, 112, 100, 3, 1.2)):
-        e = ORBextractor(nf, sf, nlev, 20, 7, max_width=w, max_height=h, max_batch=16, lib=dev_lib, options=opts)
-        frames = [synth_frame(700 + i, h, w, sparse=(i % 3 == 1)) for i in range(16)]
-        oe = oracle.OracleExtractor(nf, sf, nlev, 20, 7)
-        outs = []
-        for img in frames[:3]:
-            ok, od = oe(img)
-            outs.append((ok, od))
-            gk, gd = e(img)
-            for l in range(nlev):
-                assert np.array_equal(e.pyramid_level(l), oe.level(l)), (w, l)
-            assert_same_output(gk, gd, ok, od)
-        # a batch (a multiple of 8 frames: the frame -> XCD remap of the grid is active) == the single calls
-        res = e.extract_batch(np.stack(frames))
-        for i in (0, 1, 2):
-            gk, gd = res[i]
-            assert_same_output(gk, gd, outs[i][0], outs[i][1])
-        ok, od = oe(frames[15])
-        assert_same_output(res[15][0], res[15][1], ok, od)
 
 
 @pytest.mark.parametrize("updown", ["0", "2"])

@@ -1,13 +1,14 @@
 """The extractor's launch plan (csrc/orbfe_plan.hip) without a GPU, through the test hook orbfe_internal_plan_table.
 
-(a) byte identity: the tables of every case of the matrix hash to tests/golden/plan_digests.json, recorded from the planner as
-    it was inside orbfe_api.hip before it became a file of its own (release and -DORBFE_DEVELOPER build);
+(a) byte identity: the tables of every case of the matrix hash to tests/golden/plan_digests.json, recorded from the release
+    planner of the last commit that carried the fused kernel variants (profiles/HISTORY.md), its plan table re-packed field by
+    field without the fields that went with them; the -DORBFE_DEVELOPER build gives the same tables;
 (b) the contracts the FAST, blur and pyramid kernels rely on, checked on the tables themselves;
 (c) the planner's errors: status and text;
 (d) the planner alone under AddressSanitizer / UBSan (tests/cpp/test_plan_sanitize.cpp, a child process).
 
 The matrix: the shapes and run lengths of tests/test_gpu_launch_options.py (imported, not copied); max_batch 1 / 8 / 9 (default
-runs of 8 / 16 / 40 rows); rows 512; blur_pieces x blur_updown x fuse_blur_pyr.  max_batch only chooses the default run length,
+runs of 8 / 16 / 40 rows); rows 512; blur_pieces x blur_updown.  max_batch only chooses the default run length,
 so it is crossed with the options that leave the run length to it; an explicit ROWS_FAST / ROWS_BLUR value is taken at 9."""
 import ctypes as C
 import hashlib
@@ -24,10 +25,10 @@ from test_gpu_launch_options import EDGE, ROWS_BLUR, ROWS_FAST, SHAPES, default_
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "plan_digests.json")
-TABLES = ("plan", "cells", "tabs", "flanes", "clanes", "blanes", "blanesR", "fast_row_steps")
-KNOBS = ("rows", "rows_fast", "rows_blur", "blur_pieces", "blur_updown", "debug", "fuse_blur_pyr")
-DEFAULT = dict(rows=0, rows_fast=0, rows_blur=0, blur_pieces=1, blur_updown=1, debug=0, fuse_blur_pyr=0)
-BLUR_LAYOUTS = [dict(blur_pieces=p, blur_updown=u, fuse_blur_pyr=f) for p in (0, 1) for u in (0, 1, 2) for f in (0, 1, 2)]
+TABLES = ("plan", "cells", "tabs", "flanes", "clanes", "blanes", "fast_row_steps")
+KNOBS = ("rows", "rows_fast", "rows_blur", "blur_pieces", "blur_updown", "debug")
+DEFAULT = dict(rows=0, rows_fast=0, rows_blur=0, blur_pieces=1, blur_updown=1, debug=0)
+BLUR_LAYOUTS = [dict(blur_pieces=p, blur_updown=u) for p in (0, 1) for u in (0, 1, 2)]
 
 
 @lru_cache(maxsize=None)
@@ -50,16 +51,14 @@ def case_line(shape, mb, knobs, ini=20, mn=7):
 
 # ---- the tables --------------------------------------------------------------------------------------------------------------
 LANE = np.dtype([("x", "<u2"), ("ys", "<u2"), ("nrows", "<u2"), ("flags", "<u2")])
-LANER = np.dtype([("dj", "<u2"), ("d0", "<u2"), ("nd", "<u2"), ("pad", "<u2")])
 TAB = np.dtype([("c0", "<i2"), ("c1", "<i2"), ("s", "<i2"), ("pad", "<i2")])
 _i = "<i4"
 LEVEL = np.dtype([(n, _i) for n in ("w", "h", "pitch", "off", "ncols", "nrows", "wcell", "hcell", "cell0", "ncells", "ncc", "nfeat", "nini")] +
                  [("hx", "<f4")] + [(n, _i) for n in ("key_off", "key_cap", "sel_off", "sel_cap", "xtab", "ytab")] +
-                 [("scale", "<f4"), ("patch_size", "<f4"), ("root_x", _i, 9), ("ix1", _i), ("iy1", _i)] +
-                 [(n, _i) for n in ("p2_gx", "p2_gy", "p2_tx", "p2_ty", "p2_cxs", "p2_cys")])
+                 [("scale", "<f4"), ("patch_size", "<f4"), ("root_x", _i, 9), ("ix1", _i), ("iy1", _i)])
 PLAN = np.dtype([(n, _i) for n in ("nlevels", "w", "h", "ncells", "cell_cap", "max_ncells", "keys_per_frame", "sel_per_frame", "node_cap",
                                    "max_nini", "ini_th", "min_th", "blur_rounding", "dbg", "nfwaves", "nfwaves_c", "fast_cellrows")] +
-                [("fwave_off", _i, 17), ("nbwaves", _i), ("bwave_off", _i, 17), ("blur_split", _i), ("pad", _i), ("pyr_frame_bytes", "<i8"),
+                [("fwave_off", _i, 17), ("nbwaves", _i), ("bwave_off", _i, 17), ("pyr_frame_bytes", "<i8"),
                  ("lv", LEVEL, 16), ("blur_wt", "<u4", (16, 4, 12))])
 
 
@@ -85,7 +84,7 @@ def params(shape, mb, ini=20, mn=7, **kw):
 def table(L, p, knobs, w, h, which):
     """(status, bytes) of one table"""
     n = C.c_size_t(0)
-    s = hook(L)(C.byref(p), (C.c_int32 * 7)(*[knobs[k] for k in KNOBS]), w, h, which, _BUF, len(_BUF), C.byref(n))
+    s = hook(L)(C.byref(p), (C.c_int32 * 6)(*[knobs[k] for k in KNOBS]), w, h, which, _BUF, len(_BUF), C.byref(n))
     return s, C.string_at(_BUF, n.value) if s == 0 else b""
 
 
@@ -93,7 +92,7 @@ def tables(L, shape, mb, knobs):
     w, h = SHAPES[shape][:2]
     p = params(shape, mb)
     out = []
-    for which in range(8):
+    for which in range(len(TABLES)):
         s, b = table(L, p, knobs, w, h, which)
         assert s == 0, (shape, mb, knobs, which, L.orbfe_last_error())
         out.append(b)
@@ -111,14 +110,13 @@ class Plan:
         self.lv = self.P["lv"][:self.nl]
         self.tabs = np.frombuffer(raw[2], TAB)
         self.flanes, self.clanes, self.blanes = (np.frombuffer(raw[k], LANE) for k in (3, 4, 5))
-        self.blanesR = np.frombuffer(raw[6], LANER)
-        self.fast_row_steps = int(np.frombuffer(raw[7], "<i8")[0])
+        self.fast_row_steps = int(np.frombuffer(raw[6], "<i8")[0])
 
 
 # ---- (a) byte identity -------------------------------------------------------------------------------------------------------
 def digests(fetch):
     """{shape: {table: sha256 over the table's bytes of every case, in the order of cases(), each prefixed with its length}};
-    fetch(shape, max_batch, knobs) -> the 8 tables"""
+    fetch(shape, max_batch, knobs) -> the tables"""
     out = {}
     for shape in SHAPES:
         hs = [hashlib.sha256() for _ in TABLES]
@@ -130,34 +128,32 @@ def digests(fetch):
     return out
 
 
-def check_digests(L, build):
-    want = json.load(open(GOLDEN))[build]
+def check_digests(L):
+    want = json.load(open(GOLDEN))["release"]
     got = digests(lambda shape, mb, knobs: tables(L, shape, mb, knobs))
     bad = [(s, t) for s in SHAPES for t in TABLES if got[s][t] != want[s][t]]
     assert not bad, bad
 
 
 def test_tables_are_byte_identical_release():
-    check_digests(_ffi.lib(), "release")
+    check_digests(_ffi.lib())
 
 
 def test_tables_are_byte_identical_developer(dev_lib):
-    """the developer build adds the two-level pyramid tiling (p2_*) to the plan and the tap-table block"""
-    check_digests(dev_lib, "developer")
-    want = json.load(open(GOLDEN))
-    assert all(want["developer"][s]["tabs"] != want["release"][s]["tabs"] for s in SHAPES)
+    """the developer build plans exactly what the release build plans"""
+    check_digests(dev_lib)
 
 
 def test_sizing_call_and_capacity():
     L = _ffi.lib()
     p, n = params("tiny", 1), C.c_size_t(0)
-    k = (C.c_int32 * 7)(*[DEFAULT[x] for x in KNOBS])
-    for which in range(8):
+    k = (C.c_int32 * 6)(*[DEFAULT[x] for x in KNOBS])
+    for which in range(len(TABLES)):
         assert hook(L)(C.byref(p), k, 209, 155, which, None, 0, C.byref(n)) == 0
         s, b = table(L, p, DEFAULT, 209, 155, which)
         assert s == 0 and len(b) == n.value > 0
         assert hook(L)(C.byref(p), k, 209, 155, which, _BUF, n.value - 1, C.byref(n)) == _ffi.ORBFE_ERR_CAP
-    assert hook(L)(C.byref(p), k, 209, 155, 8, None, 0, C.byref(n)) == _ffi.ORBFE_ERR_ARG
+    assert hook(L)(C.byref(p), k, 209, 155, len(TABLES), None, 0, C.byref(n)) == _ffi.ORBFE_ERR_ARG
     assert hook(L)(C.byref(p), k, 0, 155, 0, None, 0, C.byref(n)) == _ffi.ORBFE_ERR_ARG
 
 
@@ -240,9 +236,9 @@ def assert_rows_once(idx, r0, n, ncol, nrow, what):
     assert (np.cumsum(d, axis=1)[:, :nrow] == 1).all(), what
 
 
-def check_blur(pl, fuse):
-    P, b, r = pl.P, pl.blanes, pl.blanesR
-    assert len(b) == len(r) == 64 * P["nbwaves"] and P["blur_split"] == (fuse == 2)
+def check_blur(pl):
+    P, b = pl.P, pl.blanes
+    assert len(b) == 64 * P["nbwaves"]
     wl = levels_of_waves(b, "blur")
     off = P["bwave_off"]
     assert off[0] == 0 and off[pl.nl] == P["nbwaves"] and (np.diff(off[:pl.nl + 1]) >= 0).all()
@@ -251,26 +247,16 @@ def check_blur(pl, fuse):
     fl = b["flags"].astype(int)
     kind = (fl & 0xE).reshape(-1, 64)
     assert (kind == kind[:, :1]).all()      # a wave is uniform in flag bits 1, 2 and 3
+    assert not (fl & 4).any()               # (bit 2 is not in use)
     lvl = fl >> 8
     x, ys, nr = b["x"].astype(int), b["ys"].astype(int), b["nrows"].astype(int)
     inner = (fl & 2) != 0
     assert ((x[inner] >= 4) & (x[inner] + 8 <= pl.lv["w"][lvl[inner]])).all()   # the window [x - 4, x + 8) lies inside the row
-    blur = (fl & 5) == 0        # neither dead nor a resize lane
-    jobs = r["nd"] > 0
-    if fuse == 0:
-        assert not r.view("<u2").any()
-    assert not (jobs & ((fl & 1) != 0)).any()
-    assert (jobs <= (((fl & 4) != 0) if fuse == 2 else blur)).all()
+    blur = (fl & 1) == 0        # not dead
     for l, L in enumerate(pl.lv):
         m = blur & (lvl == l)
         assert (x[m] % 4 == 0).all()
         assert_rows_once(x[m] // 4, ys[m], nr[m], (int(L["w"]) + 3) // 4, int(L["h"]), ("blur", l))
-        if fuse and l + 1 < pl.nl:
-            D, j = pl.lv[l + 1], jobs & (lvl == l)
-            assert_rows_once(r["dj"][j].astype(int), r["d0"][j].astype(int), r["nd"][j].astype(int), (int(D["w"]) + 3) // 4, int(D["h"]),
-                             ("resize jobs", l))
-        else:
-            assert not (jobs & (lvl == l)).any()
     # the 12 weight bytes of every (level, lane type, output pixel) are the 7 taps of the kernel
     wt = np.ascontiguousarray(P["blur_wt"][:pl.nl]).view(np.uint8).reshape(pl.nl, 4, 4, 12)
     assert (wt.sum(axis=3) == 257).all()
@@ -314,15 +300,15 @@ def test_fast_lane_lists(oracle, shape):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_blur_lane_list(shape):
-    """the blur lane list in its three layouts, the resize jobs and the folded weights, for every case that shapes them"""
+    """the blur lane list in its layouts and the folded weights, for every case that shapes them"""
     L, seen = _ffi.lib(), set()
     for mb, k in cases():
-        key = (effective(k["rows_blur"], k["rows"], mb), k["blur_pieces"], k["blur_updown"], k["fuse_blur_pyr"])
+        key = (effective(k["rows_blur"], k["rows"], mb), k["blur_pieces"], k["blur_updown"])
         if key in seen:
             continue
         seen.add(key)
-        check_blur(Plan(L, shape, mb, k), k["fuse_blur_pyr"])
-    assert seen >= {(r, lay["blur_pieces"], lay["blur_updown"], lay["fuse_blur_pyr"]) for r in ROWS_BLUR + (16, 40) for lay in BLUR_LAYOUTS}
+        check_blur(Plan(L, shape, mb, k))
+    assert seen >= {(r, lay["blur_pieces"], lay["blur_updown"]) for r in ROWS_BLUR + (16, 40) for lay in BLUR_LAYOUTS}
 
 
 def test_updown_split_keeps_the_wave_count(oracle):
