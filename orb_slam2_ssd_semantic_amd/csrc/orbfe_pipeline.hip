@@ -7,10 +7,13 @@
 // chip with the HBM / LDS-bound stages of its neighbours -- and frame k is matched against frame k - 1 ACROSS sub-batch
 // boundaries and across calls (the last frame of a call is carried over), i.e. a real sequence.  How many streams there are, and
 // with them P_eff, follows from the hardware queues of the process (orbfe_pipe_plan.h).  The same header has the second way to
-// cut a call over the streams, by stage instead of by sub-batch (lanes), which run_device takes where its rule and the
-// pipeline's lane mode say so.
+// cut a call over the streams, by stage instead of by sub-batch (lanes), taken where its rule and the pipeline's lane mode say so.
+//
+// What one call enqueues -- which stream every piece runs on, which events it waits for and records, in both cuts -- is stated
+// once, in orbfe_pipe_graph.h, without a device call; run_device here walks it with the HIP and library calls (PipeCall).
 //
 // Host code only: every kernel is launched through the extractor / matcher entry points of this library.
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <utility>
@@ -19,7 +22,7 @@
 #include "orbfe_common.h"
 #include "orbfe_kernels.h"
 #include "orbfe_matcher.h"
-#include "orbfe_pipe_plan.h"
+#include "orbfe_pipe_graph.h"
 
 // Streams outlive their pipeline.  Which hardware queue the runtime gives a new stream depends on every stream the process has
 // made and destroyed before, and a pipeline whose copy, kernel and side streams landed on queues of their own runs its host
@@ -40,6 +43,8 @@ static hipStream_t take_spare_stream(int device)
     return nullptr;
 }
 
+static_assert(sizeof(orbfe_keypoint) == ORB_PIPE_KEYPOINT_BYTES && ORBFE_PIPE_CONTINUE == ORB_PIPE_CONTINUE, "orbfe_pipe_graph.h restates these");
+
 struct orbfe_pipeline {
     orbfe_params prm;
     int device = 0;
@@ -56,69 +61,52 @@ struct orbfe_pipeline {
     std::vector<hipStream_t> pool;
     hipStream_t stream_of(int pipe) const { return pool[(size_t)(cur.first + cur.stream_of_pipe[pipe])]; }
     hipStream_t side() const { return cur.side ? pool[(size_t)cur.side_index] : nullptr; }
-    std::vector<char> ev_end_valid;
-    std::vector<hipEvent_t> ev_end;    // per pipe: behind the pipe's last launch of the most recent call
-    std::vector<hipEvent_t> ev_ext;    // per sub-batch index: extraction finished (most recent call)
-    std::vector<hipEvent_t> ev_match;  // per sub-batch index: matcher finished (most recent call)
-    std::vector<char> ev_match_valid;
-    std::vector<char> ev_ext_valid;
-    // the output slices the events of index j stand for (keypoint block, descriptor block, counts): a later call that lays its
-    // sub-batches over other addresses (shifted base pointer, another call size) is ordered by ADDRESS, not by index
-    struct Slice { const char *k = nullptr, *d = nullptr, *n = nullptr; size_t kb = 0, db = 0, nb = 0; };
-    std::vector<Slice> ev_slice;
+
+    // ---- the call graph (orbfe_pipe_graph.h): its state, the events its {kind, index} pairs name, what chooses its route
+    OrbPipeState g;
     hipEvent_t ev_fork = nullptr;
-    // seq[i] = i - 1: qframe = seq + q0 + 1 (q0, q0 + 1, ...), tframe = seq + q0 (q0 - 1, q0, ...)
-    int32_t *d_seq = nullptr;
-    int seq_len = 0;
-    // the last frame of the previous call (keypoints, descriptors, count): two slots, written alternately
-    orbfe_keypoint *d_ckps[2] = {nullptr, nullptr};
-    uint8_t *d_cdesc[2] = {nullptr, nullptr};
-    int32_t *d_cn[2] = {nullptr, nullptr};
-    hipEvent_t ev_carry[2] = {nullptr, nullptr};
-    hipEvent_t ev_m0[2] = {nullptr, nullptr};   // behind the frame-0 match of a call that READ carry slot k (recorded on that call's pipe)
-    bool m0_valid[2] = {false, false};
-    bool carry_written[2] = {false, false};
-    int carry_cur = 0;          // slot the NEXT call reads
-    bool have_carry = false;
-    // where the carried frame was copied FROM (the caller's blocks of the previous call): a sub-batch of the next call that
-    // writes over these addresses waits for the copy, the others do not (no drain at the call boundary)
-    const void *carry_src[3] = {nullptr, nullptr, nullptr};
-    size_t carry_src_bytes[3] = {0, 0, 0};
-    bool joined = true;
-    int rot = 0;                // pipe of sub-batch 0 of the next call: consecutive short calls take turns on the pipes
-    int host_pipes = 1;         // pipes the host entry point deals its chunks to (orbfe_pipeline_set_host_pipes)
+    std::vector<hipEvent_t> ev_ext, ev_match;   // per sub-batch index
+    std::vector<hipEvent_t> ev_end;             // per pipe
+    hipEvent_t ev_carry[2] = {nullptr, nullptr}, ev_m0[2] = {nullptr, nullptr};   // per carry slot
     // lanes (orbfe_pipe_plan.h): -1 automatic, 0 never, 1 wherever the rule allows them (orbfe_internal_pipeline_set_lanes)
     int lane_mode = -1;
     int lane_sets = 0;          // buffer sets of a lane call; 0: ORBFE_PIPE_LANE_SETS
     int lane_place = -1;        // 0: blur behind the pyramid on kernel stream 0, matcher on the side stream; 1: blur on the side
                                 // stream, matcher behind the descriptor on kernel stream 2 (where chains have both); -1: ORBFE_PIPE_LANE_PLACE
-    int lane_rot = 0;           // buffer set of sub-batch 0 of the next lane call
-    hipStream_t kernel_stream(int i) const { return pool[(size_t)(cur.first + i)]; }
-    // host entry point (orbfe_pipeline_extract_match): device input / output sets, copy streams
+    // seq[i] = i - 1: qframe = seq + q0 + 1 (q0, q0 + 1, ...), tframe = seq + q0 (q0 - 1, q0, ...)
+    DevBuf d_seq;
+    int seq_len = 0;
+
+    // ---- the carry slots: the last frame of the previous call (keypoints, descriptors, count)
+    DevBuf d_ckps[2], d_cdesc[2], d_cn[2];
+
+    // ---- host entry point (orbfe_pipeline_extract_match): device input / output sets, copy streams
+    int host_pipes = 1;         // pipes the host entry point deals its chunks to (orbfe_pipeline_set_host_pipes)
     static const int NSETS = 3;
-    uint8_t *d_in[NSETS] = {nullptr, nullptr, nullptr};
-    orbfe_keypoint *d_okps[NSETS] = {nullptr, nullptr, nullptr};
-    uint8_t *d_odesc[NSETS] = {nullptr, nullptr, nullptr};
-    int32_t *d_on[NSETS] = {nullptr, nullptr, nullptr}, *d_om[NSETS] = {nullptr, nullptr, nullptr}, *d_onm[NSETS] = {nullptr, nullptr, nullptr};
-    size_t in_bytes = 0;
-    int out_frames = 0;
+    struct HostSet {
+        DevBuf in, kps, desc, n, match, nmatch;
+        hipEvent_t ev_out = nullptr;   // the set's results have left it
+    } host[NSETS];
     hipStream_t s_in() const { return pool[0]; }   // (with a plan that has copy streams)
     hipStream_t s_out() const { return pool[1]; }
-    hipEvent_t ev_out[NSETS] = {nullptr, nullptr, nullptr};
 };
+
+static orbfe_status drain_streams(orbfe_pipeline *pl)
+{
+    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
+    return ORBFE_OK;
+}
+
+static hipError_t make_event(hipEvent_t *e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }
 
 static orbfe_status ensure_events(orbfe_pipeline *pl, int nsub)
 {
-    while ((int)pl->ev_ext.size() < nsub) {
-        hipEvent_t a = nullptr, b = nullptr;
-        ORBFE_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-        pl->ev_ext.push_back(a);
-        ORBFE_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-        pl->ev_match.push_back(b);
-        pl->ev_match_valid.push_back(0);
-        pl->ev_ext_valid.push_back(0);
-        pl->ev_slice.push_back(orbfe_pipeline::Slice());
-    }
+    for (std::vector<hipEvent_t> *v : {&pl->ev_ext, &pl->ev_match})
+        while ((int)v->size() < nsub) {
+            hipEvent_t e = nullptr;
+            ORBFE_HIP(make_event(&e));
+            v->push_back(e);
+        }
     return ORBFE_OK;
 }
 
@@ -126,15 +114,14 @@ static orbfe_status ensure_seq(orbfe_pipeline *pl, int nframes)
 {
     if (nframes + 1 <= pl->seq_len) return ORBFE_OK;
     // the index table is about to be replaced: no launch of an earlier call may still read it
-    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
-    if (pl->d_seq) ORBFE_HIP(hipFree(pl->d_seq));
-    pl->d_seq = nullptr;
+    const orbfe_status s = drain_streams(pl);
+    if (s != ORBFE_OK) return s;
     pl->seq_len = 0;
     const int len = std::max(nframes + 1, 4096);
     std::vector<int32_t> h((size_t)len);
     for (int i = 0; i < len; ++i) h[(size_t)i] = i - 1;
-    ORBFE_HIP(hipMalloc((void **)&pl->d_seq, (size_t)len * sizeof(int32_t)));
-    ORBFE_HIP(hipMemcpy(pl->d_seq, h.data(), (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice));
+    ORBFE_HIP(pl->d_seq.ensure((size_t)len * sizeof(int32_t)));
+    ORBFE_HIP(hipMemcpy(pl->d_seq.p, h.data(), (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice));
     pl->seq_len = len;
     return ORBFE_OK;
 }
@@ -147,27 +134,17 @@ extern "C" void orbfe_pipeline_destroy(orbfe_pipeline *pl)
         if (s) (void)hipStreamSynchronize(s);
     for (orbfe_handle *h : pl->ext) orbfe_destroy(h);
     for (orbfe_matcher *m : pl->mat) orbfe_matcher_destroy(m);
-    for (hipEvent_t e : pl->ev_end)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl->ev_ext)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl->ev_match)
-        if (e) (void)hipEventDestroy(e);
-    if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
-    for (int k = 0; k < 2; ++k) {
-        if (pl->ev_carry[k]) (void)hipEventDestroy(pl->ev_carry[k]);
-        if (pl->ev_m0[k]) (void)hipEventDestroy(pl->ev_m0[k]);
-        if (pl->d_ckps[k]) (void)hipFree(pl->d_ckps[k]);
-        if (pl->d_cdesc[k]) (void)hipFree(pl->d_cdesc[k]);
-        if (pl->d_cn[k]) (void)hipFree(pl->d_cn[k]);
+    std::vector<hipEvent_t> ev = {pl->ev_fork, pl->ev_carry[0], pl->ev_carry[1], pl->ev_m0[0], pl->ev_m0[1]};
+    for (const std::vector<hipEvent_t> *v : {&pl->ev_ext, &pl->ev_match, &pl->ev_end}) ev.insert(ev.end(), v->begin(), v->end());
+    for (orbfe_pipeline::HostSet &h : pl->host) {
+        ev.push_back(h.ev_out);
+        for (DevBuf *b : {&h.in, &h.kps, &h.desc, &h.n, &h.match, &h.nmatch}) b->release();
     }
-    if (pl->d_seq) (void)hipFree(pl->d_seq);
-    for (int k = 0; k < orbfe_pipeline::NSETS; ++k) {
-        void *bufs[] = {pl->d_in[k], pl->d_okps[k], pl->d_odesc[k], pl->d_on[k], pl->d_om[k], pl->d_onm[k]};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-        if (pl->ev_out[k]) (void)hipEventDestroy(pl->ev_out[k]);
-    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (int k = 0; k < 2; ++k)
+        for (DevBuf *b : {&pl->d_ckps[k], &pl->d_cdesc[k], &pl->d_cn[k]}) b->release();
+    pl->d_seq.release();
     {   // (drained above) last stream first, so that the next pipeline's stream i is this one's stream i
         std::lock_guard<std::mutex> lk(g_spare_mu);
         for (size_t i = pl->pool.size(); i-- > 0;)
@@ -184,7 +161,8 @@ static orbfe_status apply_plan(orbfe_pipeline *pl, const OrbPipePlan &plan)
     const bool same = pl->cur_valid && pl->cur.copies == plan.copies && pl->cur.S == plan.S && pl->cur.side == plan.side &&
                       pl->cur.P_eff == plan.P_eff;
     if (same) return ORBFE_OK;
-    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
+    const orbfe_status ds = drain_streams(pl);
+    if (ds != ORBFE_OK) return ds;
     while ((int)pl->pool.size() < plan.nstreams) {
         hipStream_t st = take_spare_stream(pl->device);
         if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { orbfe_set_error("pipeline stream creation failed"); return ORBFE_ERR_HIP; }
@@ -192,7 +170,7 @@ static orbfe_status apply_plan(orbfe_pipeline *pl, const OrbPipePlan &plan)
     }
     pl->cur = plan;
     pl->cur_valid = true;
-    pl->rot %= plan.P_eff;
+    pl->g.rot %= plan.P_eff;
     for (int i = 0; i < pl->P && i < (int)pl->ext.size(); ++i) {
         const orbfe_status s = orbfe_internal_set_side_stream(pl->ext[(size_t)i], (void *)pl->side());
         if (s != ORBFE_OK) return s;
@@ -239,11 +217,13 @@ extern "C" orbfe_status orbfe_internal_pipeline_create_queues(const orbfe_params
         const orbfe_status s = apply_plan(pl, plan);
         if (s != ORBFE_OK) return fail(s);
     }
-    for (int i = 0; i < npipes; ++i) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { orbfe_set_error("pipeline event creation failed"); return fail(ORBFE_ERR_HIP); }
-        pl->ev_end.push_back(e);
-        pl->ev_end_valid.push_back(0);
+    pl->ev_end.assign((size_t)npipes, nullptr);
+    bool events = make_event(&pl->ev_fork) == hipSuccess;
+    for (hipEvent_t &e : pl->ev_end) events = events && make_event(&e) == hipSuccess;
+    for (int k = 0; k < 2; ++k) events = events && make_event(&pl->ev_carry[k]) == hipSuccess && make_event(&pl->ev_m0[k]) == hipSuccess;
+    if (!events) {
+        orbfe_set_error("pipeline event creation failed");
+        return fail(ORBFE_ERR_HIP);
     }
     for (int i = 0; i < npipes; ++i) {
         orbfe_handle *h = nullptr;
@@ -265,17 +245,13 @@ extern "C" orbfe_status orbfe_internal_pipeline_create_queues(const orbfe_params
             for (int l = 0; l < pl->prm.nlevels; ++l) worst += std::max(feat[l] + 2, 4 * ORBFE_MAX_ROOTS);
         pl->cap = std::max(orbfe_keypoint_capacity(pl->ext[0]), (worst + 63) & ~63);
     }
-    if (hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming) != hipSuccess) { orbfe_set_error("pipeline event creation failed"); return fail(ORBFE_ERR_HIP); }
     for (int k = 0; k < 2; ++k) {
-        if (hipEventCreateWithFlags(&pl->ev_carry[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&pl->ev_m0[k], hipEventDisableTiming) != hipSuccess ||
-            hipMalloc((void **)&pl->d_ckps[k], (size_t)pl->cap * sizeof(orbfe_keypoint)) != hipSuccess ||
-            hipMalloc((void **)&pl->d_cdesc[k], (size_t)pl->cap * 32) != hipSuccess ||
-            hipMalloc((void **)&pl->d_cn[k], 64) != hipSuccess) {
+        if (pl->d_ckps[k].ensure((size_t)pl->cap * sizeof(orbfe_keypoint)) != hipSuccess || pl->d_cdesc[k].ensure((size_t)pl->cap * 32) != hipSuccess ||
+            pl->d_cn[k].ensure(64) != hipSuccess) {
             orbfe_set_error("pipeline carry buffers: %s", hipGetErrorString(hipGetLastError()));
             return fail(ORBFE_ERR_NOMEM);
         }
-        (void)hipMemset(pl->d_cn[k], 0, 64);
+        (void)hipMemset(pl->d_cn[k].p, 0, 64);
     }
     orbfe_status s = ensure_seq(pl, 4095);
     if (s != ORBFE_OK) return fail(s);
@@ -368,7 +344,7 @@ extern "C" orbfe_status orbfe_pipeline_set_host_pipes(orbfe_pipeline *pl, int32_
 extern "C" orbfe_status orbfe_pipeline_reset_sequence(orbfe_pipeline *pl)
 {
     if (!pl) return ORBFE_ERR_ARG;
-    pl->have_carry = false;
+    pl->g.new_sequence();
     return ORBFE_OK;
 }
 
@@ -377,8 +353,7 @@ extern "C" orbfe_status orbfe_pipeline_join(orbfe_pipeline *pl, void *stream)
     if (!pl) return ORBFE_ERR_ARG;
     DeviceGuard g(pl->device);
     for (int p = 0; p < pl->P; ++p)
-        if (pl->ev_end_valid[(size_t)p]) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, pl->ev_end[(size_t)p], 0));
-    pl->joined = true;
+        if (pl->g.end_valid[p]) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, pl->ev_end[(size_t)p], 0));
     return ORBFE_OK;
 }
 
@@ -386,8 +361,7 @@ extern "C" orbfe_status orbfe_pipeline_synchronize(orbfe_pipeline *pl)
 {
     if (!pl) return ORBFE_ERR_ARG;
     DeviceGuard g(pl->device);
-    for (hipStream_t s : pl->pool) ORBFE_HIP(hipStreamSynchronize(s));
-    return ORBFE_OK;
+    return drain_streams(pl);
 }
 
 extern "C" orbfe_status orbfe_pipeline_get_overflow(orbfe_pipeline *pl, int32_t *flags)
@@ -403,183 +377,103 @@ extern "C" orbfe_status orbfe_pipeline_get_overflow(orbfe_pipeline *pl, int32_t 
     return ORBFE_OK;
 }
 
-// one call on the pipeline's current plan (apply_plan): the device entry point's, or the host entry point's with its copy streams
-static orbfe_status run_device(orbfe_pipeline *pl, const uint8_t *d_gray, int32_t nframes, int32_t w, int32_t ht, int32_t stride,
-                               size_t frame_stride, orbfe_keypoint *d_kps, uint8_t *d_desc, int32_t cap, int32_t *d_n_out, int32_t *d_match,
-                               int32_t *d_nmatches, float nnratio, int32_t th, int32_t check_ori, int32_t flags, void *stream)
-{
-    const int F = pl->F;
-    const int nsub = (nframes + F - 1) / F;
-    // Chains: sub-batch j runs on pipe (rot + j) mod P_eff, every kernel stream gets its share.  Lanes: the streams carry one stage
-    // group each and sub-batch j takes buffer set (handle) (lane_rot + j) mod sets.
-    const OrbPipeLanes lr = orb_pipe_lanes(pl->cur, nsub, pl->lane_sets);
-    const bool lanes = lr.lanes && (pl->lane_mode < 0 ? ORBFE_PIPE_LANES_AUTO != 0 : pl->lane_mode != 0);
-    const int P = lanes ? lr.sets : pl->cur.P_eff;
-    const int rot0 = lanes ? pl->lane_rot % P : pl->rot;
-    // the streams of a lane call: pyramid, FAST, quadtree + descriptor, blur; and the matcher's
-    void *lane[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t lane_match = nullptr;
-    if (lanes) {
-        const int place = pl->lane_place < 0 ? ORBFE_PIPE_LANE_PLACE : pl->lane_place;
-        lane[0] = (void *)pl->kernel_stream(0);
-        lane[1] = (void *)pl->kernel_stream(1);
-        lane[2] = (void *)pl->kernel_stream(2);
-        lane[3] = place ? (void *)pl->side() : lane[0];
-        lane_match = place ? pl->kernel_stream(2) : pl->side();
+// The arguments of one call and what the graph's operations (orbfe_pipe_graph.h) are on the device: streams of the pool, events of
+// the pipeline, the extractor and matcher handles' entry points, copies into the carry slots.
+struct PipeCall {
+    orbfe_pipeline *pl;
+    const uint8_t *d_gray;
+    int32_t w, ht, stride;
+    size_t frame_stride;
+    orbfe_keypoint *d_kps;
+    uint8_t *d_desc;
+    int32_t cap;
+    int32_t *d_n_out, *d_match, *d_nmatches;
+    float nnratio;
+    int32_t th, check_ori;
+    hipStream_t caller;
+
+    hipStream_t stream(int32_t s) const { return s == ORB_PIPE_CALLER ? caller : pl->pool[(size_t)s]; }
+    hipEvent_t event(OrbPipeEvent e) const
+    {
+        switch (e.kind) {
+        case ORB_EV_EXT: return pl->ev_ext[(size_t)e.index];
+        case ORB_EV_MATCH: return pl->ev_match[(size_t)e.index];
+        case ORB_EV_CARRY: return pl->ev_carry[e.index];
+        case ORB_EV_M0: return pl->ev_m0[e.index];
+        case ORB_EV_END: return pl->ev_end[(size_t)e.index];
+        default: return pl->ev_fork;
+        }
     }
-    const int nend = lanes ? ORBFE_PIPE_LANE_STREAMS + 1 : P;   // streams that carry work of this call, the side stream last
-    auto end_stream = [&](int i) { return !lanes ? pl->stream_of(i) : (i < ORBFE_PIPE_LANE_STREAMS ? pl->kernel_stream(i) : pl->side()); };
+    const int32_t *seq() const { return pl->d_seq.as<int32_t>(); }
+    orbfe_status wait(int32_t s, OrbPipeEvent e) const
+    {
+        ORBFE_HIP(hipStreamWaitEvent(stream(s), event(e), 0));
+        return ORBFE_OK;
+    }
+    orbfe_status record(int32_t s, OrbPipeEvent e) const
+    {
+        ORBFE_HIP(hipEventRecord(event(e), stream(s)));
+        return ORBFE_OK;
+    }
+    orbfe_status extract(int32_t h, int32_t lo, int32_t nf, const OrbPipeRoute &r) const
+    {
+        const uint8_t *gray = d_gray + (size_t)lo * frame_stride;
+        orbfe_keypoint *kps = d_kps + (size_t)lo * cap;
+        uint8_t *desc = d_desc + (size_t)lo * cap * 32;
+        if (!r.lanes)
+            return orbfe_extract_batch_device(pl->ext[(size_t)h], gray, nf, w, ht, stride, frame_stride, kps, desc, cap, d_n_out + lo,
+                                              (void *)stream(r.start_of[h]));
+        void *lane[4] = {(void *)stream(r.lane[0]), (void *)stream(r.lane[1]), (void *)stream(r.lane[2]), (void *)stream(r.lane[3])};
+        return orbfe_internal_extract_batch_lanes(pl->ext[(size_t)h], gray, nf, w, ht, stride, frame_stride, kps, desc, cap, d_n_out + lo, lane);
+    }
+    orbfe_status match(int32_t h, int32_t s, int32_t q0, int32_t np) const
+    {
+        return orbfe_match_bf_blocks_device(pl->mat[(size_t)h], d_kps, d_desc, d_n_out, d_kps, d_desc, d_n_out, cap, seq() + q0 + 1, seq() + q0, np, nnratio,
+                                            th, check_ori, d_match + (size_t)q0 * cap, d_nmatches + q0, (void *)stream(s));
+    }
+    orbfe_status match_carry(int32_t h, int32_t s, int32_t slot) const   // query = frame 0 of this call, train = frame 0 of the carry block
+    {
+        return orbfe_match_bf_blocks_device(pl->mat[(size_t)h], d_kps, d_desc, d_n_out, pl->d_ckps[slot].as<orbfe_keypoint>(), pl->d_cdesc[slot].as<uint8_t>(),
+                                            pl->d_cn[slot].as<int32_t>(), cap, seq() + 1, seq() + 1, 1, nnratio, th, check_ori, d_match, d_nmatches,
+                                            (void *)stream(s));
+    }
+    orbfe_status clear_row0(int32_t s) const
+    {
+        ORBFE_HIP(hipMemsetAsync(d_match, 0xFF, (size_t)cap * sizeof(int32_t), stream(s)));
+        ORBFE_HIP(hipMemsetAsync(d_nmatches, 0, sizeof(int32_t), stream(s)));
+        return ORBFE_OK;
+    }
+    orbfe_status carry_copy(int32_t s, int32_t slot, int32_t last_frame) const
+    {
+        const size_t last = (size_t)last_frame, slots = (size_t)std::min(cap, pl->cap);
+        ORBFE_HIP(hipMemcpyAsync(pl->d_ckps[slot].p, d_kps + last * cap, slots * sizeof(orbfe_keypoint), hipMemcpyDeviceToDevice, stream(s)));
+        ORBFE_HIP(hipMemcpyAsync(pl->d_cdesc[slot].p, d_desc + last * cap * 32, slots * 32, hipMemcpyDeviceToDevice, stream(s)));
+        ORBFE_HIP(hipMemcpyAsync(pl->d_cn[slot].p, d_n_out + last, sizeof(int32_t), hipMemcpyDeviceToDevice, stream(s)));
+        return ORBFE_OK;
+    }
+};
+
+// One call on the pipeline's current plan (apply_plan): the device entry point's, or the host entry point's with its copy streams
+// (`first_pipe` >= 0: the pipe of its one-sub-batch chunk)
+static orbfe_status run_device(orbfe_pipeline *pl, const PipeCall &c, int32_t nframes, int32_t flags, int32_t first_pipe = -1)
+{
+    const int nsub = (nframes + pl->F - 1) / pl->F;
     orbfe_status s = ensure_events(pl, nsub + 1);
     if (s != ORBFE_OK) return s;
     s = ensure_seq(pl, nframes);
     if (s != ORBFE_OK) return s;
-    hipStream_t cs = (hipStream_t)stream;
-    const bool match = d_match != nullptr;
-    const bool cont = (flags & ORBFE_PIPE_CONTINUE) != 0 && pl->have_carry && match;
-    const int rd = pl->carry_cur, wr = pl->carry_cur ^ 1;
-
-    // fork: the pipes start behind whatever the caller's stream holds (the producer of d_gray, the consumer of the output
-    // blocks of an earlier call)
-    ORBFE_HIP(hipEventRecord(pl->ev_fork, cs));
-    for (int i = 0; i < nend; ++i) ORBFE_HIP(hipStreamWaitEvent(end_stream(i), pl->ev_fork, 0));
-    // An error in the middle of the loop leaves launches of this call in flight and the event / carry bookkeeping half
-    // updated: drain the pipes and start the sequence over (the next call has no predecessor frame), then report.
-    auto bail = [&](orbfe_status e) {
+    const OrbPipeRoute route(pl->cur, orb_pipe_lanes(pl->cur, nsub, pl->lane_sets), pl->lane_mode, pl->lane_place, first_pipe, pl->g);
+    const OrbPipeBlocks out{(uintptr_t)c.d_kps, (uintptr_t)c.d_desc, (uintptr_t)c.d_n_out, c.cap};
+    const OrbPipeCall call{route, out, pl->F, nframes, c.d_match != nullptr, flags};
+    s = orb_pipe_call(pl->g, call, c);
+    if (s != ORBFE_OK) {
+        // launches of this call are in flight and the ledger is half updated: drain the pipes and start the sequence over (the next
+        // call has no predecessor frame), then report
         for (hipStream_t x : pl->pool) (void)hipStreamSynchronize(x);
-        pl->have_carry = false;
-        pl->m0_valid[0] = pl->m0_valid[1] = false;
-        pl->joined = true;
-        return e;
-    };
-    auto overlaps = [](const void *a, size_t na, const void *b, size_t nb) {
-        const char *pa = (const char *)a, *pb = (const char *)b;
-        return a && b && pa < pb + nb && pb < pa + na;
-    };
-
-    for (int j = 0; j < nsub; ++j) {
-        const int p = (rot0 + j) % P;
-        // st: where the extraction starts (what orders it is waited for there), sx: where it ends, sm: the matcher's stream
-        hipStream_t st = lanes ? (hipStream_t)lane[0] : pl->stream_of(p);
-        hipStream_t sx = lanes ? (hipStream_t)lane[2] : st, sm = lanes ? lane_match : st;
-        const int lo = j * F, nf = std::min(F, nframes - lo);
-        // The output blocks may be the ones of the previous call (a host that re-uses its buffers), and the pipes take turns: what
-        // the PREVIOUS call did with slices j happened on other pipes' streams.  This sub-batch overwrites them only after that
-        // call's extraction of sub-batch j (write after write), its matcher of sub-batch j (queries) and its matcher of
-        // sub-batch j + 1 (whose first pair reads the last frame of slice j) have finished.  (Events of finished work cost nothing.)
-        {
-            const char *ok = (const char *)(d_kps + (size_t)lo * cap), *od = (const char *)(d_desc + (size_t)lo * cap * 32), *on = (const char *)(d_n_out + lo);
-            const size_t okb = (size_t)nf * cap * sizeof(orbfe_keypoint), odb = (size_t)nf * cap * 32, onb = (size_t)nf * sizeof(int32_t);
-            auto wait_index = [&](size_t i) -> hipError_t {   // everything that wrote or read the slices recorded under index i
-                hipError_t e = hipSuccess;
-                if (pl->ev_ext_valid[i]) e = hipStreamWaitEvent(st, pl->ev_ext[i], 0);
-                if (e == hipSuccess && pl->ev_match_valid[i]) e = hipStreamWaitEvent(st, pl->ev_match[i], 0);
-                if (e == hipSuccess && i + 1 < pl->ev_match_valid.size() && pl->ev_match_valid[i + 1]) e = hipStreamWaitEvent(st, pl->ev_match[i + 1], 0);
-                return e;
-            };
-            // index j (its events are about to be re-recorded), and every other index whose recorded slices overlap this sub-batch's:
-            // with the usual re-use of the same buffers and call size that is index j alone
-            ORBFE_HIP(wait_index((size_t)j));
-            for (size_t i = 0; i < pl->ev_slice.size(); ++i) {
-                const orbfe_pipeline::Slice &si = pl->ev_slice[i];
-                if ((int)i != j && si.k && (overlaps(si.k, si.kb, ok, okb) || overlaps(si.d, si.db, od, odb) || overlaps(si.n, si.nb, on, onb)))
-                    ORBFE_HIP(wait_index(i));
-            }
-        }
-        // ... and the copy of the previous call's last frame into the carry slot must have read it before this sub-batch
-        // writes over it (only the sub-batch whose output slices cover those addresses waits: no drain at the call boundary)
-        if (pl->have_carry &&
-            (overlaps(pl->carry_src[0], pl->carry_src_bytes[0], d_kps + (size_t)lo * cap, (size_t)nf * cap * sizeof(orbfe_keypoint)) ||
-             overlaps(pl->carry_src[1], pl->carry_src_bytes[1], d_desc + (size_t)lo * cap * 32, (size_t)nf * cap * 32) ||
-             overlaps(pl->carry_src[2], pl->carry_src_bytes[2], d_n_out + lo, (size_t)nf * sizeof(int32_t))))
-            ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_carry[rd], 0));
-        if (lanes)
-            s = orbfe_internal_extract_batch_lanes(pl->ext[(size_t)p], d_gray + (size_t)lo * frame_stride, nf, w, ht, stride, frame_stride,
-                                                   d_kps + (size_t)lo * cap, d_desc + (size_t)lo * cap * 32, cap, d_n_out + lo, lane);
-        else
-            s = orbfe_extract_batch_device(pl->ext[(size_t)p], d_gray + (size_t)lo * frame_stride, nf, w, ht, stride, frame_stride,
-                                           d_kps + (size_t)lo * cap, d_desc + (size_t)lo * cap * 32, cap, d_n_out + lo, (void *)st);
-        if (s != ORBFE_OK) return bail(s);
-        ORBFE_HIP(hipEventRecord(pl->ev_ext[(size_t)j], sx));
-        pl->ev_ext_valid[(size_t)j] = 1;
-        {
-            orbfe_pipeline::Slice &sj = pl->ev_slice[(size_t)j];
-            sj.k = (const char *)(d_kps + (size_t)lo * cap); sj.kb = (size_t)nf * cap * sizeof(orbfe_keypoint);
-            sj.d = (const char *)(d_desc + (size_t)lo * cap * 32); sj.db = (size_t)nf * cap * 32;
-            sj.n = (const char *)(d_n_out + lo); sj.nb = (size_t)nf * sizeof(int32_t);
-        }
-        if (!match) continue;
-        // (lanes: the matcher's writes into the match rows follow the previous call's through this sub-batch's extraction, which
-        // waited for them above)
-        if (sm != sx) ORBFE_HIP(hipStreamWaitEvent(sm, pl->ev_ext[(size_t)j], 0));
-        if (j > 0) ORBFE_HIP(hipStreamWaitEvent(sm, pl->ev_ext[(size_t)j - 1], 0));   // frame lo - 1 comes from the neighbour pipe
-        const int q0 = lo == 0 ? 1 : lo;
-        const int np = lo + nf - q0;
-        if (np > 0) {
-            s = orbfe_match_bf_blocks_device(pl->mat[(size_t)p], d_kps, d_desc, d_n_out, d_kps, d_desc, d_n_out, cap, pl->d_seq + q0 + 1,
-                                             pl->d_seq + q0, np, nnratio, th, check_ori, d_match + (size_t)q0 * cap, d_nmatches + q0,
-                                             (void *)sm);
-            if (s != ORBFE_OK) return bail(s);
-        }
-        if (lo == 0) {
-            if (cont) {
-                ORBFE_HIP(hipStreamWaitEvent(sm, pl->ev_carry[rd], 0));
-                // query = frame 0 of this call, train = the carried frame (frame 0 of the carry block)
-                s = orbfe_match_bf_blocks_device(pl->mat[(size_t)p], d_kps, d_desc, d_n_out, pl->d_ckps[rd], pl->d_cdesc[rd], pl->d_cn[rd], cap,
-                                                 pl->d_seq + 1, pl->d_seq + 1, 1, nnratio, th, check_ori, d_match, d_nmatches, (void *)sm);
-                if (s != ORBFE_OK) return bail(s);
-                ORBFE_HIP(hipEventRecord(pl->ev_m0[rd], sm));   // slot rd has been read: the NEXT call may write it
-                pl->m0_valid[rd] = true;
-            } else {  // the first frame of a sequence has no predecessor
-                ORBFE_HIP(hipMemsetAsync(d_match, 0xFF, (size_t)cap * sizeof(int32_t), sm));
-                ORBFE_HIP(hipMemsetAsync(d_nmatches, 0, sizeof(int32_t), sm));
-            }
-        }
-        ORBFE_HIP(hipEventRecord(pl->ev_match[(size_t)j], sm));
-        pl->ev_match_valid[(size_t)j] = 1;
+        pl->g.reset();
+        return s;
     }
-    // (the events of sub-batch indices this call did not use keep their last record: a later, longer call still orders itself
-    // behind whatever touched those slices last)
-
-    // carry: the last frame of this call, for the first frame of the next one.  Slot `wr` was read by the PREVIOUS call's
-    // frame-0 match, on whatever pipe that call's sub-batch 0 ran (the pipes take turns): the copy waits for that match's own
-    // event.
-    {
-        const int jl = nsub - 1;
-        // (lanes: on the matcher's stream, behind the last sub-batch's extraction on the tail stream)
-        hipStream_t st = lanes ? lane_match : pl->stream_of((rot0 + jl) % P);
-        if (lanes && st != (hipStream_t)lane[2]) ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_ext[(size_t)jl], 0));
-        const size_t last = (size_t)nframes - 1;
-        if (pl->m0_valid[wr]) {
-            ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_m0[wr], 0));
-            pl->m0_valid[wr] = false;
-        }
-        // ... and behind the previous WRITER of the slot (two calls ago, possibly on another pipe's stream): calls without a frame-0
-        // match (extract only, no CONTINUE) record no ev_m0, and nothing else would order the two copies
-        if (pl->carry_written[wr]) ORBFE_HIP(hipStreamWaitEvent(st, pl->ev_carry[wr], 0));
-        ORBFE_HIP(hipMemcpyAsync(pl->d_ckps[wr], d_kps + last * cap, (size_t)std::min(cap, pl->cap) * sizeof(orbfe_keypoint),
-                                 hipMemcpyDeviceToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(pl->d_cdesc[wr], d_desc + last * cap * 32, (size_t)std::min(cap, pl->cap) * 32, hipMemcpyDeviceToDevice, st));
-        ORBFE_HIP(hipMemcpyAsync(pl->d_cn[wr], d_n_out + last, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        ORBFE_HIP(hipEventRecord(pl->ev_carry[wr], st));
-        pl->carry_written[wr] = true;
-        pl->carry_cur = wr;
-        pl->have_carry = true;
-        pl->carry_src[0] = d_kps + last * cap;
-        pl->carry_src_bytes[0] = (size_t)std::min(cap, pl->cap) * sizeof(orbfe_keypoint);
-        pl->carry_src[1] = d_desc + last * cap * 32;
-        pl->carry_src_bytes[1] = (size_t)std::min(cap, pl->cap) * 32;
-        pl->carry_src[2] = d_n_out + last;
-        pl->carry_src_bytes[2] = sizeof(int32_t);
-    }
-    // every stream that carried work of this call (lanes: the side stream too; the rule has P > 3, so there is a fourth event)
-    for (int i = 0; i < nend; ++i) {
-        ORBFE_HIP(hipEventRecord(pl->ev_end[(size_t)i], end_stream(i)));
-        pl->ev_end_valid[(size_t)i] = 1;
-    }
-    pl->joined = false;
-    if (lanes) pl->lane_rot = (rot0 + nsub) % P;
-    else pl->rot = (pl->rot + nsub) % P;
-    if (!(flags & ORBFE_PIPE_NO_JOIN)) return orbfe_pipeline_join(pl, stream);
+    if (!(flags & ORBFE_PIPE_NO_JOIN)) return orbfe_pipeline_join(pl, (void *)c.caller);
     return ORBFE_OK;
 }
 
@@ -598,8 +492,8 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
     if (!orb_pipe_plan(pl->P, pl->Q, false, &plan)) return ORBFE_ERR_ARG;
     const orbfe_status s = apply_plan(pl, plan);
     if (s != ORBFE_OK) return s;
-    return run_device(pl, d_gray, nframes, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out, d_match, d_nmatches, nnratio, th, check_ori,
-                      flags, stream);
+    const PipeCall c{pl, d_gray, w, ht, stride, frame_stride, d_kps, d_desc, cap, d_n_out, d_match, d_nmatches, nnratio, th, check_ori, (hipStream_t)stream};
+    return run_device(pl, c, nframes, flags);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -607,26 +501,26 @@ extern "C" orbfe_status orbfe_pipeline_extract_match_device(orbfe_pipeline *pl, 
 // ---------------------------------------------------------------------------------------------------
 static orbfe_status ensure_host_sets(orbfe_pipeline *pl, int w, int ht)
 {
-    const size_t need = (size_t)pl->F * w * ht;
-    if (need <= pl->in_bytes && pl->out_frames == pl->F) return ORBFE_OK;
     // (measured and rejected: copy streams at the highest stream priority -- 159 k frames/s with 3 pipes, 41 k with 12)
-    for (hipStream_t st : pl->pool) ORBFE_HIP(hipStreamSynchronize(st));
     const size_t F = (size_t)pl->F, cap = (size_t)pl->cap;
-    for (int k = 0; k < orbfe_pipeline::NSETS; ++k) {
-        if (pl->d_in[k]) ORBFE_HIP(hipFree(pl->d_in[k]));
-        pl->d_in[k] = nullptr;
-        ORBFE_HIP(hipMalloc((void **)&pl->d_in[k], need + 64));
-        if (!pl->ev_out[k]) ORBFE_HIP(hipEventCreateWithFlags(&pl->ev_out[k], hipEventDisableTiming));
-        if (!pl->d_okps[k]) {
-            ORBFE_HIP(hipMalloc((void **)&pl->d_okps[k], F * cap * sizeof(orbfe_keypoint)));
-            ORBFE_HIP(hipMalloc((void **)&pl->d_odesc[k], F * cap * 32));
-            ORBFE_HIP(hipMalloc((void **)&pl->d_on[k], F * sizeof(int32_t)));
-            ORBFE_HIP(hipMalloc((void **)&pl->d_om[k], F * cap * sizeof(int32_t)));
-            ORBFE_HIP(hipMalloc((void **)&pl->d_onm[k], F * sizeof(int32_t)));
+    const size_t need[6] = {F * w * ht + 64,          F * cap * sizeof(orbfe_keypoint), F * cap * 32,
+                            F * sizeof(int32_t),      F * cap * sizeof(int32_t),        F * sizeof(int32_t)};
+    // every buffer grows on its own, so a failed allocation leaves the others what they say they are; a buffer is replaced only
+    // with nothing in flight
+    bool drained = false;
+    for (orbfe_pipeline::HostSet &h : pl->host) {
+        if (!h.ev_out) ORBFE_HIP(make_event(&h.ev_out));
+        DevBuf *const bufs[6] = {&h.in, &h.kps, &h.desc, &h.n, &h.match, &h.nmatch};
+        for (int i = 0; i < 6; ++i) {
+            if (need[i] <= bufs[i]->bytes) continue;
+            if (!drained) {
+                const orbfe_status s = drain_streams(pl);
+                if (s != ORBFE_OK) return s;
+                drained = true;
+            }
+            ORBFE_HIP(bufs[i]->ensure(need[i]));
         }
     }
-    pl->in_bytes = need;
-    pl->out_frames = pl->F;
     return ORBFE_OK;
 }
 
@@ -664,39 +558,40 @@ extern "C" orbfe_status orbfe_pipeline_extract_match(orbfe_pipeline *pl, const u
         }
     } drain{pl};
     for (int c = 0; c < nchunks; ++c) {
-        const int k = c % orbfe_pipeline::NSETS, lo = c * F, nf = std::min(F, nframes - lo);
-        // set k is free once the results of chunk c - NSETS have left it
-        if (c >= orbfe_pipeline::NSETS) ORBFE_HIP(hipStreamWaitEvent(pl->s_in(), pl->ev_out[k], 0));
+        const int lo = c * F, nf = std::min(F, nframes - lo);
+        orbfe_pipeline::HostSet &hs = pl->host[c % orbfe_pipeline::NSETS];
+        // the set is free once the results of chunk c - NSETS have left it
+        if (c >= orbfe_pipeline::NSETS) ORBFE_HIP(hipStreamWaitEvent(pl->s_in(), hs.ev_out, 0));
         bool contiguous = stride == w;
         for (int f = 1; f < nf && contiguous; ++f) contiguous = grays[lo + f] == grays[lo + f - 1] + fbytes;
         if (contiguous) {
-            ORBFE_HIP(hipMemcpyAsync(pl->d_in[k], grays[lo], fbytes * nf, hipMemcpyHostToDevice, pl->s_in()));
+            ORBFE_HIP(hipMemcpyAsync(hs.in.p, grays[lo], fbytes * nf, hipMemcpyHostToDevice, pl->s_in()));
         } else {
             for (int f = 0; f < nf; ++f)
-                ORBFE_HIP(hipMemcpy2DAsync(pl->d_in[k] + fbytes * f, (size_t)w, grays[lo + f], (size_t)stride, (size_t)w, (size_t)ht,
+                ORBFE_HIP(hipMemcpy2DAsync(hs.in.as<uint8_t>() + fbytes * f, (size_t)w, grays[lo + f], (size_t)stride, (size_t)w, (size_t)ht,
                                            hipMemcpyHostToDevice, pl->s_in()));
         }
         // the pipes start behind the copy (the call forks from s_in) and are not joined: the next chunk's copy and pipes follow at once
         const int fl = ((c > 0 || (flags & ORBFE_PIPE_CONTINUE)) ? ORBFE_PIPE_CONTINUE : 0) | ORBFE_PIPE_NO_JOIN;
-        pl->rot = c % pl->cur.P_eff;   // the chunk is one sub-batch: this is its pipe
-        s = run_device(pl, pl->d_in[k], nf, w, ht, w, fbytes, pl->d_okps[k], pl->d_odesc[k], pc, pl->d_on[k], match ? pl->d_om[k] : nullptr,
-                       match ? pl->d_onm[k] : nullptr, nnratio, th, check_ori, fl, (void *)pl->s_in());
+        const PipeCall call{pl, hs.in.as<uint8_t>(), w, ht, w, fbytes, hs.kps.as<orbfe_keypoint>(), hs.desc.as<uint8_t>(), pc, hs.n.as<int32_t>(),
+                            match ? hs.match.as<int32_t>() : nullptr, match ? hs.nmatch.as<int32_t>() : nullptr, nnratio, th, check_ori, pl->s_in()};
+        s = run_device(pl, call, nf, fl, c % pl->cur.P_eff);   // the chunk is one sub-batch: this is its pipe
         if (s != ORBFE_OK) return s;
         s = orbfe_pipeline_join(pl, (void *)pl->s_out());   // everything submitted so far, i.e. this chunk and older ones
         if (s != ORBFE_OK) return s;
         // padded blocks straight into the caller's arrays (row pitch cap >= pc)
-        ORBFE_HIP(hipMemcpyAsync(n_out + lo, pl->d_on[k], (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out()));
+        ORBFE_HIP(hipMemcpyAsync(n_out + lo, hs.n.p, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out()));
         auto rows_out = [&](void *dst, const void *src, size_t elem) -> hipError_t {   // nf rows of pc elements, host pitch cap
             if (cap == pc) return hipMemcpyAsync(dst, src, (size_t)nf * pc * elem, hipMemcpyDeviceToHost, pl->s_out());   // one linear copy
             return hipMemcpy2DAsync(dst, (size_t)cap * elem, src, (size_t)pc * elem, (size_t)pc * elem, (size_t)nf, hipMemcpyDeviceToHost, pl->s_out());
         };
-        ORBFE_HIP(rows_out(kps + (size_t)lo * cap, pl->d_okps[k], sizeof(orbfe_keypoint)));
-        ORBFE_HIP(rows_out(desc + (size_t)lo * cap * 32, pl->d_odesc[k], 32));
+        ORBFE_HIP(rows_out(kps + (size_t)lo * cap, hs.kps.p, sizeof(orbfe_keypoint)));
+        ORBFE_HIP(rows_out(desc + (size_t)lo * cap * 32, hs.desc.p, 32));
         if (match) {
-            ORBFE_HIP(rows_out(match + (size_t)lo * cap, pl->d_om[k], sizeof(int32_t)));
-            ORBFE_HIP(hipMemcpyAsync(nmatches + lo, pl->d_onm[k], (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out()));
+            ORBFE_HIP(rows_out(match + (size_t)lo * cap, hs.match.p, sizeof(int32_t)));
+            ORBFE_HIP(hipMemcpyAsync(nmatches + lo, hs.nmatch.p, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, pl->s_out()));
         }
-        ORBFE_HIP(hipEventRecord(pl->ev_out[k], pl->s_out()));
+        ORBFE_HIP(hipEventRecord(hs.ev_out, pl->s_out()));
     }
     ORBFE_HIP(hipStreamSynchronize(pl->s_out()));
     int32_t ovf = 0;

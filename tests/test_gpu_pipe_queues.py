@@ -8,7 +8,9 @@ Case 1: calls of 7 frames in sub-batches of 2 (nsub = 4: with P_eff = 3 and 5 co
         last call's blocks checked, whose first match row needs the carried frame of the call before).
 Case 2: 4 x 128 frames, sub-batch 128: the size from which an extractor puts the blur on its side stream -- where the plan has one;
         where it has none the same call takes the in-stream blur.
-Both: counts, keypoints, descriptors and matches byte-identical to orbfe_extract_batch_device on ONE handle plus brute-force
+Case 3: the restart behind a failed call, in chains (16 queues, 3 pipes) and in lanes (4 queues, 5 pipes): a CONTINUE call that the
+        extractor rejects, then two more CONTINUE calls -- the first without a predecessor frame, the second with one.
+All: counts, keypoints, descriptors and matches byte-identical to orbfe_extract_batch_device on ONE handle plus brute-force
 match calls over the same frames (computed once per case)."""
 import numpy as np
 import pytest
@@ -122,6 +124,41 @@ def test_continuing_calls_into_the_same_blocks_equal_single_handle_calls(short_s
             torch.cuda.synchronize()
             _same(out, ref, 14, 21, "third unjoined call")
         assert pl.overflow() == 0
+    pl.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("queues,pipes", [(16, 3), (4, 5)])   # chains, lanes
+def test_a_failed_call_restarts_the_sequence(short_sequence, queues, pipes):
+    """A call that fails behind its fork (a frame one row taller than the pipeline was made for: the extractor of sub-batch 0 answers
+    ORBFE_ERR_SIZE before it launches anything) drains the pipes and starts the sequence over: the next CONTINUE call has no
+    predecessor frame, the one after it has."""
+    import torch
+    from orb_slam2_ssd_semantic_amd import _ffi
+    dg, cap, ref = short_sequence
+    pl = _pipeline(queues, pipes, 2)
+    st = torch.cuda.current_stream().cuda_stream
+    n, k, d, m, nm = out = _blocks(7, cap)
+
+    def call(lo, flags, h=H):
+        pl.extract_match_device(dg[lo].data_ptr(), 7, W, h, W, W * h, k.data_ptr(), d.data_ptr(), cap, n.data_ptr(), m.data_ptr(),
+                                nm.data_ptr(), flags=flags, stream=st)
+        torch.cuda.synchronize()
+
+    call(0, 0)
+    _same(out, ref, 0, 7, "first call")
+    with pytest.raises(_ffi.OrbfeError) as err:
+        call(7, pl.CONTINUE, h=H + 1)
+    assert err.value.status == _ffi.ORBFE_ERR_SIZE
+    call(7, pl.CONTINUE)
+    assert int(nm[0]) == 0 and bool((m[0] == -1).all())   # the "no predecessor" row
+    _same([t[1:] for t in out], ref, 8, 14, "call behind the failed one, rows 1..6")
+    first = [t[:1].clone() for t in out]
+    first[3], first[4] = ref[3][7:8], ref[4][7:8]         # (row 0 but for its matches)
+    _same(first, ref, 7, 8, "call behind the failed one, row 0")
+    call(14, pl.CONTINUE)
+    _same(out, ref, 14, 21, "second call behind the failed one")   # row 0: frame 14 against the carried frame 13
+    assert pl.overflow() == 0
     pl.close()
 
 
