@@ -505,11 +505,14 @@ static orbfe_status hand_off_auto_probe(orbfe_handle *h, hipStream_t st)
 // The stages of a call on a stream per stage group (orbfe_internal_extract_batch_lanes): lane[0] pyramid, lane[1] FAST, lane[2]
 // quadtree + descriptor, lane[3] blur.  pyramid -> FAST and pyramid -> blur (ev_fork), FAST -> quadtree (ev_fork2), blur ->
 // descriptor (ev_join); the descriptor is the last launch on the tail stream lane[2], so that the next call of this handle starts
-// its pyramid behind everything of this one.
+// its pyramid behind everything of this one.  The clear of FAST's survivor counts and cell flags runs on the pyramid's stream, so
+// that the FAST stream carries FAST launches and nothing else: run_batch has made lane[0] wait for ev_last of the handle's previous
+// call, behind which the last readers of those words (quadtree, taps) lie, and FAST waits for ev_fork, which follows the clear.
 static orbfe_status enqueue_lanes(orbfe_handle *h, const OrbLaunch &a, bool auto_probe, const hipStream_t *lane)
 {
     const hipStream_t sp = lane[0], sf = lane[1], st = lane[2], sb = lane[3];
     ORBFE_HIP(orbk_launch_pyramid(a, sp));
+    ORBFE_HIP(orbk_clear_fast(a, sp));
     ORBFE_HIP(hipEventRecord(h->ev_fork, sp));
     ORBFE_HIP(hipStreamWaitEvent(sf, h->ev_fork, 0));
     if (sb != sp) ORBFE_HIP(hipStreamWaitEvent(sb, h->ev_fork, 0));
@@ -546,6 +549,7 @@ static orbfe_status enqueue_single_stream(orbfe_handle *h, const OrbLaunch &a, b
     ORBFE_HIP(orbk_launch_pyramid(a, st));
     if (ev) ORBFE_HIP(hipEventRecord(ev[1], st));
     if (ov == 1) ORBFE_HIP(fork_blur());
+    ORBFE_HIP(orbk_clear_fast(a, st));
     ORBFE_HIP(orbk_launch_fast(a, st));
     if (auto_probe) {
         const orbfe_status s = hand_off_auto_probe(h, st);

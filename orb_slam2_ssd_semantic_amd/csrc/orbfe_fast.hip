@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256) FC_OCC void k_fast_map_c(const OrbPlan *__rest
 // ---------------------------------------------------------------------------------------------------
 // launchers (host)
 // ---------------------------------------------------------------------------------------------------
-static hipError_t fast_clear(const OrbLaunch &a, hipStream_t st)
+hipError_t orbk_clear_fast(const OrbLaunch &a, hipStream_t st)
 {
     // the survivor counts and, right behind them, the cell flags of this call's frames: one clear
     const int nl = a.h_plan->nlevels;
@@ -311,8 +311,6 @@ static void fast_launch_dense(Kernel kernel, const OrbLaunch &a, unsigned long l
 
 hipError_t orbk_launch_fast(const OrbLaunch &a, hipStream_t st)
 {
-    hipError_t e = fast_clear(a, st);
-    if (e != hipSuccess) return e;
     unsigned long long *const nostat = nullptr;   // the dense instantiations keep no statistics
     if (a.fast_sparse == 2)
         hipLaunchKernelGGL(k_fast_map_c, dim3((a.h_plan->nfwaves_c + 3) / 4, a.nframes), dim3(256), (size_t)a.cf_words * 16, st, a.d_plan,

@@ -71,6 +71,9 @@ hipError_t orbk_prepare_octree(int node_cap, int max_nini, int w, int h, int nce
 // dynamic LDS of the pyramid kernel for a destination level of dh rows (inline: the planner, orbfe_plan.hip, bounds it without the kernel file)
 inline size_t orbk_pyramid_lds_bytes(int dh) { return (size_t)(dh + 8) * sizeof(uint2) + (size_t)ORBFE_PW_ROWS * 256 * 4; }
 hipError_t orbk_launch_pyramid(const OrbLaunch &a, hipStream_t st);
+// the FAST pass in two pieces: the clear of the survivor counts and cell flags it fills (a fill kernel of the runtime; on any stream
+// that is behind the last reader of the handle's previous call and in front of the launch), and the launch itself
+hipError_t orbk_clear_fast(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_fast(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_octree(const OrbLaunch &a, hipStream_t st);
 hipError_t orbk_launch_blur(const OrbLaunch &a, hipStream_t st);

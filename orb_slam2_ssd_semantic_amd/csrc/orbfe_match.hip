@@ -38,17 +38,20 @@
 // produces.  Between train tiles the field of the running keys is forced to 127 (an older row beats any newer
 // one on equal distance) and the global index of the best is latched whenever the best key changed in a tile.
 //
-// Workgroup = 4 waves x BM_Q query tiles of 32 = 512 queries; the train descriptors stream through LDS in tiles of
+// Workgroup = 4 waves x BM_Q query tiles of 32 (BM_Q = 4: 512 queries); the train descriptors stream through LDS in tiles of
 // 32 rows, expanded bit -> +-64 byte on the way in (8-byte table look-up per source byte) and laid out so that the
 // A operand of lane (row r, k-half h) at k-step s is one conflict-free ds_read_b128 at ((2s + h) * 32 + r) * 16.
 // The query tiles (B operands, 32 VGPRs each) are expanded once and stay in registers.  The bit -> k assignment is
 // the same on both sides, which is all a dot product needs.
 // The wave is software-pipelined: the MFMA chain of the next query tile (at the end of a train tile: of query tile 0
 // of the next train tile) is issued between the ranking instructions of the current one.
+// BM_Q is a template parameter, instantiated for 4 (the default of every caller), 2 and 1: 253, 176 and 101 VGPRs under the same
+// launch bound.  A workgroup needs its registers on all four SIMDs of one CU at once; beside the dense FAST pass (three resident
+// workgroups of 160 registers per SIMD) the 4-tile form waits until two of them have left, the 2-tile form fits where one has
+// (176 + 2 x 160 <= 512).  Fewer tiles re-read every train tile from the LDS more often per MFMA; the results are the same bytes.
 // ---------------------------------------------------------------------------------------------------
 #define BM_WAVES 4
-#define BM_Q 4
-#define BM_QW (BM_WAVES * BM_Q * 32)
+#define BM_QUERIES(Q) (BM_WAVES * (Q) * 32)   // queries of a workgroup of Q tiles per wave
 #define BM_NEG (-(1 << 30))
 #define BM_MAX_NT (1 << 22)  // the index is latched as a plain int; only nt * 32 bytes must be addressable in 32 bits
 
@@ -67,6 +70,7 @@ __device__ __forceinline__ uint2 bm_expand_byte(uint32_t v, uint32_t mag)
     return make_uint2(lo, hi);
 }
 
+template <int BM_Q>
 __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__restrict__ q_base,
                                                                const uint8_t *__restrict__ t_base,
                                                                const int32_t *__restrict__ n_arr,  // per-frame counts or NULL
@@ -93,6 +97,7 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
     }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int BM_QW = BM_QUERIES(BM_Q);
     const int q0 = blockIdx.x * BM_QW;
     const int nslots = n_arr ? cap : nq;  // output slots of this pair
     if (q0 >= nslots) return;
@@ -509,6 +514,15 @@ extern "C" orbfe_status orbfe_matcher_set_bf_kernel(orbfe_matcher *m, int32_t ke
     return ORBFE_OK;
 }
 
+// query tiles per wave of k_match_bf for this handle's brute-force calls: 4 (the default), 2 or 1.  Same results, fewer registers
+// (not in include/orbfe.h: an A/B and test knob)
+extern "C" orbfe_status orbfe_internal_matcher_set_bf_tiles(orbfe_matcher *m, int32_t tiles)
+{
+    if (!m || !orb_match_tiles_ok(tiles)) return ORBFE_ERR_ARG;
+    m->bf_tiles = tiles;
+    return ORBFE_OK;
+}
+
 extern "C" orbfe_status orbfe_matcher_set_projection_kernel(orbfe_matcher *m, int32_t kernel)
 {
     if (!m || kernel < 0 || kernel > 1) return ORBFE_ERR_ARG;
@@ -531,7 +545,18 @@ extern "C" void orbfe_matcher_destroy(orbfe_matcher *m)
     delete m;
 }
 
-static orbfe_status launch_bf(int kernel, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, const float *d_qa,
+// one launch of k_match_bf<tiles> (tiles 4, 2 or 1; the setters let nothing else through)
+template <typename... Args>
+static void launch_match_bf(int tiles, int nslots, int npairs, hipStream_t st, Args... args)
+{
+    const dim3 block(BM_WAVES * 64);
+    auto grid = [&](int qw) { return dim3((nslots + qw - 1) / qw, npairs); };
+    if (tiles == 1) hipLaunchKernelGGL(k_match_bf<1>, grid(BM_QUERIES(1)), block, 0, st, args...);
+    else if (tiles == 2) hipLaunchKernelGGL(k_match_bf<2>, grid(BM_QUERIES(2)), block, 0, st, args...);
+    else hipLaunchKernelGGL(k_match_bf<4>, grid(BM_QUERIES(4)), block, 0, st, args...);
+}
+
+static orbfe_status launch_bf(int kernel, int tiles, const uint8_t *d_q, int nq, const uint8_t *d_t, int nt, const float *d_qa,
                               const float *d_ta, int ang_stride, float nnratio, int th, int check_ori,
                               int32_t *d_match, int32_t *d_best, int32_t *d_second, int32_t *d_nm, hipStream_t st)
 {
@@ -541,9 +566,8 @@ static orbfe_status launch_bf(int kernel, const uint8_t *d_q, int nq, const uint
                                (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, nq, nt, nnratio, th,
                                d_match, d_best, d_second);
         else
-            hipLaunchKernelGGL(k_match_bf, dim3((nq + BM_QW - 1) / BM_QW, 1), dim3(BM_WAVES * 64), 0, st, d_q, d_t,
-                               (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
-                               (const int32_t *)nullptr, 0, nq, nt, nnratio, th, d_match, d_best, d_second);
+            launch_match_bf(tiles, nq, 1, st, d_q, d_t, (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                            (const int32_t *)nullptr, 0, nq, nt, nnratio, th, d_match, d_best, d_second);
         ORBFE_HIP(hipGetLastError());
     }
     const int ori = (check_ori && d_qa && d_ta) ? 1 : 0;
@@ -563,7 +587,7 @@ extern "C" orbfe_status orbfe_match_bf_device(orbfe_matcher *m, const uint8_t *d
         return ORBFE_ERR_ARG;
     }
     DeviceGuard g(m->device);
-    return launch_bf(m->bf_kernel, d_q, nq, d_t, nt, d_q_angle, d_t_angle, 1, nnratio, th, check_ori, d_match_q2t, d_best, d_second,
+    return launch_bf(m->bf_kernel, m->bf_tiles, d_q, nq, d_t, nt, d_q_angle, d_t_angle, 1, nnratio, th, check_ori, d_match_q2t, d_best, d_second,
                      d_nmatches, (hipStream_t)stream);
 }
 
@@ -598,7 +622,7 @@ extern "C" orbfe_status orbfe_match_bf(orbfe_matcher *m, const uint8_t *q, int32
         ORBFE_HIP(hipMemcpyAsync(m->b[2].p, q_angle, (size_t)nq * 4, hipMemcpyHostToDevice, st));
         if (nt > 0) ORBFE_HIP(hipMemcpyAsync(m->b[3].p, t_angle, (size_t)nt * 4, hipMemcpyHostToDevice, st));
     }
-    orbfe_status s = launch_bf(m->bf_kernel, m->b[0].as<const uint8_t>(), nq, m->b[1].as<const uint8_t>(), nt,
+    orbfe_status s = launch_bf(m->bf_kernel, m->bf_tiles, m->b[0].as<const uint8_t>(), nq, m->b[1].as<const uint8_t>(), nt,
                                ori ? m->b[2].as<const float>() : nullptr, ori ? m->b[3].as<const float>() : nullptr, 1,
                                nnratio, th, ori ? 1 : 0, m->b[4].as<int32_t>(), m->b[5].as<int32_t>(),
                                m->b[6].as<int32_t>(), m->b[7].as<int32_t>(), st);
@@ -619,8 +643,20 @@ extern "C" orbfe_status orbfe_match_bf_blocks_device(orbfe_matcher *m, const orb
                                                      const int32_t *d_tframe, int32_t npairs, float nnratio, int32_t th,
                                                      int32_t check_ori, int32_t *d_match_q2t, int32_t *d_nmatches, void *stream)
 {
+    return orbfe_internal_match_bf_blocks_tiles(m, d_qkps, d_qdesc, d_qn, d_tkps, d_tdesc, d_tn, cap, d_qframe, d_tframe, npairs, nnratio, th,
+                                                check_ori, d_match_q2t, d_nmatches, m ? m->bf_tiles : 0, stream);
+}
+
+// orbfe_match_bf_blocks_device with the query tiles per wave of k_match_bf given by the call (the pipeline's lane calls) instead of
+// by the handle
+orbfe_status orbfe_internal_match_bf_blocks_tiles(orbfe_matcher *m, const orbfe_keypoint *d_qkps, const uint8_t *d_qdesc,
+                                                  const int32_t *d_qn, const orbfe_keypoint *d_tkps, const uint8_t *d_tdesc,
+                                                  const int32_t *d_tn, int32_t cap, const int32_t *d_qframe, const int32_t *d_tframe,
+                                                  int32_t npairs, float nnratio, int32_t th, int32_t check_ori, int32_t *d_match_q2t,
+                                                  int32_t *d_nmatches, int32_t tiles, void *stream)
+{
     if (!m || !d_qkps || !d_qdesc || !d_qn || !d_tkps || !d_tdesc || !d_tn || !d_qframe || !d_tframe || !d_match_q2t ||
-        !d_nmatches || cap < 1 || cap > BM_MAX_NT || npairs < 0) {
+        !d_nmatches || cap < 1 || cap > BM_MAX_NT || npairs < 0 || !orb_match_tiles_ok(tiles)) {
         orbfe_set_error("bad argument to orbfe_match_bf_blocks_device / _frames_device (cap 1..%d)", BM_MAX_NT);
         return ORBFE_ERR_ARG;
     }
@@ -631,9 +667,8 @@ extern "C" orbfe_status orbfe_match_bf_blocks_device(orbfe_matcher *m, const orb
         hipLaunchKernelGGL(k_match_popc, dim3((cap + 255) / 256, npairs), dim3(256), 0, st, d_qdesc, d_tdesc, d_qn, d_tn, d_qframe,
                            d_tframe, cap, 0, 0, nnratio, th, d_match_q2t, (int32_t *)nullptr, (int32_t *)nullptr);
     else
-        hipLaunchKernelGGL(k_match_bf, dim3((cap + BM_QW - 1) / BM_QW, npairs), dim3(BM_WAVES * 64), 0, st, d_qdesc, d_tdesc,
-                           d_qn, d_tn, d_qframe, d_tframe, cap, 0, 0, nnratio, th, d_match_q2t, (int32_t *)nullptr,
-                           (int32_t *)nullptr);
+        launch_match_bf(tiles, cap, npairs, st, d_qdesc, d_tdesc, d_qn, d_tn, d_qframe, d_tframe, cap, 0, 0, nnratio, th, d_match_q2t,
+                        (int32_t *)nullptr, (int32_t *)nullptr);
     ORBFE_HIP(hipGetLastError());
     // orbfe_keypoint.angle, stride 7 floats
     hipLaunchKernelGGL(k_rot_prune, dim3(npairs), dim3(256), 0, st, d_match_q2t, &d_qkps->angle, &d_tkps->angle, 7, d_qn, d_qframe,

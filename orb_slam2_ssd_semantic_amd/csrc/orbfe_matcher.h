@@ -11,6 +11,7 @@ struct orbfe_matcher {
     DevBuf b[16];
     bool own_stream = true;  // false: the stream belongs to a pipeline (orbfe_internal_matcher_create_on_stream)
     int bf_kernel = 0;  // 0 = k_match_bf (int8 dot product on the matrix cores), 1 = k_match_popc (xor / popcount)
+    int bf_tiles = 4;   // query tiles per wave of k_match_bf: 4, 2 or 1 (orbfe_internal_matcher_set_bf_tiles)
     // Device entry points that use the scratch blocks b[] run on the CALLER's stream: one that arrives on another stream
     // than its predecessor waits (at stream level) for the event recorded behind that predecessor's last launch.
     hipStream_t scratch_stream = nullptr;
@@ -41,6 +42,14 @@ static inline hipError_t scratch_release(orbfe_matcher *m, hipStream_t st)
 
 // a matcher for a pipe of orbfe_pipeline: `st` (the pipe's stream) is its own stream and stays the pipeline's
 orbfe_status orbfe_internal_matcher_create_on_stream(int32_t device, void *st, orbfe_matcher **out);
+
+// the instantiations of k_match_bf (orbfe_match.hip): query tiles per wave
+static inline bool orb_match_tiles_ok(int32_t tiles) { return tiles == 4 || tiles == 2 || tiles == 1; }
+// orbfe_match_bf_blocks_device with the tile count of the call instead of the handle's
+orbfe_status orbfe_internal_match_bf_blocks_tiles(orbfe_matcher *m, const orbfe_keypoint *d_qkps, const uint8_t *d_qdesc, const int32_t *d_qn,
+                                                  const orbfe_keypoint *d_tkps, const uint8_t *d_tdesc, const int32_t *d_tn, int32_t cap,
+                                                  const int32_t *d_qframe, const int32_t *d_tframe, int32_t npairs, float nnratio, int32_t th,
+                                                  int32_t check_ori, int32_t *d_match_q2t, int32_t *d_nmatches, int32_t tiles, void *stream);
 
 // single-workgroup exclusive scan cnt[0..nq) -> off[0..nq] on `st`: k_scan_u32 lives in orbfe_grid.hip and this is its one launch
 // site, for the grid's own entry points and for orbfe_projection.hip (not exported)

@@ -106,6 +106,7 @@ struct OrbPipeRoute {
     int32_t sets;    // handles that take the sub-batches in turn
     int32_t first;   // handle of sub-batch 0
     int32_t lane[4] = {-1, -1, -1, -1};   // lanes: the streams of pyramid, FAST, quadtree + descriptor, blur
+    int32_t fast_odd = -1;                // lanes: the FAST stream of odd sub-batches (lane[1] unless placement 2 gives FAST two streams)
     // per handle: where its extraction starts (what must precede it is waited for there), where it ends, and its matcher's stream
     int32_t start_of[ORBFE_PIPE_MAX_PIPES] = {}, tail_of[ORBFE_PIPE_MAX_PIPES] = {}, match_of[ORBFE_PIPE_MAX_PIPES] = {};
     int32_t nstreams;   // streams that carry work of the call ...
@@ -114,7 +115,8 @@ struct OrbPipeRoute {
 
     // `lane_mode`: -1 the library's choice, 0 never, 1 wherever the rule `lr` allows lanes.  `place` (-1: ORBFE_PIPE_LANE_PLACE) 1: blur
     // on the side stream, matcher behind the descriptor on kernel stream 2; 0: blur behind the pyramid on kernel stream 0, matcher on
-    // the side stream.  `first_pipe` >= 0: the pipe of a chain call's sub-batch 0 instead of the state's rotation.
+    // the side stream; 2: blur behind the pyramid, matcher behind the descriptor, and the side stream takes the FAST launches of odd
+    // sub-batches.  `first_pipe` >= 0: the pipe of a chain call's sub-batch 0 instead of the state's rotation.
     OrbPipeRoute(const OrbPipePlan &plan, const OrbPipeLanes &lr, int32_t lane_mode, int32_t place, int32_t first_pipe, const OrbPipeState &g)
     {
         lanes = lr.lanes && (lane_mode < 0 ? ORBFE_PIPE_LANES_AUTO != 0 : lane_mode != 0);
@@ -122,13 +124,14 @@ struct OrbPipeRoute {
         turn = lanes ? &OrbPipeState::lane_rot : &OrbPipeState::rot;
         first = (lanes || first_pipe < 0 ? g.*turn : first_pipe) % sets;
         const int32_t side = plan.side_index, k0 = plan.first;
-        const bool blur_on_side = (place < 0 ? ORBFE_PIPE_LANE_PLACE : place) != 0;
-        if (lanes) lane[0] = k0, lane[1] = k0 + 1, lane[2] = k0 + 2, lane[3] = blur_on_side ? side : k0;
+        const int32_t pc = place < 0 ? ORBFE_PIPE_LANE_PLACE : place;
+        const bool blur_on_side = pc == 1, match_on_side = pc == 0;
+        if (lanes) lane[0] = k0, lane[1] = k0 + 1, lane[2] = k0 + 2, lane[3] = blur_on_side ? side : k0, fast_odd = pc == 2 ? side : lane[1];
         for (int32_t h = 0; h < sets; ++h) {
             const int32_t chain = k0 + plan.stream_of_pipe[h];
             start_of[h] = lanes ? lane[0] : chain;
             tail_of[h] = lanes ? lane[2] : chain;
-            match_of[h] = lanes ? (blur_on_side ? lane[2] : side) : chain;
+            match_of[h] = lanes ? (match_on_side ? side : lane[2]) : chain;
         }
         nstreams = lanes ? ORBFE_PIPE_LANE_STREAMS + 1 : plan.P_eff;
         for (int32_t i = 0; i < nstreams; ++i) streams[i] = lanes && i == ORBFE_PIPE_LANE_STREAMS ? side : k0 + i;
@@ -137,6 +140,7 @@ struct OrbPipeRoute {
     int32_t start(int32_t j) const { return start_of[handle(j)]; }
     int32_t tail(int32_t j) const { return tail_of[handle(j)]; }
     int32_t matcher(int32_t j) const { return match_of[handle(j)]; }
+    int32_t fast(int32_t j) const { return (j & 1) ? fast_odd : lane[1]; }   // lanes: the FAST stream of sub-batch j
     int32_t carry(int32_t nsub) const { return matcher(nsub - 1); }   // the carry copy: with the last sub-batch's matcher
 };
 
@@ -158,7 +162,8 @@ struct OrbPipeCall {
 // One call.  The sink's methods answer an orbfe_status; the first that is not ORBFE_OK ends the walk and is returned, with launches
 // of the call in flight and the ledger half updated: the caller drains its streams and resets the state.
 //   wait(stream, event) / record(stream, event)
-//   extract(handle, lo, nf, route)            frames lo .. lo + nf - 1 into their slices, from route.start_of[handle] to .tail_of[handle]
+//   extract(handle, lo, nf, route)            frames lo .. lo + nf - 1 into their slices, from route.start_of[handle] to .tail_of[handle];
+//                                             lanes: route.lane[] holds the stage streams of THIS sub-batch (lane[1] = route.fast(j))
 //   match(handle, stream, q0, np)             rows q0 .. q0 + np - 1: frame q against frame q - 1
 //   match_carry(handle, stream, slot)         row 0: frame 0 against the frame in the carry slot
 //   clear_row0(stream)                        row 0 of a frame without predecessor: all -1, count 0
@@ -170,6 +175,7 @@ int32_t orb_pipe_call(OrbPipeState &g, const OrbPipeCall &c, Sink &sink)
     const int32_t nsub = (c.nframes + c.F - 1) / c.F;
     if (g.index.size() < (size_t)nsub + 1) g.index.resize((size_t)nsub + 1);
     const bool cont = (c.flags & ORB_PIPE_CONTINUE) != 0 && g.have_carry && c.match;
+    OrbPipeRoute rj = r;   // the route as sub-batch j sees it: its own FAST stream in lane[1]
     const int32_t rd = g.carry_cur, wr = g.carry_cur ^ 1;
 
     // fork: the streams start behind whatever the caller's stream holds (the producer of the frames, the consumer of the output
@@ -200,7 +206,8 @@ int32_t orb_pipe_call(OrbPipeState &g, const OrbPipeCall &c, Sink &sink)
         ORB_PIPE_DO(wait_index((size_t)j));
         for (size_t i = 0; i < g.index.size(); ++i)
             if ((int32_t)i != j && orb_overlaps((int32_t)i < j ? g.index[i].before : g.index[i].slice, mine)) ORB_PIPE_DO(wait_index(i));
-        ORB_PIPE_DO(sink.extract(h, lo, nf, r));
+        if (r.lanes) rj.lane[1] = r.fast(j);
+        ORB_PIPE_DO(sink.extract(h, lo, nf, rj));
         ORB_PIPE_DO(sink.record(sx, OrbPipeEvent{ORB_EV_EXT, j}));
         g.index[(size_t)j].ext_valid = true;
         g.index[(size_t)j].before = g.index[(size_t)j].slice;

@@ -10,6 +10,8 @@
 // whatever the streams are: what the plan decides is which Q kernels those are.  Measured on 4 queues with 12 pipes asked for
 // (profiles/pipe_queues.md): 3 kernel streams + the side stream that puts the blur beside the latency-bound quadtree beat 4 kernel
 // streams with the blur in line, which equal 12 streams that share the queues.
+// The second half of the file is the other cut over the same four streams, by stage (lanes), with its three placements: since
+// profiles/pipe_fast2.md the default gives two of the four streams to the FAST launches of even and odd sub-batches.
 #pragma once
 
 #include <errno.h>
@@ -84,9 +86,31 @@ static inline bool orb_pipe_plan(int32_t P, int32_t Q, bool copies, OrbPipePlan 
 // stream carries nothing but FAST, back to back, and the other three feed it the pyramid, the blur and the quadtree / descriptor /
 // matcher of neighbouring sub-batches; `sets` extractor handles serve as rotating buffer sets, sub-batch j on set
 // (rot + j) mod sets.  profiles/pipe_lanes.md has the measurements.
+//
+// Placement 2 gives FAST two of the four streams: a queue starts a kernel only when its predecessor has drained, so on one FAST
+// stream every launch ends in a tail in which FAST's wave slots empty out and FAST cannot refill them.  With the FAST launches of
+// even sub-batches on kernel stream 1 and of odd ones on the side stream, launch j + 1 places waves as those of launch j retire;
+// the blur moves in behind the pyramid (as in placement 0) and the matcher stays behind the descriptor (as in placement 1).
+// Nothing relies on FAST launches being in stream order: consecutive sub-batches use different buffer sets, and a set that comes
+// back on the other FAST stream (an odd number of sets) is ordered by its handle's events like any re-use.  The lane defaults
+// below can be set on the compiler's command line for A/B builds; profiles/pipe_fast2.md has the measurements.
+#ifndef ORBFE_PIPE_LANE_SETS
 #define ORBFE_PIPE_LANE_SETS 8         // buffer sets of a lane call (at most P): 3, 4, 6, 8 measured, each a little faster than the last
-#define ORBFE_PIPE_LANE_PLACE 1        // 1: blur on the side stream, matcher behind the descriptor (where chains have both); 0: blur
-                                       // behind the pyramid on kernel stream 0, matcher on the side stream (a tie at 4 sets)
+#endif
+// the placements: 0: blur behind the pyramid on kernel stream 0, matcher on the side stream; 1: blur on the side stream, matcher
+// behind the descriptor (where chains have both; 0 against 1: a tie at 4 sets); 2: blur behind the pyramid, matcher behind the
+// descriptor, FAST on kernel stream 1 and the side stream in turn
+#define ORBFE_PIPE_LANE_PLACE 1        // what a route (orbfe_pipe_graph.h) that is given no placement takes
+#ifndef ORBFE_PIPE_LANE_PLACE_AUTO
+#define ORBFE_PIPE_LANE_PLACE_AUTO 2   // what a pipeline left to itself asks its routes for: with 2-tile matchers +2.4 % over
+                                       // placement 1, with 4-tile matchers -5 % (profiles/pipe_fast2.md)
+#endif
+#ifndef ORBFE_PIPE_LANE_MATCH_TILES
+#define ORBFE_PIPE_LANE_MATCH_TILES 2  // query tiles per wave of a lane call's brute-force matcher (4, 2, 1: orbfe_match.hip): fewer
+                                       // tiles are fewer registers, and with 2 a workgroup fits where ONE FAST workgroup has left.
+                                       // Measured with placement 1 / 2: 4 tiles 0 / -5.1 %, 2 tiles +0.1 / +2.4 %, 1 tile -3.2 / -0.7 %
+#endif
+#define ORBFE_PIPE_LANE_PLACES 3       // placements 0 .. 2
 #define ORBFE_PIPE_LANES_AUTO 1        // what a pipeline left to itself does where the rule allows lanes: 1 lanes, 0 chains
 #define ORBFE_PIPE_LANE_STREAMS 3      // the kernel streams lanes are defined for; with the side stream: four stage streams
 

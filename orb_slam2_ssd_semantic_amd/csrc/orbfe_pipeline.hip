@@ -72,7 +72,9 @@ struct orbfe_pipeline {
     int lane_mode = -1;
     int lane_sets = 0;          // buffer sets of a lane call; 0: ORBFE_PIPE_LANE_SETS
     int lane_place = -1;        // 0: blur behind the pyramid on kernel stream 0, matcher on the side stream; 1: blur on the side
-                                // stream, matcher behind the descriptor on kernel stream 2 (where chains have both); -1: ORBFE_PIPE_LANE_PLACE
+                                // stream, matcher behind the descriptor on kernel stream 2 (where chains have both); 2: blur as 0,
+                                // matcher as 1, FAST of odd sub-batches on the side stream; -1: ORBFE_PIPE_LANE_PLACE_AUTO
+    int lane_tiles = 0;         // query tiles per wave of a lane call's brute-force matcher (4, 2, 1); 0: ORBFE_PIPE_LANE_MATCH_TILES
     // seq[i] = i - 1: qframe = seq + q0 + 1 (q0, q0 + 1, ...), tframe = seq + q0 (q0 - 1, q0, ...)
     DevBuf d_seq;
     int seq_len = 0;
@@ -313,12 +315,21 @@ extern "C" orbfe_status orbfe_internal_pipeline_set_lanes(orbfe_pipeline *pl, in
     return ORBFE_OK;
 }
 // the A/B knobs of a lane call: buffer sets (0: ORBFE_PIPE_LANE_SETS; at most the pipes) and the placement of blur and matcher
-// (0: blur on kernel stream 0, matcher on the side stream; 1: blur on the side stream, matcher on kernel stream 2; -1: ORBFE_PIPE_LANE_PLACE)
+// (0: blur on kernel stream 0, matcher on the side stream; 1: blur on the side stream, matcher on kernel stream 2; 2: blur on kernel
+// stream 0, matcher on kernel stream 2, FAST on kernel stream 1 and the side stream in turn; -1: ORBFE_PIPE_LANE_PLACE_AUTO)
 extern "C" orbfe_status orbfe_internal_pipeline_set_lane_options(orbfe_pipeline *pl, int32_t sets, int32_t place)
 {
-    if (!pl || sets < 0 || sets > ORBFE_PIPE_MAX_PIPES || place < -1 || place > 1) return ORBFE_ERR_ARG;
+    if (!pl || sets < 0 || sets > ORBFE_PIPE_MAX_PIPES || place < -1 || place >= ORBFE_PIPE_LANE_PLACES) return ORBFE_ERR_ARG;
     pl->lane_sets = sets;
     pl->lane_place = place;
+    return ORBFE_OK;
+}
+// ... and the query tiles per wave of a lane call's brute-force matcher (4, 2, 1; 0: ORBFE_PIPE_LANE_MATCH_TILES).  Chain calls and the
+// pipes' matcher handles keep their own (orbfe_internal_matcher_set_bf_tiles)
+extern "C" orbfe_status orbfe_internal_pipeline_set_lane_match_tiles(orbfe_pipeline *pl, int32_t tiles)
+{
+    if (!pl || (tiles != 0 && !orb_match_tiles_ok(tiles))) return ORBFE_ERR_ARG;
+    pl->lane_tiles = tiles;
     return ORBFE_OK;
 }
 
@@ -391,6 +402,7 @@ struct PipeCall {
     float nnratio;
     int32_t th, check_ori;
     hipStream_t caller;
+    int32_t lane_tiles = 0;   // run_device: the matcher's query tiles per wave if the call runs in lanes; 0: the matcher handles' own
 
     hipStream_t stream(int32_t s) const { return s == ORB_PIPE_CALLER ? caller : pl->pool[(size_t)s]; }
     hipEvent_t event(OrbPipeEvent e) const
@@ -426,16 +438,17 @@ struct PipeCall {
         void *lane[4] = {(void *)stream(r.lane[0]), (void *)stream(r.lane[1]), (void *)stream(r.lane[2]), (void *)stream(r.lane[3])};
         return orbfe_internal_extract_batch_lanes(pl->ext[(size_t)h], gray, nf, w, ht, stride, frame_stride, kps, desc, cap, d_n_out + lo, lane);
     }
+    int32_t tiles(int32_t h) const { return lane_tiles ? lane_tiles : pl->mat[(size_t)h]->bf_tiles; }
     orbfe_status match(int32_t h, int32_t s, int32_t q0, int32_t np) const
     {
-        return orbfe_match_bf_blocks_device(pl->mat[(size_t)h], d_kps, d_desc, d_n_out, d_kps, d_desc, d_n_out, cap, seq() + q0 + 1, seq() + q0, np, nnratio,
-                                            th, check_ori, d_match + (size_t)q0 * cap, d_nmatches + q0, (void *)stream(s));
+        return orbfe_internal_match_bf_blocks_tiles(pl->mat[(size_t)h], d_kps, d_desc, d_n_out, d_kps, d_desc, d_n_out, cap, seq() + q0 + 1, seq() + q0, np,
+                                                    nnratio, th, check_ori, d_match + (size_t)q0 * cap, d_nmatches + q0, tiles(h), (void *)stream(s));
     }
     orbfe_status match_carry(int32_t h, int32_t s, int32_t slot) const   // query = frame 0 of this call, train = frame 0 of the carry block
     {
-        return orbfe_match_bf_blocks_device(pl->mat[(size_t)h], d_kps, d_desc, d_n_out, pl->d_ckps[slot].as<orbfe_keypoint>(), pl->d_cdesc[slot].as<uint8_t>(),
-                                            pl->d_cn[slot].as<int32_t>(), cap, seq() + 1, seq() + 1, 1, nnratio, th, check_ori, d_match, d_nmatches,
-                                            (void *)stream(s));
+        return orbfe_internal_match_bf_blocks_tiles(pl->mat[(size_t)h], d_kps, d_desc, d_n_out, pl->d_ckps[slot].as<orbfe_keypoint>(),
+                                                    pl->d_cdesc[slot].as<uint8_t>(), pl->d_cn[slot].as<int32_t>(), cap, seq() + 1, seq() + 1, 1, nnratio, th,
+                                                    check_ori, d_match, d_nmatches, tiles(h), (void *)stream(s));
     }
     orbfe_status clear_row0(int32_t s) const
     {
@@ -455,16 +468,19 @@ struct PipeCall {
 
 // One call on the pipeline's current plan (apply_plan): the device entry point's, or the host entry point's with its copy streams
 // (`first_pipe` >= 0: the pipe of its one-sub-batch chunk)
-static orbfe_status run_device(orbfe_pipeline *pl, const PipeCall &c, int32_t nframes, int32_t flags, int32_t first_pipe = -1)
+static orbfe_status run_device(orbfe_pipeline *pl, const PipeCall &args, int32_t nframes, int32_t flags, int32_t first_pipe = -1)
 {
     const int nsub = (nframes + pl->F - 1) / pl->F;
     orbfe_status s = ensure_events(pl, nsub + 1);
     if (s != ORBFE_OK) return s;
     s = ensure_seq(pl, nframes);
     if (s != ORBFE_OK) return s;
-    const OrbPipeRoute route(pl->cur, orb_pipe_lanes(pl->cur, nsub, pl->lane_sets), pl->lane_mode, pl->lane_place, first_pipe, pl->g);
+    PipeCall c = args;
+    const OrbPipeRoute route(pl->cur, orb_pipe_lanes(pl->cur, nsub, pl->lane_sets), pl->lane_mode, pl->lane_place < 0 ? ORBFE_PIPE_LANE_PLACE_AUTO : pl->lane_place,
+                             first_pipe, pl->g);
     const OrbPipeBlocks out{(uintptr_t)c.d_kps, (uintptr_t)c.d_desc, (uintptr_t)c.d_n_out, c.cap};
     const OrbPipeCall call{route, out, pl->F, nframes, c.d_match != nullptr, flags};
+    c.lane_tiles = route.lanes ? (pl->lane_tiles ? pl->lane_tiles : ORBFE_PIPE_LANE_MATCH_TILES) : 0;
     s = orb_pipe_call(pl->g, call, c);
     if (s != ORBFE_OK) {
         // launches of this call are in flight and the ledger is half updated: drain the pipes and start the sequence over (the next

@@ -102,6 +102,13 @@ class ORBmatcher(Handle):
         """0 = matrix-core int8 dot product (default), 1 = xor / popcount: same results (orbfe_matcher_set_bf_kernel)"""
         check(self._L.orbfe_matcher_set_bf_kernel(self._m, int(kernel)), "orbfe_matcher_set_bf_kernel")
 
+    def set_bf_tiles(self, tiles):
+        """query tiles per wave of the matrix-core brute-force kernel: 4 (default), 2 or 1: same results, fewer registers
+        (orbfe_internal_matcher_set_bf_tiles)"""
+        f = self._L.orbfe_internal_matcher_set_bf_tiles
+        f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self._m, int(tiles)), "orbfe_internal_matcher_set_bf_tiles")
+
     def set_projection_kernel(self, kernel):
         """0 = the projection search in one launch (default), 1 = the four-kernel path: same results (orbfe_matcher_set_projection_kernel)"""
         check(self._L.orbfe_matcher_set_projection_kernel(self._m, int(kernel)), "orbfe_matcher_set_projection_kernel")

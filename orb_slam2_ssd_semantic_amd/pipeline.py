@@ -16,11 +16,13 @@ class FramePipeline(Handle):
 
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, *, max_width=640, max_height=480,
                  sub_batch=1024, npipes=3, device=-1, blur_rounding=0, nnratio=0.9, th=100, check_ori=True, _queues=None, _lanes=None,
-                 _lane_sets=0, _lane_place=-1):
+                 _lane_sets=0, _lane_place=-1, _lane_tiles=0):
         """_queues (tests): the hardware queues the pipeline fits its streams to, instead of what the process's environment says.
         _lanes (tests, A/Bs): None / -1 the library's choice between chains and lanes (csrc/orbfe_pipe_plan.h), 0 chains, 1 lanes
         wherever their rule allows them (an argument error on a pipeline without the streams for them); _lane_sets, _lane_place:
-        buffer sets (0: the default) and blur / matcher placement (-1: the default) of a lane call (orbfe_internal_pipeline_set_lane_options)"""
+        buffer sets (0: the default) and blur / matcher / FAST placement (-1: the default) of a lane call
+        (orbfe_internal_pipeline_set_lane_options); _lane_tiles: query tiles per wave of a lane call's brute-force matcher (4, 2, 1; 0: the
+        default; orbfe_internal_pipeline_set_lane_match_tiles)"""
         self._L = _ffi.lib()
         self._p = C.c_void_p()
         prm = OrbfeParams(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, max_width, max_height, sub_batch, device,
@@ -31,9 +33,10 @@ class FramePipeline(Handle):
             f = self._L.orbfe_internal_pipeline_create_queues
             f.argtypes = [C.POINTER(OrbfeParams), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
             check(f(C.byref(prm), npipes, int(_queues), C.byref(self._p)), "orbfe_internal_pipeline_create_queues")
-        if _lanes is not None or _lane_sets or _lane_place != -1:
+        if _lanes is not None or _lane_sets or _lane_place != -1 or _lane_tiles:
             try:
                 self.set_lanes(-1 if _lanes is None else _lanes, _lane_sets, _lane_place)
+                self.set_lane_match_tiles(_lane_tiles)
             except Exception:
                 self._L.orbfe_pipeline_destroy(self._p)
                 self._p = None
@@ -85,6 +88,12 @@ class FramePipeline(Handle):
         f = self._L.orbfe_internal_pipeline_set_lanes
         f.argtypes = [C.c_void_p, C.c_int32]
         check(f(self._p, int(mode)), "orbfe_internal_pipeline_set_lanes")
+
+    def set_lane_match_tiles(self, tiles):
+        """query tiles per wave of the brute-force matcher in later lane calls: 4, 2, 1, or 0 for the library's default"""
+        f = self._L.orbfe_internal_pipeline_set_lane_match_tiles
+        f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self._p, int(tiles)), "orbfe_internal_pipeline_set_lane_match_tiles")
 
     def streams(self):
         """(kernel streams, pipes that take sub-batches, 1 if the blur has a side stream) of the plan in force"""

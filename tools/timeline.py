@@ -58,6 +58,20 @@ for t, dlt in fpts:
     depth += dlt
     last = t
 fast_time[0] = fast_time.get(0, 0) + (t1 - last)
+# the same over the inner sub-batches only: from the start of the third timed FAST launch to the start of the third last, which
+# leaves out the head (nothing to overlap with yet) and the tail (the last quadtree / descriptor / matcher behind the last FAST)
+fast_inner = {}
+timed = fm[n_warm:n_warm + n_timed]
+if len(timed) > 6:
+    i0, i1 = timed[2][0], timed[-3][0]
+    depth, last = 0, i0
+    for t, dlt in fpts:
+        if t > i0:
+            fast_inner[depth] = fast_inner.get(depth, 0) + (min(t, i1) - last)
+            last = min(t, i1)
+        depth += dlt
+        if t >= i1:
+            break
 per = {}
 for s, e, k in sel:
     p = per.setdefault(k, [0, 0])
@@ -67,6 +81,7 @@ wall = t1 - t0
 res = {"wall_ms": wall / 1e6, "busy_frac": busy / wall, "mean_kernels_in_flight": sum(v[1] for v in per.values()) / wall,
        "time_share_by_kernels_in_flight": {str(k): round(v / wall, 4) for k, v in sorted(conc_time.items())},
        "time_share_by_fast_launches_in_flight": {str(k): round(v / wall, 4) for k, v in sorted(fast_time.items())},
+       "time_share_by_fast_launches_in_flight_inner": {str(k): round(v / max(1, sum(fast_inner.values())), 4) for k, v in sorted(fast_inner.items())},
        "idle_gaps": len(gaps), "longest_idle_gaps_us": [round(g / 1e3, 1) for g in sorted(gaps, reverse=True)[:5]],
        "per_kernel": {k: {"calls": v[0], "sum_ms": round(v[1] / 1e6, 3), "avg_us": round(v[1] / v[0] / 1e3, 1)} for k, v in sorted(per.items(), key=lambda x: -x[1][1])},
        "bench_value": bench["value"] if bench else None, "command": "python bench.py " + " ".join(args),
