@@ -1284,6 +1284,101 @@ enum {
 };
 orbfe_status orbfe_pnp_kat(int32_t what, int32_t n, const double *in, double *out);
 
+/* ---- the monocular Initializer (csrc/orbfe_initializer.hip) ---------------------------------------------------
+ * ORB_SLAM2::Initializer::Initialize of src/Initializer.cc: the H / F RANSAC over `iterations` sets of eight matches, the model
+ * choice by RH = SH / (SH + SF) > 0.40, ReconstructH (8 hypotheses) or ReconstructF (4), CheckRT with Triangulate, and the
+ * final ladder.  The random draws are an INPUT: iterations x 8 raw rand() values, turned into mvSets as the reference does
+ * (RandomInt on the shrinking list, swap with back).  Bit-exact against tests/initializer_oracle.py (an unpinned restatement;
+ * its numbered assumptions I1.. are DESIGN 8j's).  K is the 3 x 3 calibration matrix, row-major. */
+typedef struct orbfe_initializer_result {
+    int32_t ok;              /* what Initialize returns */
+    int32_t status;          /* ORBFE_INIT_*: why nothing ran, 0 if the chain ran */
+    int32_t model;           /* 0 none, 1 H (RH > 0.40), 2 F */
+    int32_t n_matches;       /* N = matches12 entries >= 0 */
+    float SH, SF;            /* the best scores; 0 when no iteration had a positive one */
+    int32_t iterH, iterF;    /* the iterations that won (strict >, so the first of equal scores), -1 if none */
+    float H21[9], F21[9];    /* their models, zeros if none */
+    float R21[9], t21[3];    /* zeros unless ok */
+    int32_t n_hyp;           /* hypotheses CheckRT ran on: 8, 4, or 0 at ReconstructH's d1/d2, d2/d3 early-out */
+    int32_t nGood[8];
+    int32_t n_cos[8];        /* size of vCosParallax per hypothesis */
+    float sel_cos[8];        /* vCosParallax[min(50, size - 1)] after the sort; 0 where nGood = 0 */
+    int32_t best;            /* H: bestSolutionIdx; F: the first hypothesis with maxGood; -1 if none */
+    int32_t second;          /* H: secondBestGood; F: nsimilar */
+    int32_t n_inliers;       /* N of ReconstructH / ReconstructF: the winner's inliers */
+    int32_t parallax_ok;     /* the best hypothesis's parallax test (> 1 for F, >= 1 for H), as a cut on sel_cos[best] */
+    float parallax_cos;      /* sel_cos[best] */
+    float parallax;          /* acosf(parallax_cos) * 180 / pi with the device's acosf: reported, never decided on */
+    int32_t reserved[3];
+} orbfe_initializer_result;   /* 72 words */
+typedef struct orbfe_initializer_pair {   /* one frame pair of the batched form */
+    float K[9];
+    float sigma;
+    int32_t iterations;      /* 1 .. ORBFE_INIT_MAX_ITERATIONS */
+    int32_t draws_offset;    /* into d_draws, in values; iterations * 8 are read */
+    int32_t reserved[4];
+} orbfe_initializer_pair;     /* 16 words */
+typedef struct orbfe_initializer_iter {   /* tap record of one iteration */
+    int32_t set[8];          /* mvSets[it]: indices into the compacted match list */
+    float Hn[9], Fn[9];      /* ComputeH21 / ComputeF21 on the normalised points */
+    float H21i[9], F21i[9];
+    float scoreH, scoreF;
+    int32_t reserved[2];
+} orbfe_initializer_iter;     /* 48 words */
+enum { ORBFE_INIT_OK = 0, ORBFE_INIT_FEW_MATCHES = 1, ORBFE_INIT_BAD_INDEX = 2, ORBFE_INIT_NO_MODEL = 3, ORBFE_INIT_BAD_SIZES = 4 };
+#define ORBFE_INIT_MAX_ITERATIONS 512
+#define ORBFE_INIT_TAP_SETS 32
+#define ORBFE_INIT_TAP_ITERS 512
+#define ORBFE_INIT_ERR_FLOATS 9
+typedef struct orbfe_initializer orbfe_initializer;
+/* Device scratch for calls of at most max_matches keys of the first frames (all pairs of a batch together; the compacted match
+ * lists live there) and max_pairs pairs, with a stream of its own. */
+orbfe_status orbfe_initializer_create(int32_t device, int32_t max_matches, int32_t max_pairs, orbfe_initializer **out);
+void orbfe_initializer_destroy(orbfe_initializer *h);
+void *orbfe_initializer_get_stream(orbfe_initializer *h);
+/* One Initialize on HOST arrays, synchronous: one launch sequence and one synchronisation on the handle's stream.  keys*_xy
+ * float [n][2] (mvKeysUn's pt), matches12 int32 [n1] (index into keys2, < 0 = none), K float [9], draws int32 [iterations * 8].
+ * Out: *result, P3D float [n1][3], triangulated uint8 [n1] (zeros unless ok).  Fewer than 8 matches, a match index >= n2,
+ * iterations outside 1 .. ORBFE_INIT_MAX_ITERATIONS, n1 > max_matches: ORBFE_ERR_ARG (undefined in the reference). */
+orbfe_status orbfe_initializer_initialize(orbfe_initializer *h, const float *keys1_xy, int32_t n1, const float *keys2_xy, int32_t n2,
+                                          const int32_t *matches12, const float *K, float sigma, int32_t iterations,
+                                          const int32_t *draws, orbfe_initializer_result *result, float *P3D, uint8_t *triangulated);
+/* Many pairs in one call on the caller's stream, everything in device memory, no synchronisation: d_offsets1 / d_offsets2 int32
+ * [npairs + 1] are the CSR offsets of the pairs' keys in d_keys1_xy / d_keys2_xy; d_matches12, d_P3D, d_triangulated follow
+ * d_offsets1 (the matches can be a row of the device matcher's output block as it stands: -1 = none).  A pair the host form
+ * would have refused gets result.status != 0 and ok = 0; nothing else of it is written.  The host reads only the pointers. */
+orbfe_status orbfe_initializer_initialize_device(orbfe_initializer *h, const int32_t *d_offsets1, const int32_t *d_offsets2,
+                                                 const float *d_keys1_xy, const float *d_keys2_xy, const int32_t *d_matches12,
+                                                 const orbfe_initializer_pair *d_pairs, const int32_t *d_draws, int32_t npairs,
+                                                 orbfe_initializer_result *d_result, float *d_P3D, uint8_t *d_triangulated,
+                                                 void *stream);
+/* Test taps, as orbfe_pnp_tap: allocated by the first orbfe_initializer_set_tap_iteration, then recorded for the first
+ * ORBFE_INIT_TAP_SETS pairs of every call:
+ *   0 ORBFE_INIT_TAP_ITERATIONS  one orbfe_initializer_iter per iteration; *count = records
+ *   1 ORBFE_INIT_TAP_MATCHES     float [N][9] per compacted match: chiSquare1, chiSquare2 of CheckHomography and of
+ *                                CheckFundamental for the models of iteration `iteration`, then p3dC1 [3], cosParallax and the
+ *                                stage at which CheckRT dropped the match (ORBFE_INIT_RT_*, as a float) for hypothesis
+ *                                `hypothesis`, both chosen BEFORE the call; ORBFE_ERR_STATE if that iteration did not run */
+enum { ORBFE_INIT_TAP_ITERATIONS = 0, ORBFE_INIT_TAP_MATCHES = 1 };
+enum {
+    ORBFE_INIT_RT_OUTLIER = 0, ORBFE_INIT_RT_NONFINITE = 1, ORBFE_INIT_RT_DEPTH1 = 2, ORBFE_INIT_RT_DEPTH2 = 3, ORBFE_INIT_RT_ERROR1 = 4,
+    ORBFE_INIT_RT_ERROR2 = 5, ORBFE_INIT_RT_FAR = 6, ORBFE_INIT_RT_GOOD = 7
+};
+orbfe_status orbfe_initializer_set_tap_iteration(orbfe_initializer *h, int32_t iteration, int32_t hypothesis);
+orbfe_status orbfe_initializer_tap(orbfe_initializer *h, int32_t pair, int32_t stage, void *dst, size_t cap, int32_t *count);
+/* Known-answer runs of the device primitives on the caller's current device, floats in and out, n items:
+ *   0..3  cv::SVD::compute(FULL_UV) of a 16x9 / 8x9 / 3x3 / 4x4 CV_32F matrix (row-major): out = w [min], u [rows][rows],
+ *         vt [cols][cols] -- OpenCV 3.2's JacobiSVDImpl_<float>; for 8x9 vt row 8 is the RNG refill row
+ *   4     Mat::inv() of a 3x3
+ *   5, 6  ComputeH21 / ComputeF21: in = vP1 [8][2], vP2 [8][2]; out = [9]
+ *   7     Triangulate: in = kp1 xy, kp2 xy, P1 [12], P2 [12]; out = x3D [3]
+ *   8     the parallax cut: in = one cosine; out = 1 or 0 */
+enum {
+    ORBFE_INIT_KAT_SVD16X9 = 0, ORBFE_INIT_KAT_SVD8X9 = 1, ORBFE_INIT_KAT_SVD3 = 2, ORBFE_INIT_KAT_SVD4 = 3, ORBFE_INIT_KAT_INV3 = 4,
+    ORBFE_INIT_KAT_H21 = 5, ORBFE_INIT_KAT_F21 = 6, ORBFE_INIT_KAT_TRIANGULATE = 7, ORBFE_INIT_KAT_PARALLAX = 8
+};
+orbfe_status orbfe_initializer_kat(int32_t what, int32_t n, const float *in, float *out);
+
 #ifdef __cplusplus
 }
 #endif

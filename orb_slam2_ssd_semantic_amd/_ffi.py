@@ -54,6 +54,8 @@ SYMBOLS = (
     "orbfe_sim3_iterate_device", "orbfe_sim3_prepare_device", "orbfe_sim3_set_tap_iteration", "orbfe_sim3_tap", "orbfe_sim3_kat",
     "orbfe_pnp_create", "orbfe_pnp_destroy", "orbfe_pnp_get_stream", "orbfe_pnp_ransac_params", "orbfe_pnp_iterations", "orbfe_pnp_iterate",
     "orbfe_pnp_iterate_device", "orbfe_pnp_prepare_device", "orbfe_pnp_set_tap_iteration", "orbfe_pnp_tap", "orbfe_pnp_kat",
+    "orbfe_initializer_create", "orbfe_initializer_destroy", "orbfe_initializer_get_stream", "orbfe_initializer_initialize",
+    "orbfe_initializer_initialize_device", "orbfe_initializer_set_tap_iteration", "orbfe_initializer_tap", "orbfe_initializer_kat",
     "orbfe_cloud_create", "orbfe_cloud_destroy", "orbfe_cloud_get_stream", "orbfe_cloud_paint_boxes_device", "orbfe_cloud_generate_device",
     "orbfe_cloud_insert_device", "orbfe_cloud_insert", "orbfe_cloud_voxel_filter_device", "orbfe_cloud_size", "orbfe_cloud_data_device",
     "orbfe_cloud_download", "orbfe_cloud_upload_device", "orbfe_cloud_pose_matrix",
@@ -343,6 +345,16 @@ def _configure(L):
     L.orbfe_pnp_set_tap_iteration.argtypes = [vp, i32]
     L.orbfe_pnp_tap.argtypes = [vp, i32, i32, vp, sz, vp]
     L.orbfe_pnp_kat.argtypes = [i32, i32, vp, vp]
+    L.orbfe_initializer_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.orbfe_initializer_destroy.argtypes = [vp]
+    L.orbfe_initializer_destroy.restype = None
+    L.orbfe_initializer_get_stream.argtypes = [vp]
+    L.orbfe_initializer_get_stream.restype = vp
+    L.orbfe_initializer_initialize.argtypes = [vp, vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp]
+    L.orbfe_initializer_initialize_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.orbfe_initializer_set_tap_iteration.argtypes = [vp, i32, i32]
+    L.orbfe_initializer_tap.argtypes = [vp, i32, i32, vp, sz, vp]
+    L.orbfe_initializer_kat.argtypes = [i32, i32, vp, vp]
     L.orbfe_cloud_create.argtypes = [i32, f64, i32, i32, i32, i32, C.POINTER(vp)]
     L.orbfe_cloud_destroy.argtypes = [vp]
     L.orbfe_cloud_destroy.restype = None

@@ -151,6 +151,140 @@ ORBFE_HD inline void jacobi_svd(double *At, double *W, double *Vt, int m, int n)
     }
 }
 
+// JacobiSVDImpl_<float> (tests/initializer_oracle.py I1, I2): the float instantiation with OpenCV's own constants (minval =
+// FLT_MIN, eps = FLT_EPSILON * 2), float rotations, double accumulators, and the n1 >= n form: At has n1 rows of length m, the first
+// n take part in the sweeps, the rows from n on (columns of a FULL_UV u, or ComputeF21's vt.row(8) of the 8 x 9 system, which goes
+// in untransposed) come out of the RNG refill and the two Gram-Schmidt sweeps.  W: n doubles of workspace; the float singular
+// values are (float)W[i].  PA / PV / PW are anything indexable (a pointer, or LdsLane below), so that a lane's matrices can live
+// in LDS laid out [entry][lane].
+template <class T, int S>
+struct LdsLane {
+    T *p;
+    ORBFE_HD T &operator[](int i) const { return p[(size_t)i * S]; }
+};
+
+template <class PA, class PW, class PV>
+ORBFE_HD inline void jacobi_svd_f(PA At, PW W, PV Vt, int m, int n, int n1)
+{
+    const double minval = FLT_MIN;
+    const float eps = FLT_EPSILON * 2;
+    const int max_iter = m > 30 ? m : 30;
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) {
+            const float t = At[i * m + k];
+            sd += (double)t * t;
+        }
+        W[i] = sd;
+        for (int k = 0; k < n; k++) Vt[i * n + k] = 0;
+        Vt[i * n + i] = 1;
+    }
+    for (int iter = 0; iter < max_iter; iter++) {
+        bool changed = false;
+        for (int i = 0; i < n - 1; i++)
+            for (int j = i + 1; j < n; j++) {
+                double a = W[i], p = 0, b = W[j];
+                for (int k = 0; k < m; k++) p += (double)At[i * m + k] * At[j * m + k];
+                if (fabs(p) <= eps * sqrt(a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = svd_hypot(p, beta);
+                float c, s;
+                if (beta < 0) {
+                    const double delta = (gamma - beta) * 0.5;
+                    s = (float)sqrt(delta / gamma);
+                    c = (float)(p / (gamma * s * 2));
+                } else {
+                    c = (float)sqrt((gamma + beta) / (gamma * 2));
+                    s = (float)(p / (gamma * c * 2));
+                }
+                a = b = 0;
+                for (int k = 0; k < m; k++) {
+                    const float ai = At[i * m + k], aj = At[j * m + k];
+                    const float t0 = c * ai + s * aj;
+                    const float t1 = -s * ai + c * aj;
+                    At[i * m + k] = t0;
+                    At[j * m + k] = t1;
+                    a += (double)t0 * t0;
+                    b += (double)t1 * t1;
+                }
+                W[i] = a;
+                W[j] = b;
+                changed = true;
+                for (int k = 0; k < n; k++) {
+                    const float vi = Vt[i * n + k], vj = Vt[j * n + k];
+                    const float t0 = c * vi + s * vj;
+                    const float t1 = -s * vi + c * vj;
+                    Vt[i * n + k] = t0;
+                    Vt[j * n + k] = t1;
+                }
+            }
+        if (!changed) break;
+    }
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) {
+            const float t = At[i * m + k];
+            sd += (double)t * t;
+        }
+        W[i] = sqrt(sd);
+    }
+    for (int i = 0; i < n - 1; i++) {
+        int j = i;
+        for (int k = i + 1; k < n; k++)
+            if (W[j] < W[k]) j = k;
+        if (i != j) {
+            const double tw = W[i];
+            W[i] = W[j];
+            W[j] = tw;
+            for (int k = 0; k < m; k++) {
+                const float t = At[i * m + k];
+                At[i * m + k] = At[j * m + k];
+                At[j * m + k] = t;
+            }
+            for (int k = 0; k < n; k++) {
+                const float t = Vt[i * n + k];
+                Vt[i * n + k] = Vt[j * n + k];
+                Vt[j * n + k] = t;
+            }
+        }
+    }
+    uint64_t rng = 0x12345678;   // cv::RNG, one per call
+    for (int i = 0; i < n1; i++) {
+        double sd = i < n ? (double)W[i] : 0;
+        for (int ii = 0; ii < 100 && sd <= minval; ii++) {
+            const float val0 = (float)(1. / m);
+            for (int k = 0; k < m; k++) {
+                rng = (uint64_t)(uint32_t)rng * 4164903690U + (uint32_t)(rng >> 32);
+                At[i * m + k] = ((uint32_t)rng & 256) != 0 ? val0 : -val0;
+            }
+            for (int iter = 0; iter < 2; iter++)
+                for (int j = 0; j < i; j++) {
+                    sd = 0;
+                    for (int k = 0; k < m; k++) {
+                        const float pr = At[i * m + k] * At[j * m + k];   // a float product into the double sum
+                        sd += pr;
+                    }
+                    float asum = 0;
+                    for (int k = 0; k < m; k++) {
+                        const float t = (float)(At[i * m + k] - sd * At[j * m + k]);
+                        At[i * m + k] = t;
+                        asum += fabsf(t);
+                    }
+                    asum = asum > eps * 100 ? 1 / asum : 0;
+                    for (int k = 0; k < m; k++) At[i * m + k] = At[i * m + k] * asum;
+                }
+            sd = 0;
+            for (int k = 0; k < m; k++) {
+                const float t = At[i * m + k];
+                sd += (double)t * t;
+            }
+            sd = sqrt(sd);
+        }
+        const float s = (float)(sd > minval ? 1 / sd : 0.);
+        for (int k = 0; k < m; k++) At[i * m + k] = At[i * m + k] * s;
+    }
+}
+
 // cv::SVD::compute on A (m x n row-major, m >= n): At takes the transpose
 ORBFE_HD inline void svd_compute(const double *A, int m, int n, double *At, double *W, double *Vt)
 {

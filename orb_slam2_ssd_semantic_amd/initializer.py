@@ -1,0 +1,141 @@
+"""The reference's monocular Initializer (src/Initializer.cc) on the GPU: the H / F RANSAC over sets of eight matches, the model
+choice, ReconstructH / ReconstructF with CheckRT and Triangulate, through the C-ABI of csrc/orbfe_initializer.hip.  The random
+draws are an input (raw values in [0, 2^31 - 1], eight per iteration), so a run can be replayed.  No CPU fallback."""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi, _ransac
+from ._ffi import stream_arg, tensor_ptr
+
+RESULT_DTYPE = np.dtype([("ok", "<i4"), ("status", "<i4"), ("model", "<i4"), ("n_matches", "<i4"), ("SH", "<f4"), ("SF", "<f4"),
+                         ("iterH", "<i4"), ("iterF", "<i4"), ("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3)), ("R21", "<f4", (3, 3)),
+                         ("t21", "<f4", (3,)), ("n_hyp", "<i4"), ("nGood", "<i4", (8,)), ("n_cos", "<i4", (8,)), ("sel_cos", "<f4", (8,)),
+                         ("best", "<i4"), ("second", "<i4"), ("n_inliers", "<i4"), ("parallax_ok", "<i4"), ("parallax_cos", "<f4"),
+                         ("parallax", "<f4"), ("reserved", "<i4", (3,))])
+PAIR_DTYPE = np.dtype([("K", "<f4", (3, 3)), ("sigma", "<f4"), ("iterations", "<i4"), ("draws_offset", "<i4"), ("reserved", "<i4", (4,))])
+ITER_DTYPE = np.dtype([("set", "<i4", (8,)), ("Hn", "<f4", (3, 3)), ("Fn", "<f4", (3, 3)), ("H21i", "<f4", (3, 3)), ("F21i", "<f4", (3, 3)),
+                       ("scoreH", "<f4"), ("scoreF", "<f4"), ("reserved", "<i4", (2,))])
+assert (RESULT_DTYPE.itemsize, PAIR_DTYPE.itemsize, ITER_DTYPE.itemsize) == (288, 64, 192)
+MAX_ITERATIONS = 512
+STATUS_OK, STATUS_FEW_MATCHES, STATUS_BAD_INDEX, STATUS_NO_MODEL, STATUS_BAD_SIZES = range(5)
+MODEL_NONE, MODEL_H, MODEL_F = range(3)
+TAP_ITERATIONS, TAP_MATCHES = range(2)
+(KAT_SVD16X9, KAT_SVD8X9, KAT_SVD3, KAT_SVD4, KAT_INV3, KAT_H21, KAT_F21, KAT_TRIANGULATE, KAT_PARALLAX) = range(9)
+_KAT_IO = {KAT_SVD16X9: (144, 346), KAT_SVD8X9: (72, 153), KAT_SVD3: (9, 21), KAT_SVD4: (16, 36), KAT_INV3: (9, 9), KAT_H21: (32, 9),
+           KAT_F21: (32, 9), KAT_TRIANGULATE: (28, 3), KAT_PARALLAX: (1, 1)}
+
+
+class InitializerHandle(_ransac.RansacHandle):
+    """Device scratch for Initialize calls over at most max_matches keys of the first frames (all pairs of a batch together) and
+    batches of at most max_pairs pairs.  The match tap is float32 [N, 9]: the chiSquare pairs of H and F of the tapped iteration,
+    then p3dC1, cosParallax and the CheckRT stage of the tapped hypothesis."""
+
+    _PREFIX, ITER_DTYPE, _ERR_SHAPE = "orbfe_initializer", ITER_DTYPE, (9,)
+
+    def __init__(self, max_matches=4096, max_pairs=1, device=0):
+        super().__init__(max_matches, max_pairs, device)
+        self.max_matches = max_matches
+
+    def set_tap_iteration(self, iteration, hypothesis=0):
+        self._call("set_tap_iteration", self.h, int(iteration), int(hypothesis))
+
+    def initialize(self, keys1, keys2, matches12, K, sigma, iterations, draws):
+        """One Initialize on host arrays: keys float32 [n, 2], matches12 int32 [n1], K [3, 3], draws int32 [iterations * 8].
+        -> (result RESULT_DTYPE record, P3D float32 [n1, 3], triangulated uint8 [n1])"""
+        k1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+        if len(m) != len(k1):
+            raise ValueError("matches12 must hold one entry per key of the first frame")
+        d = np.ascontiguousarray(draws, np.int32).reshape(-1)
+        if len(d) < 8 * int(iterations):
+            raise ValueError("eight draws per iteration are needed")
+        k = np.ascontiguousarray(K, np.float32).reshape(9)
+        res = np.zeros(1, RESULT_DTYPE)
+        P3D = np.zeros((len(k1), 3), np.float32)
+        tri = np.zeros(len(k1), np.uint8)
+        one = np.zeros(1, np.float32)   # a valid address for an empty array
+        self._call("initialize", self.h, _ffi.ptr(k1 if len(k1) else one), len(k1), _ffi.ptr(k2 if len(k2) else one), len(k2),
+                   _ffi.ptr(m if len(m) else one), _ffi.ptr(k), float(sigma), int(iterations), _ffi.ptr(d if len(d) else one),
+                   _ffi.ptr(res), _ffi.ptr(P3D if len(k1) else one), _ffi.ptr(tri if len(k1) else one))
+        return res[0], P3D, tri
+
+    def initialize_device(self, offsets1, offsets2, keys1, keys2, matches12, pairs, draws, result=None, P3D=None, triangulated=None,
+                          stream=None):
+        """The batched form on torch device tensors: offsets1 / offsets2 int32 [npairs + 1] (CSR over the pairs' keys), keys1 /
+        keys2 float32 [., 2], matches12 int32 following offsets1, pairs uint8 [npairs, 64] (PAIR_DTYPE bytes), draws int32.
+        Returns (result uint8 [npairs, 288] of RESULT_DTYPE bytes, P3D float32 [., 3], triangulated uint8 [.]) on the device.
+        Enqueued on `stream` (default: torch's current stream), no synchronisation."""
+        import torch
+        npairs = offsets1.numel() - 1
+        dev = offsets1.device
+        _ransac.check_tensors((offsets1, torch.int32, "offsets1"), (offsets2, torch.int32, "offsets2"), (keys1, torch.float32, "keys1"),
+                              (keys2, torch.float32, "keys2"), (matches12, torch.int32, "matches12"), (pairs, torch.uint8, "pairs"),
+                              (draws, torch.int32, "draws"))
+        if offsets2.numel() != npairs + 1 or pairs.numel() != npairs * PAIR_DTYPE.itemsize:
+            raise ValueError("offsets2 / pairs must hold one entry per pair")
+        n = matches12.numel()
+        if keys1.numel() != 2 * n:
+            raise ValueError("keys1 and matches12 must hold one entry per key of the first frames")
+        if result is None:
+            result = torch.zeros((npairs, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if P3D is None:
+            P3D = torch.zeros((max(n, 1), 3), dtype=torch.float32, device=dev)
+        if triangulated is None:
+            triangulated = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        self._call("initialize_device", self.h, tensor_ptr(offsets1), tensor_ptr(offsets2), tensor_ptr(keys1), tensor_ptr(keys2),
+                   tensor_ptr(matches12), tensor_ptr(pairs), tensor_ptr(draws), npairs, tensor_ptr(result), tensor_ptr(P3D),
+                   tensor_ptr(triangulated), stream_arg(dev, stream))
+        return result, P3D[:n], triangulated[:n]
+
+
+_default = {}
+
+
+def _handle(device, n):
+    return _ransac.default_handle(_default, InitializerHandle, "max_matches", device, n)
+
+
+def initialize_device(handle, offsets1, offsets2, keys1, keys2, matches12, pairs, draws, **kw):
+    """InitializerHandle.initialize_device as a function: every pair of a batch in one launch sequence"""
+    return handle.initialize_device(offsets1, offsets2, keys1, keys2, matches12, pairs, draws, **kw)
+
+
+class Initializer:
+    """Mirrors the reference's class: constructed on the reference frame's undistorted keypoints keys1 [n1, 2] and K [3, 3];
+    initialize(keys2, matches12) is Initialize on the current frame.  Draws come from `draws` of each call, or from `rand` (a
+    callable returning k raw values in [0, 2^31 - 1]; default: a numpy generator seeded with 0, as the reference seeds rand()
+    with 0 once), iterations * 8 per call."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, device=0, handle=None, rand=None):
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        self.K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self.sigma, self.iterations = float(sigma), int(iterations)
+        self._h = handle if handle is not None else _handle(device, len(self.keys1))
+        if rand is None:
+            rng = np.random.default_rng(0)
+            rand = lambda k: rng.integers(0, 2 ** 31, k)   # noqa: E731
+        self._rand = rand
+        self.result = None
+
+    def initialize(self, keys2, matches12, draws=None):
+        """-> (ok, R21 float32 [3, 3], t21 float32 [3], P3D float32 [n1, 3], triangulated bool [n1]); self.result keeps the
+        whole RESULT_DTYPE record"""
+        if draws is None:
+            draws = self._rand(8 * self.iterations)
+        res, P3D, tri = self._h.initialize(self.keys1, keys2, matches12, self.K, self.sigma, self.iterations, draws)
+        self.result = res
+        return bool(res["ok"]), res["R21"].copy(), res["t21"].copy(), P3D, tri.astype(bool)
+
+
+def kat(what, data):
+    """Runs a device primitive on host data (orbfe_initializer_kat), float32, n items: data [n, in] -> [n, out] with KAT_SVD16X9:
+    144 -> w 9, u 256, vt 81; KAT_SVD8X9: 72 -> w 8, u 64, vt 81; KAT_SVD3: 9 -> 3, 9, 9; KAT_SVD4: 16 -> 4, 16, 16; KAT_INV3:
+    9 -> 9; KAT_H21 / KAT_F21: vP1 16, vP2 16 -> 9; KAT_TRIANGULATE: kp1 2, kp2 2, P1 12, P2 12 -> 3; KAT_PARALLAX: cos -> 0 / 1."""
+    i, o = _KAT_IO[what]
+    x = np.ascontiguousarray(data, np.float32).reshape(-1, i)
+    out = np.zeros((len(x), o), np.float32)
+    if len(x):
+        _ffi.check(_ffi.lib().orbfe_initializer_kat(int(what), len(x), _ffi.ptr(x), _ffi.ptr(out)), "orbfe_initializer_kat")
+    return out
