@@ -376,9 +376,9 @@ orbfe_status orbfe_features_in_area_device(orbfe_matcher *m, const orbfe_keypoin
  *   ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, th)       src/ORBmatcher.cc:63-157
  *   ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono)   src/ORBmatcher.cc:1578-1724
  *   (and the perfect/ overload that also returns the 2-D point pairs, perfect/src/ORBmatcher.cc:1727-1911).
- * The pose projection and its gates (isBad, mbTrackInView, depth sign, image bounds, forward / backward level window) stay
- * with the caller (shim/ORBmatcher_orbfe.cc does them on cv::Mat exactly as the reference); one query = one MapPoint that
- * passed them.  Per query: Frame::GetFeaturesInArea(u, v, r, min_level, max_level) on the frame's grid, the right-image gate
+ * In these HOST-buffer forms the pose projection and its gates (isBad, mbTrackInView, depth sign, image bounds, forward /
+ * backward level window) are the caller's (shim/ORBmatcher_orbfe.cc does them on cv::Mat exactly as the reference); the
+ * device-resident forms below ("Tracker") run them on the device.  One query = one MapPoint that passed them.  Per query: Frame::GetFeaturesInArea(u, v, r, min_level, max_level) on the frame's grid, the right-image gate
  * (candidate idx skipped when uRight[idx] > 0 && fabs(ur - uRight[idx]) > r -- both call sites compare against the very
  * expression they pass as the search radius, :114-119 / :1654-1660), best / second-best Hamming with the :128-140 idiom
  * over the candidates whose slot is free, acceptance: best <= th (th <= 255; TH_HIGH / ORBdist in the reference) and, with ratio_rule != 0, not (bestLevel == bestLevel2 &&
@@ -486,6 +486,136 @@ orbfe_status orbfe_search_for_triangulation(orbfe_matcher *m, const uint8_t *des
                                             const uint32_t *node2, const uint32_t *off2, const uint32_t *idx2, int32_t nn2,
                                             const float F12[9], float ex, float ey, const float *scale_factors2,
                                             const float *level_sigma2_2, int32_t nlevels2, int32_t th_low, int32_t *match12);
+
+/* Tracker: the two projection searches Tracking runs on every frame -- SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+ * (TrackWithMotionModel, the fork's TrackHomo) and SearchByProjection(F, vpMapPoints, th) (SearchLocalPoints) -- batched and
+ * device-resident, with the pose projection and its gates ON THE DEVICE (csrc/orbfe_track.hip; the per-point arithmetic is
+ * csrc/orbfe_track_geom.h, host and device alike).  Every call is enqueued on `stream`, none waits for the device, none
+ * writes host memory; scratch is the matcher's.  Batch layout = the other *_batch_device calls: frame f's keypoints are
+ * d_kps[f * cap .. f * cap + d_n[f]), descriptors d_desc[(f * cap + i) * 32], the grid of orbfe_assign_grid_batch_device, depth /
+ * uRight of orbfe_frame_geometry_batch_device, poses d_Tcw[f][12] = row-major 3x4 (Rcw | tcw).  Limits: cap <= 15360,
+ * th <= 255, nlevels <= 16, nframes * qcap < 2^25.  DESIGN.md 8k. */
+typedef struct orbfe_track_camera {
+    float fx, fy, cx, cy, bf;
+    float minx, maxx, miny, maxy;    /* Frame::mnMinX .. mnMaxY (orbfe_image_bounds) */
+} orbfe_track_camera;
+/* the frames that are searched ("current" frames) */
+typedef struct orbfe_track_frames {
+    const orbfe_keypoint *d_kps;     /* [nframes][cap], mvKeysUn */
+    const uint8_t *d_desc;           /* [nframes][cap][32] */
+    const int32_t *d_n;              /* [nframes] */
+    int32_t cap;
+    const uint32_t *d_cell_off;      /* [nframes][ORBFE_GRID_COLS * ORBFE_GRID_ROWS + 1] */
+    const uint32_t *d_cell_idx;      /* [nframes][cap] */
+    float minx, miny, gw_inv, gh_inv;
+    const float *d_uright;           /* [nframes][cap] or NULL (no right-image gate) */
+    const uint8_t *d_slot;           /* [nframes][cap] or NULL: mvpMapPoints[i] before the call -- 0 NULL, 1 a MapPoint with
+                                      * Observations() == 0, 2 one with Observations() > 0 (candidate scans skip the slot) */
+} orbfe_track_frames;
+/* the "last" frames of the last-frame form: a separate pointer set, so a sequence passes its own block shifted by one frame
+ * and a replay pairs arbitrary frames */
+typedef struct orbfe_track_last {
+    const orbfe_keypoint *d_kps;     /* [nframes][cap]: octave and angle are read */
+    const int32_t *d_n;              /* [nframes] */
+    int32_t cap;
+    const uint8_t *d_valid;          /* [nframes][cap]: has a MapPoint && !mvbOutlier */
+    const float *d_world_pos;        /* [nframes][cap][3] */
+    const uint8_t *d_obs_gt0;        /* [nframes][cap]: Observations() > 0 */
+    const uint8_t *d_mpdesc;         /* [nframes][cap][32]: MapPoint::GetDescriptor() (a created point: the keypoint's own row) */
+    const float *d_Tcw;              /* [nframes][12] */
+} orbfe_track_last;
+/* the map as flat point arrays */
+typedef struct orbfe_track_map {
+    const float *d_world_pos, *d_normal;       /* [npoints][3] */
+    const float *d_min_dist, *d_max_dist;      /* GetMinDistanceInvariance / GetMaxDistanceInvariance */
+    const uint8_t *d_bad, *d_obs_gt0;
+    const uint8_t *d_desc;                     /* [npoints][32]; read by the search only */
+    int32_t npoints;
+} orbfe_track_map;
+/* what isInFrustum leaves in a MapPoint: mTrackProjX / Y / XR, mTrackViewCos, mnTrackScaleLevel (level -1: not in view) */
+typedef struct orbfe_track_proj {
+    float u, v, ur, view_cos;
+    int32_t level;
+} orbfe_track_proj;
+/* results of a chain call; d_pairs / d_npairs may be NULL */
+typedef struct orbfe_track_out {
+    orbfe_proj_query *d_q;           /* [nframes][qcap] the queries, compacted in source order */
+    int32_t *d_qsrc;                 /* [nframes][qcap] last-frame feature / map point of each query */
+    int32_t *d_nq;                   /* [nframes] */
+    int32_t qcap;
+    int32_t *d_match, *d_best, *d_second;   /* [nframes][qcap] as orbfe_search_by_projection */
+    int32_t *d_status;               /* [2]: entries needed when ent_cap was too small (else 0); most rounds any frame ran */
+    int32_t *d_assigned;             /* [nframes][cap]: -1 NULL, -2 the MapPoint the slot held before, else the source that took it */
+    int32_t *d_nmatches;             /* [nframes] the reference's return value */
+    int32_t *d_pairs, *d_npairs;     /* [nframes][qcap][2] (source, current feature) in match order; [nframes] their count */
+} orbfe_track_out;
+
+/* Frame::UnprojectStereo (src/Frame.cc:879-899) of every keypoint with d_depth > 0 into d_world_pos [nframes][cap][3] (zeros
+ * elsewhere), and the selection of Tracking::UpdateLastFrame (:1833-1883): sorted by (depth, index), all points up to
+ * th_depth, at least 100, one more than either.  d_keeps [nframes][cap] (may be NULL): the slot holds a MapPoint with
+ * Observations() >= 1; d_created = selected && !keeps.  Localisation-only mode and the mnLastKeyFrameId early return are the
+ * caller's `if`. */
+orbfe_status orbfe_unproject_select_batch_device(orbfe_matcher *m, const orbfe_keypoint *d_kps, const float *d_depth, const int32_t *d_n,
+                                                 int32_t cap, int32_t nframes, const float *d_Tcw, const orbfe_track_camera *cam,
+                                                 float th_depth, const uint8_t *d_keeps, float *d_world_pos, uint8_t *d_created,
+                                                 void *stream);
+/* the gating of the last-frame form (src/ORBmatcher.cc:1590-1644, operation order of the oracle's orc_proj_queries_last_frame):
+ * projection, invzc < 0, closed image bounds, forward / backward level window from tlc against mb (unless mono), r = th *
+ * scale_factors[octave], ur = u - bf * invzc, RIGHT_GATE | CLAIMS iff obs_gt0.  A keypoint whose octave is outside
+ * [0, nlevels) makes no query.  Queries are compacted in feature order (no atomics take a slot); those past qcap are dropped,
+ * d_nq[f] <= qcap.  scale_factors is a HOST array. */
+orbfe_status orbfe_gate_last_frame_batch_device(orbfe_matcher *m, const float *d_Tcw_cur, const orbfe_track_last *last,
+                                                const orbfe_track_camera *cam, float mb, int32_t mono, float th, const float *scale_factors,
+                                                int32_t nlevels, int32_t nframes, orbfe_proj_query *d_q, int32_t *d_qsrc, int32_t *d_nq,
+                                                int32_t qcap, void *stream);
+/* Frame::isInFrustum(pMP, 0.5) (src/Frame.cc:387-451) with MapPoint::PredictScale (src/MapPoint.cc:465-480) and the gating of
+ * SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:63-93) for every frame's list of local map points: frame f's list
+ * is d_list_idx[d_list_off[f] .. d_list_off[f + 1]) (indices into `map`), d_seen[entry] (may be NULL) = mnLastFrameSeen ==
+ * mnId.  d_qsrc holds map point indices; d_visible[f] (may be NULL) = nToMatch; d_proj[nentries] (may be NULL) what
+ * isInFrustum left in each entry's MapPoint.  PcZ == 0 is undefined here as in the reference (NaN passes its bounds test). */
+orbfe_status orbfe_gate_local_map_batch_device(orbfe_matcher *m, const float *d_Tcw, const orbfe_track_camera *cam, float th,
+                                               const float *scale_factors, int32_t nlevels, float log_scale_factor,
+                                               const orbfe_track_map *map, const uint32_t *d_list_off, const int32_t *d_list_idx,
+                                               const uint8_t *d_seen, int64_t nentries, int32_t nframes, orbfe_proj_query *d_q,
+                                               int32_t *d_qsrc, int32_t *d_nq, int32_t qcap, int32_t *d_visible, orbfe_track_proj *d_proj,
+                                               void *stream);
+/* the same arithmetic on the HOST for n points of one frame (no device, no handle): proj[n], in_view[n]; seen / bad may be NULL */
+orbfe_status orbfe_frustum_points(const float *Tcw, const orbfe_track_camera *cam, float log_scale_factor, int32_t nlevels, int32_t n,
+                                  const float *world_pos, const float *normal, const float *min_dist, const float *max_dist,
+                                  const uint8_t *seen, const uint8_t *bad, orbfe_track_proj *proj, uint8_t *in_view);
+/* orbfe_search_by_projection for a batch: query i of frame f is d_q[f * qcap + i], i < d_nq[f] (read on the device), its
+ * descriptor row d_qsrc[f * qcap + i] of the pool d_qpool + f * pool_frame_rows * 32 (pool_frame_rows 0: one pool for all
+ * frames; a row outside [0, pool_rows) finds nothing).  Candidate entries of all frames go into ONE buffer of ent_cap entries
+ * in the matcher's scratch; when it is too small nothing is written past any buffer, d_match is -1 everywhere and
+ * d_status[0] holds the exact need -- call again with it.  inv_level_sigma2 (HOST, may be NULL) as in the _chi2 form. */
+orbfe_status orbfe_search_by_projection_batch_device(orbfe_matcher *m, const orbfe_track_frames *frames, int32_t nframes,
+                                                     const orbfe_proj_query *d_q, const int32_t *d_qsrc, const int32_t *d_nq, int32_t qcap,
+                                                     const uint8_t *d_qpool, int32_t pool_rows, int32_t pool_frame_rows,
+                                                     const float *inv_level_sigma2, int32_t nlevels, int32_t th, float nnratio,
+                                                     int32_t ratio_rule, int64_t ent_cap, int32_t *d_match, int32_t *d_best,
+                                                     int32_t *d_second, int32_t *d_status, void *stream);
+/* what the reference's loop leaves behind, from the core's matches: d_assigned starts from frames->d_slot, a slot takes the
+ * LAST query in order that matched it; with check_ori the 30-bin rotation histogram (angle of d_last_kps[f][source] minus
+ * the current keypoint's) and ComputeThreeMaxima: a slot goes back to -1 if ANY match to it lies in a dropped bin, d_nmatches
+ * = matches - dropped entries (a slot matched twice counts twice, as in the reference). */
+orbfe_status orbfe_track_replay_batch_device(orbfe_matcher *m, const orbfe_track_frames *frames, int32_t nframes, const int32_t *d_match,
+                                             const int32_t *d_qsrc, const int32_t *d_nq, int32_t qcap, const orbfe_keypoint *d_last_kps,
+                                             int32_t cap_last, int32_t check_ori, int32_t *d_assigned, int32_t *d_nmatches,
+                                             int32_t *d_pairs, int32_t *d_npairs, void *stream);
+/* gating -> search -> replay in one call.  Last frame: ratio rule off (:1673), th_high = TH_HIGH; d_pairs feed
+ * orbfe_find_homographies_device as the perfect/ overload's points_last / points_current.  Local map: ratio rule on. */
+orbfe_status orbfe_track_last_frame_batch_device(orbfe_matcher *m, const orbfe_track_frames *cur, const float *d_Tcw_cur,
+                                                 const orbfe_track_last *last, const orbfe_track_camera *cam, float mb, int32_t mono,
+                                                 float th, const float *scale_factors, int32_t nlevels, int32_t th_high, int32_t check_ori,
+                                                 int64_t ent_cap, int32_t nframes, const orbfe_track_out *out, void *stream);
+orbfe_status orbfe_track_local_map_batch_device(orbfe_matcher *m, const orbfe_track_frames *cur, const float *d_Tcw,
+                                                const orbfe_track_camera *cam, float th, const float *scale_factors, int32_t nlevels,
+                                                float log_scale_factor, const orbfe_track_map *map, const uint32_t *d_list_off,
+                                                const int32_t *d_list_idx, const uint8_t *d_seen, int64_t nentries, int32_t th_high,
+                                                float nnratio, int64_t ent_cap, int32_t nframes, const orbfe_track_out *out,
+                                                int32_t *d_visible, orbfe_track_proj *d_proj, void *stream);
+/* bytes of matcher scratch the search takes for (nframes, qcap, ent_cap); -1 outside the limits.  No device needed. */
+int64_t orbfe_track_scratch_bytes(int32_t nframes, int32_t qcap, int64_t ent_cap);
 
 /* Frame::ComputeStereoMatches (src/Frame.cc:642-846): row-band descriptor search in the right image,
  * 11 x 11 SAD refinement over 11 shifts on the two extractors' device-resident pyramids (mvImagePyramid of the LAST

@@ -61,6 +61,9 @@ SYMBOLS = (
     "orbfe_cloud_download", "orbfe_cloud_upload_device", "orbfe_cloud_pose_matrix",
     "orbfe_cloud_outlier_filter_device", "orbfe_cloud_objects_device", "orbfe_cloud_objects", "orbfe_cloud_objects_scratch_bytes",
     "orbfe_objects_create", "orbfe_objects_destroy", "orbfe_objects_merge", "orbfe_objects_size", "orbfe_objects_get", "orbfe_objects_clear",
+    "orbfe_unproject_select_batch_device", "orbfe_gate_last_frame_batch_device", "orbfe_gate_local_map_batch_device", "orbfe_frustum_points",
+    "orbfe_search_by_projection_batch_device", "orbfe_track_replay_batch_device", "orbfe_track_last_frame_batch_device",
+    "orbfe_track_local_map_batch_device", "orbfe_track_scratch_bytes",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -89,6 +92,41 @@ class OrbfeCamera(C.Structure):
 
 
 DEPTH_U16, DEPTH_F32 = 0, 1   # ORBFE_DEPTH_*
+
+
+class TrackCamera(C.Structure):
+    """orbfe_track_camera"""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "minx", "maxx", "miny", "maxy")]
+
+
+class TrackFrames(C.Structure):
+    """orbfe_track_frames: the frames that are searched (device pointers)"""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_n", C.c_void_p), ("cap", C.c_int32), ("d_cell_off", C.c_void_p),
+                ("d_cell_idx", C.c_void_p), ("minx", C.c_float), ("miny", C.c_float), ("gw_inv", C.c_float), ("gh_inv", C.c_float),
+                ("d_uright", C.c_void_p), ("d_slot", C.c_void_p)]
+
+
+class TrackLast(C.Structure):
+    """orbfe_track_last: the "last" frames of the last-frame form"""
+    _fields_ = [("d_kps", C.c_void_p), ("d_n", C.c_void_p), ("cap", C.c_int32), ("d_valid", C.c_void_p), ("d_world_pos", C.c_void_p),
+                ("d_obs_gt0", C.c_void_p), ("d_mpdesc", C.c_void_p), ("d_Tcw", C.c_void_p)]
+
+
+class TrackMap(C.Structure):
+    """orbfe_track_map: the map as flat point arrays"""
+    _fields_ = [("d_world_pos", C.c_void_p), ("d_normal", C.c_void_p), ("d_min_dist", C.c_void_p), ("d_max_dist", C.c_void_p),
+                ("d_bad", C.c_void_p), ("d_obs_gt0", C.c_void_p), ("d_desc", C.c_void_p), ("npoints", C.c_int32)]
+
+
+class TrackOut(C.Structure):
+    """orbfe_track_out: results of a chain call"""
+    _fields_ = [("d_q", C.c_void_p), ("d_qsrc", C.c_void_p), ("d_nq", C.c_void_p), ("qcap", C.c_int32), ("d_match", C.c_void_p),
+                ("d_best", C.c_void_p), ("d_second", C.c_void_p), ("d_status", C.c_void_p), ("d_assigned", C.c_void_p),
+                ("d_nmatches", C.c_void_p), ("d_pairs", C.c_void_p), ("d_npairs", C.c_void_p)]
+
+
+TRACK_PROJ_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("view_cos", "<f4"), ("level", "<i4")])   # orbfe_track_proj
+assert TRACK_PROJ_DTYPE.itemsize == 20
 
 
 def tensor_ptr(t):
@@ -389,6 +427,20 @@ def _configure(L):
     L.orbfe_image_bounds.argtypes = [cam, i32, i32, vp]
     L.orbfe_frame_geometry_batch_device.argtypes = [vp, vp, vp, i32, i32, cam, vp, i32, i32, i32, sz, sz, f32, vp, vp, vp, vp]
     L.orbfe_depth_to_float_device.argtypes = [vp, i32, i32, i32, i32, sz, sz, f32, vp, sz, sz, vp]
+    i64 = C.c_int64
+    tcam, tfr, tlast, tmap, tout = (C.POINTER(t) for t in (TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut))
+    L.orbfe_unproject_select_batch_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, tcam, f32, vp, vp, vp, vp]
+    L.orbfe_gate_last_frame_batch_device.argtypes = [vp, vp, tlast, tcam, f32, i32, f32, vp, i32, i32, vp, vp, vp, i32, vp]
+    L.orbfe_gate_local_map_batch_device.argtypes = [vp, vp, tcam, f32, vp, i32, f32, tmap, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.orbfe_frustum_points.argtypes = [vp, tcam, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_search_by_projection_batch_device.argtypes = [vp, tfr, i32, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, f32, i32, i64, vp, vp,
+                                                          vp, vp, vp]
+    L.orbfe_track_replay_batch_device.argtypes = [vp, tfr, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.orbfe_track_last_frame_batch_device.argtypes = [vp, tfr, vp, tlast, tcam, f32, i32, f32, vp, i32, i32, i32, i64, i32, tout, vp]
+    L.orbfe_track_local_map_batch_device.argtypes = [vp, tfr, vp, tcam, f32, vp, i32, f32, tmap, vp, vp, vp, i64, i32, f32, i64, i32, tout,
+                                                     vp, vp, vp]
+    L.orbfe_track_scratch_bytes.argtypes = [i32, i32, i64]
+    L.orbfe_track_scratch_bytes.restype = i64
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default -> orbfe_status / int32

@@ -1,5 +1,6 @@
 // orbfe_matcher.h -- the matcher handle, shared by the translation units that implement its entry points (orbfe_match.hip,
-// orbfe_grid.hip, orbfe_projection.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip.  Host only.
+// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip.
+// Host only.
 #pragma once
 
 #include "orbfe_common.h"
