@@ -572,7 +572,10 @@ orbfe_status orbfe_gate_last_frame_batch_device(orbfe_matcher *m, const float *d
  * SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:63-93) for every frame's list of local map points: frame f's list
  * is d_list_idx[d_list_off[f] .. d_list_off[f + 1]) (indices into `map`), d_seen[entry] (may be NULL) = mnLastFrameSeen ==
  * mnId.  d_qsrc holds map point indices; d_visible[f] (may be NULL) = nToMatch; d_proj[nentries] (may be NULL) what
- * isInFrustum left in each entry's MapPoint.  PcZ == 0 is undefined here as in the reference (NaN passes its bounds test). */
+ * isInFrustum left in each entry's MapPoint.  An entry whose index is outside [0, map->npoints) makes no query and leaves
+ * level -1 and zeros in d_proj, like an entry that is seen, bad or out of view.  Offsets beyond nentries are cut there (a
+ * list that starts beyond it is empty); queries past qcap are dropped, d_nq[f] <= qcap, while d_visible[f] keeps the full
+ * count.  PcZ == 0 is undefined here as in the reference (NaN passes its bounds test). */
 orbfe_status orbfe_gate_local_map_batch_device(orbfe_matcher *m, const float *d_Tcw, const orbfe_track_camera *cam, float th,
                                                const float *scale_factors, int32_t nlevels, float log_scale_factor,
                                                const orbfe_track_map *map, const uint32_t *d_list_off, const int32_t *d_list_idx,
