@@ -1479,7 +1479,12 @@ orbfe_status orbfe_initializer_initialize(orbfe_initializer *h, const float *key
 /* Many pairs in one call on the caller's stream, everything in device memory, no synchronisation: d_offsets1 / d_offsets2 int32
  * [npairs + 1] are the CSR offsets of the pairs' keys in d_keys1_xy / d_keys2_xy; d_matches12, d_P3D, d_triangulated follow
  * d_offsets1 (the matches can be a row of the device matcher's output block as it stands: -1 = none).  A pair the host form
- * would have refused gets result.status != 0 and ok = 0; nothing else of it is written.  The host reads only the pointers. */
+ * would have refused gets result.status != 0 and ok = 0; nothing else of it is written.  The host reads only the pointers.
+ * A pair without keys in either frame (n1 = 0 or n2 = 0, its matches all < 0) is ORBFE_INIT_FEW_MATCHES like any pair of fewer
+ * than 8 matches: its (possibly empty) slices of d_P3D / d_triangulated keep what they held.  A pair fits when offsets1[p + 1] <=
+ * max_matches: a batch may end exactly at max_matches; a pair that ends past it is ORBFE_INIT_BAD_SIZES, the pairs before it run.
+ * Pairs may differ in `iterations` (1 .. ORBFE_INIT_MAX_ITERATIONS side by side), and a handle may run batches of any order and
+ * size one after the other: a pair reads only what the same call wrote into the handle's scratch. */
 orbfe_status orbfe_initializer_initialize_device(orbfe_initializer *h, const int32_t *d_offsets1, const int32_t *d_offsets2,
                                                  const float *d_keys1_xy, const float *d_keys2_xy, const int32_t *d_matches12,
                                                  const orbfe_initializer_pair *d_pairs, const int32_t *d_draws, int32_t npairs,
@@ -1491,7 +1496,10 @@ orbfe_status orbfe_initializer_initialize_device(orbfe_initializer *h, const int
  *   1 ORBFE_INIT_TAP_MATCHES     float [N][9] per compacted match: chiSquare1, chiSquare2 of CheckHomography and of
  *                                CheckFundamental for the models of iteration `iteration`, then p3dC1 [3], cosParallax and the
  *                                stage at which CheckRT dropped the match (ORBFE_INIT_RT_*, as a float) for hypothesis
- *                                `hypothesis`, both chosen BEFORE the call; ORBFE_ERR_STATE if that iteration did not run */
+ *                                `hypothesis`, both chosen BEFORE the call; ORBFE_ERR_STATE if that iteration did not run
+ * A pair at or past ORBFE_INIT_TAP_SETS (or past the handle's max_pairs, or of no call yet) has no tap: ORBFE_ERR_STATE; its
+ * result, points and flags are those of any other pair.  ORBFE_INIT_TAP_ITERS = ORBFE_INIT_MAX_ITERATIONS: every iteration of
+ * a tapped pair has its record.  A NaN in a tap is a NaN of the reference's arithmetic at that place; its payload is not. */
 enum { ORBFE_INIT_TAP_ITERATIONS = 0, ORBFE_INIT_TAP_MATCHES = 1 };
 enum {
     ORBFE_INIT_RT_OUTLIER = 0, ORBFE_INIT_RT_NONFINITE = 1, ORBFE_INIT_RT_DEPTH1 = 2, ORBFE_INIT_RT_DEPTH2 = 3, ORBFE_INIT_RT_ERROR1 = 4,
