@@ -253,8 +253,8 @@ orbfe_status orbfe_match_bf(orbfe_matcher *m, const uint8_t *q, int32_t nq, cons
                             int32_t check_ori, int32_t *match_q2t, int32_t *best, int32_t *second,
                             int32_t *nmatches);
 void *orbfe_matcher_get_stream(orbfe_matcher *m);
-/* all-pairs kernel behind the three orbfe_match_bf* calls: 0 (default) = exact int8 dot product on the matrix cores
- * (dot = 128 * (128 - hamming)), 1 = xor / popcount.  Results are identical; see DESIGN.md for the measured A/B. */
+/* all-pairs kernel behind the three orbfe_match_bf* calls: 0 (default) = exact FP4 dot product on the matrix cores
+ * (every bit a +-1, dot = 256 - 2 * hamming, v_mfma_scale_f32_32x32x64_f8f6f4), 1 = xor / popcount.  Results are identical; see DESIGN.md for the measured A/B. */
 orbfe_status orbfe_matcher_set_bf_kernel(orbfe_matcher *m, int32_t kernel);
 /* orbfe_search_by_projection(_chi2): 0 (default) = the whole search in ONE launch (k_proj_fused: per-query slabs, round 0 of the
  * relaxation decided while the candidates are written, the last workgroup finishes the rounds, results stored straight into

@@ -7,7 +7,7 @@
 //   rotation histogram + prune         src/ORBmatcher.cc:308-316, :338-360
 //   ComputeThreeMaxima                 src/ORBmatcher.cc:1912-1957
 // Candidate-list matchers (SearchByBoW, CSR Hamming, stereo, BoW descent, distinctive descriptors): xor + v_bcnt_u32_b32.
-// All-pairs brute force (M3): by default an EXACT int8 dot product on the matrix cores (k_match_bf); the xor / popcount
+// All-pairs brute force (M3): by default an EXACT FP4 dot product on the matrix cores (k_match_bf); the xor / popcount
 // all-pairs kernel the north star names is kept as k_match_popc (orbfe_matcher_set_bf_kernel), bit-identical, slower
 // (profiles/r02_match_variants.json).  No CPU path.
 #include <stddef.h>
@@ -24,50 +24,60 @@
 // ---------------------------------------------------------------------------------------------------
 // K8  brute force on the matrix cores.
 //
-// All-pairs Hamming is a GEMM in disguise: with every query bit mapped to the int8 value 2b-1 and every train bit
-// to 64(2b-1),
-//     dot(t', q') = 64 * (256 - 2 * hamming(q, t)) = 128 * (128 - d),
-// exact in int32.  v_mfma_i32_32x32x32_i8 evaluates a 32 x 32 tile of such dots over 32 bit positions per
-// instruction; 8 of them cover the 256 bits.  The accumulators do not start at zero but at a 7-bit "field"
-// 32 - (train row inside the tile), so an accumulator IS the ranking key
-//     key = 128 * (128 - d) + field                      (larger = closer, earlier row wins ties)
-// and all that is left for the VALU is to keep, per query, the two largest keys: 2.5 instructions per distance
-// instead of the 20 of an xor/popcount loop.  The best key gives (distance, lowest index) and the second key the
-// second-smallest distance with multiplicity, which is exactly what the reference's sequential
+// All-pairs Hamming is a GEMM in disguise: with every descriptor bit b mapped to 2b-1 on both sides,
+//     dot(t', q') = 256 - 2 * hamming(q, t).
+// +-1 needs one bit of operand, and the narrowest operand the matrix cores take is FP4 (E2M1), which holds +-1 exactly:
+// v_mfma_scale_f32_32x32x64_f8f6f4 with FP4 on both sides evaluates a 32 x 32 tile of such dots over 64 bit positions per
+// instruction, 4 of them cover the 256 bits, and the E8M0 block scales (2^5 on the train side, 1 on the query side; powers
+// of two, exact) multiply the dot by 32.  Every partial sum is an integer below 2^17, exact in the fp32 accumulator.
+// The accumulators do not start at zero but at (32 - train row inside the tile) + an offset, so that the fp32 BIT PATTERN
+// of an accumulator IS the ranking key (orbfe_match_dev.h, bm_key_*; pinned by a static_assert over every distance and row)
+//     bits = 0x47000000 + ((64 * (256 - d) + field) << 8)              (larger = closer, earlier row wins ties)
+// and all that is left for the VALU is to keep, per query, the two largest keys as integers: 2.5 instructions per distance
+// instead of the 20 of an xor/popcount loop, and no convert.  The best key gives (distance, lowest index) and the second key
+// the second-smallest distance with multiplicity, which is exactly what the reference's sequential
 //     if (d < best) {second = best; best = d; idx = j;} else if (d < second) second = d;
-// produces.  Between train tiles the field of the running keys is forced to 127 (an older row beats any newer
+// produces.  Between train tiles the field of the running keys is forced to 63 (an older row beats any newer
 // one on equal distance) and the global index of the best is latched whenever the best key changed in a tile.
 //
 // Workgroup = 4 waves x BM_Q query tiles of 32 (BM_Q = 4: 512 queries); the train descriptors stream through LDS in tiles of
-// 32 rows, expanded bit -> +-64 byte on the way in (8-byte table look-up per source byte) and laid out so that the
-// A operand of lane (row r, k-half h) at k-step s is one conflict-free ds_read_b128 at ((2s + h) * 32 + r) * 16.
-// The query tiles (B operands, 32 VGPRs each) are expanded once and stay in registers.  The bit -> k assignment is
-// the same on both sides, which is all a dot product needs.
+// 32 rows (4 KB per buffer), expanded bit -> nibble on the way in (one table dword per source byte, one ds_write_b128 per
+// source dword) and laid out so that the A operand of lane (row r, k-half h) at k-step s is one conflict-free ds_read_b128 at
+// ((2s + h) * 32 + r) * 16.  The query tiles (B operands, 16 VGPRs each) are expanded once through the same table and stay in
+// registers.  Lane (r, h) holds source dword 4h + s of its row at k-step s on both sides, nibble for nibble in the same
+// order, and every block scale of a side is the same number, so whatever k the hardware gives an operand position, the dot
+// product pairs bit i with bit i.
 // The wave is software-pipelined: the MFMA chain of the next query tile (at the end of a train tile: of query tile 0
 // of the next train tile) is issued between the ranking instructions of the current one.
-// BM_Q is a template parameter, instantiated for 4 (the default of every caller), 2 and 1: 253, 176 and 101 VGPRs under the same
-// launch bound.  A workgroup needs its registers on all four SIMDs of one CU at once; beside the dense FAST pass (three resident
-// workgroups of 160 registers per SIMD) the 4-tile form waits until two of them have left, the 2-tile form fits where one has
-// (176 + 2 x 160 <= 512).  Fewer tiles re-read every train tile from the LDS more often per MFMA; the results are the same bytes.
+// BM_Q is a template parameter, instantiated for 4 (the default of every caller), 2 and 1 under the same launch bound; the
+// register counts (174, 133, 87) are in DESIGN.md sections 4 and 6.  A workgroup needs its registers on all four SIMDs of one CU at
+// once; beside the dense FAST pass (three resident workgroups of 160 registers per SIMD) the 4-tile form fits where one of them
+// has left (174 + 2 x 160 <= 512).  Fewer tiles re-read every train tile from the LDS more often per MFMA; the results are the
+// same bytes.
 // ---------------------------------------------------------------------------------------------------
 #define BM_WAVES 4
 #define BM_QUERIES(Q) (BM_WAVES * (Q) * 32)   // queries of a workgroup of Q tiles per wave
-#define BM_NEG (-(1 << 30))
 #define BM_MAX_NT (1 << 22)  // the index is latched as a plain int; only nt * 32 bytes must be addressable in 32 bits
 
 typedef int bm_v4i __attribute__((ext_vector_type(4)));
 typedef int bm_v16i __attribute__((ext_vector_type(16)));
+typedef float bm_v16f __attribute__((ext_vector_type(16)));
 
-// bit b of v -> byte b: +mag if set, -mag if clear (two dwords for the 8 bits)
-__device__ __forceinline__ uint2 bm_expand_byte(uint32_t v, uint32_t mag)
+// bit b of v -> nibble b: FP4 +1 if set, -1 if clear (one dword for the 8 bits)
+__device__ __forceinline__ uint32_t bm_expand_byte(uint32_t v)
 {
-    uint32_t lo = 0, hi = 0;
+    uint32_t e = 0;
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        lo |= (((v >> b) & 1u) ? mag : (0x100u - mag)) << (8 * b);
-        hi |= (((v >> (4 + b)) & 1u) ? mag : (0x100u - mag)) << (8 * b);
-    }
-    return make_uint2(lo, hi);
+    for (int b = 0; b < 8; ++b) e |= (((v >> b) & 1u) ? BM_FP4_POS : BM_FP4_NEG) << (4 * b);
+    return e;
+}
+
+// one k-step of the chain: 64 bit positions, FP4 x FP4 (cbsz 4, blgp 4: the low 4 registers of each operand are read)
+__device__ __forceinline__ bm_v16f bm_mfma_fp4(const bm_v4i &a, const bm_v4i &b, const bm_v16f &acc)
+{
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(__builtin_shufflevector(a, a, 0, 1, 2, 3, -1, -1, -1, -1),
+                                                           __builtin_shufflevector(b, b, 0, 1, 2, 3, -1, -1, -1, -1), acc, 4, 4, 0,
+                                                           (int)BM_SCALE_TRAIN, 0, (int)BM_SCALE_QUERY);
 }
 
 template <int BM_Q>
@@ -81,8 +91,8 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
                                                                int32_t *__restrict__ match, int32_t *__restrict__ best_o,
                                                                int32_t *__restrict__ second_o)
 {
-    __shared__ uint2 s_tabq[256], s_tabt[256];  // query bits -> +-1, train bits -> +-64
-    __shared__ __attribute__((aligned(16))) uint8_t s_tile[2][32 * 256];
+    __shared__ uint32_t s_tab[256];  // source byte -> 8 FP4 nibbles of +-1 (both sides)
+    __shared__ __attribute__((aligned(16))) uint8_t s_tile[2][32 * 128];
     const int pair = blockIdx.y;
     const uint8_t *q = q_base, *t = t_base;
     int nq = nq_s, nt = nt_s;
@@ -109,30 +119,26 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
         }
         return;
     }
-    s_tabq[tid] = bm_expand_byte((uint32_t)tid, 1u);
-    s_tabt[tid] = bm_expand_byte((uint32_t)tid, 64u);
+    s_tab[tid] = bm_expand_byte((uint32_t)tid);
     __syncthreads();
 
     const int c = lane & 31, h = lane >> 5;
-    // ---- B operands: BM_Q query tiles, lane (c, h) holds bits [128h, 128h + 128) of query c as 8 x 16 bytes ----
-    bm_v4i B[BM_Q][8];
+    // ---- B operands: BM_Q query tiles, lane (c, h) holds bits [128h, 128h + 128) of query c as 4 x 16 bytes ----
+    bm_v4i B[BM_Q][4];
 #pragma unroll
     for (int u = 0; u < BM_Q; ++u) {
         const int qi = q0 + (wid * BM_Q + u) * 32 + c;
         const uint4 raw = *(const uint4 *)(q + (int64_t)min(qi, nq - 1) * 32 + h * 16);
         const uint32_t rw[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
-        for (int sstep = 0; sstep < 8; ++sstep) {
-            const uint32_t b0 = (rw[sstep >> 1] >> (16 * (sstep & 1))) & 0xFFu;
-            const uint32_t b1 = (rw[sstep >> 1] >> (16 * (sstep & 1) + 8)) & 0xFFu;
-            const uint2 e0 = s_tabq[b0], e1 = s_tabq[b1];
-            B[u][sstep] = bm_v4i{(int)e0.x, (int)e0.y, (int)e1.x, (int)e1.y};
-        }
+        for (int sstep = 0; sstep < 4; ++sstep)
+            B[u][sstep] = bm_v4i{(int)s_tab[rw[sstep] & 0xFFu], (int)s_tab[(rw[sstep] >> 8) & 0xFFu],
+                                 (int)s_tab[(rw[sstep] >> 16) & 0xFFu], (int)s_tab[rw[sstep] >> 24]};
     }
     int kb[BM_Q], ks[BM_Q], bi[BM_Q];
 #pragma unroll
     for (int u = 0; u < BM_Q; ++u) {
-        kb[u] = ks[u] = BM_NEG;
+        kb[u] = ks[u] = BM_KEY_NONE;
         bi[u] = -1;
     }
     if (nt > 0) {
@@ -141,34 +147,31 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
         const uint32_t *t32 = (const uint32_t *)t;
         // rows past the end re-read the last row: their keys are masked in the last tile
         auto stage_load = [&](int T) -> uint32_t { return t32[(uint32_t)(min(T + sr, nt - 1) * 8 + sw)]; };
+        // source dword sw = 4 hh + s of row sr is the 16 bytes lane (sr, hh) reads at k-step s
         auto stage_store = [&](uint32_t dw, int buf) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int beta = 4 * sw + i, hh = beta >> 4, bp = beta & 15;
-                const int off = (((bp >> 1) * 2 + hh) * 32 + sr) * 16 + (bp & 1) * 8;
-                *(uint2 *)(s_tile[buf] + off) = s_tabt[(dw >> (8 * i)) & 0xFFu];
-            }
+            const int off = (((sw & 3) * 2 + (sw >> 2)) * 32 + sr) * 16;
+            *(uint4 *)(s_tile[buf] + off) = make_uint4(s_tab[dw & 0xFFu], s_tab[(dw >> 8) & 0xFFu], s_tab[(dw >> 16) & 0xFFu], s_tab[dw >> 24]);
         };
-        auto load_a = [&](bm_v4i (&A)[8], int buf) {
+        auto load_a = [&](bm_v4i (&A)[4], int buf) {
 #pragma unroll
-            for (int sstep = 0; sstep < 8; ++sstep)
+            for (int sstep = 0; sstep < 4; ++sstep)
                 A[sstep] = *(const bm_v4i *)(s_tile[buf] + ((sstep * 2 + h) * 32 + c) * 16);
         };
-        // accumulator start values = key fields: 32 - (train row of the accumulator inside the tile)
-        bm_v16i cfull;
+        // accumulator start values: the key of (no agreeing bit yet, train row of the accumulator inside the tile)
+        bm_v16f cfull;
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) cfull[reg] = 32 - ((reg & 3) + 8 * (reg >> 2) + 4 * h);
-        auto chain = [&](const bm_v4i (&A)[8], const bm_v4i (&Bu)[8]) -> bm_v16i {
-            bm_v16i acc = cfull;
+        for (int reg = 0; reg < 16; ++reg) cfull[reg] = bm_key_start((reg & 3) + 8 * (reg >> 2) + 4 * h);
+        auto chain = [&](const bm_v4i (&A)[4], const bm_v4i (&Bu)[4]) -> bm_v16i {
+            bm_v16f acc = cfull;
 #pragma unroll
-            for (int sstep = 0; sstep < 8; ++sstep) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[sstep], Bu[sstep], acc, 0, 0, 0);
-            return acc;
+            for (int sstep = 0; sstep < 4; ++sstep) acc = bm_mfma_fp4(A[sstep], Bu[sstep], acc);
+            return __builtin_bit_cast(bm_v16i, acc);  // the fp32 patterns are the keys
         };
         auto interleave = [&]() {
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);  // five VALU
+            for (int g = 0; g < 4; ++g) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x002, 13, 0);  // a quarter of the ranking VALU
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -181,8 +184,8 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
             for (int p = 0; p < 8; ++p) {
                 int k0 = acc[2 * p], k1 = acc[2 * p + 1];
                 if (mask_tail) {
-                    if (T + ((2 * p) & 3) + 8 * ((2 * p) >> 2) + 4 * h >= nt) k0 = BM_NEG;
-                    if (T + ((2 * p + 1) & 3) + 8 * ((2 * p + 1) >> 2) + 4 * h >= nt) k1 = BM_NEG;
+                    if (T + ((2 * p) & 3) + 8 * ((2 * p) >> 2) + 4 * h >= nt) k0 = BM_KEY_NONE;
+                    if (T + ((2 * p + 1) & 3) + 8 * ((2 * p + 1) >> 2) + 4 * h >= nt) k1 = BM_KEY_NONE;
                 }
                 hi[p] = max(k0, k1);
                 lo[p] = min(k0, k1);
@@ -195,10 +198,10 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
                     lo[p] = max(min(hi[p], hi[p + w]), max(lo[p], lo[p + w]));
                     hi[p] = h2;
                 }
-            const int bprev = kb[u] | 127, sprev = ks[u] | 127;
+            const int bprev = kb[u] | BM_KEY_FORCE, sprev = ks[u] | BM_KEY_FORCE;
             const int b = max(bprev, hi[0]);
             const int s2 = max(min(bprev, hi[0]), max(sprev, lo[0]));
-            if (b != bprev) bi[u] = T + 32 - (b & 127);
+            if (b != bprev) bi[u] = T + bm_key_row(b);
             kb[u] = b;
             ks[u] = s2;
         };
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
         stage_store(stage_load(0), 0);
         uint32_t g1 = stage_load(32);  // source dword of the tile after next, fetched two tiles before it is consumed
         __syncthreads();
-        bm_v4i A[8];
+        bm_v4i A[4];
         load_a(A, 0);
         bm_v16i acc = chain(A, B[0]);
         int buf = 0, T = 0;
@@ -242,15 +245,15 @@ __global__ __launch_bounds__(BM_WAVES * 64, 2) void k_match_bf(const uint8_t *__
 #pragma unroll
     for (int u = 0; u < BM_Q; ++u) {
         const int ob = __shfl_xor(kb[u], 32, 64), os = __shfl_xor(ks[u], 32, 64), oi = __shfl_xor(bi[u], 32, 64);
-        // distance part of a key: m = 128 - d (sentinels stay far below)
-        const int mb = kb[u] >> 7, mo = ob >> 7;
+        // distance part of a key: larger = closer, 0 where no key was seen
+        const int mb = bm_key_m(kb[u]), mo = bm_key_m(ob);
         const bool take_o = mo > mb || (mo == mb && oi >= 0 && (bi[u] < 0 || oi < bi[u]));
         const int m1 = take_o ? mo : mb, idx = take_o ? oi : bi[u];
-        const int m2 = max(min(mb, mo), max(ks[u] >> 7, os >> 7));
+        const int m2 = max(min(mb, mo), max(bm_key_m(ks[u]), bm_key_m(os)));
         const int qi = q0 + (wid * BM_Q + u) * 32 + c;
         if (h == 0 && qi < nslots) {
-            const int best = idx >= 0 ? 128 - m1 : 256;
-            const int second = m2 > (BM_NEG >> 8) ? 128 - m2 : 256;
+            const int best = idx >= 0 ? bm_m_dist(m1) : 256;
+            const int second = m2 > 0 ? bm_m_dist(m2) : 256;
             const bool valid = qi < nq;
             int m = -1;
             // best < 256: with the reference's initial bestDist = 256 a row at distance 256 never becomes the best

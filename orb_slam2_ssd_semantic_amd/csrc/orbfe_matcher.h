@@ -11,7 +11,7 @@ struct orbfe_matcher {
     hipStream_t stream = nullptr;
     DevBuf b[16];
     bool own_stream = true;  // false: the stream belongs to a pipeline (orbfe_internal_matcher_create_on_stream)
-    int bf_kernel = 0;  // 0 = k_match_bf (int8 dot product on the matrix cores), 1 = k_match_popc (xor / popcount)
+    int bf_kernel = 0;  // 0 = k_match_bf (FP4 dot product on the matrix cores), 1 = k_match_popc (xor / popcount)
     int bf_tiles = 4;   // query tiles per wave of k_match_bf: 4, 2 or 1 (orbfe_internal_matcher_set_bf_tiles)
     // Device entry points that use the scratch blocks b[] run on the CALLER's stream: one that arrives on another stream
     // than its predecessor waits (at stream level) for the event recorded behind that predecessor's last launch.

@@ -102,13 +102,14 @@ static inline bool orb_pipe_plan(int32_t P, int32_t Q, bool copies, OrbPipePlan 
 // descriptor, FAST on kernel stream 1 and the side stream in turn
 #define ORBFE_PIPE_LANE_PLACE 1        // what a route (orbfe_pipe_graph.h) that is given no placement takes
 #ifndef ORBFE_PIPE_LANE_PLACE_AUTO
-#define ORBFE_PIPE_LANE_PLACE_AUTO 2   // what a pipeline left to itself asks its routes for: with 2-tile matchers +2.4 % over
-                                       // placement 1, with 4-tile matchers -5 % (profiles/pipe_fast2.md)
+#define ORBFE_PIPE_LANE_PLACE_AUTO 2   // what a pipeline left to itself asks its routes for: +2.4 % over placement 1 with a matcher
+                                       // that fits beside two FAST workgroups, -5 % with one that does not (profiles/pipe_fast2.md)
 #endif
 #ifndef ORBFE_PIPE_LANE_MATCH_TILES
-#define ORBFE_PIPE_LANE_MATCH_TILES 2  // query tiles per wave of a lane call's brute-force matcher (4, 2, 1: orbfe_match.hip): fewer
-                                       // tiles are fewer registers, and with 2 a workgroup fits where ONE FAST workgroup has left.
-                                       // Measured with placement 1 / 2: 4 tiles 0 / -5.1 %, 2 tiles +0.1 / +2.4 %, 1 tile -3.2 / -0.7 %
+#define ORBFE_PIPE_LANE_MATCH_TILES 4  // query tiles per wave of a lane call's brute-force matcher (4, 2, 1: orbfe_match.hip): fewer
+                                       // tiles are fewer registers.  The FP4 kernel's 4-tile form (174 registers) fits where ONE FAST
+                                       // workgroup has left, which only the 2-tile form of the int8 kernel (176 against 253) did.
+                                       // Measured with placement 2 (profiles/match_fp4.md): 4 tiles +1.1 % over 2, 1 tile -1.3 %
 #endif
 #define ORBFE_PIPE_LANE_PLACES 3       // placements 0 .. 2
 #define ORBFE_PIPE_LANES_AUTO 1        // what a pipeline left to itself does where the rule allows lanes: 1 lanes, 0 chains

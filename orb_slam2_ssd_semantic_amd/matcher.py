@@ -99,7 +99,7 @@ class ORBmatcher(Handle):
         return m, n.value
 
     def set_bf_kernel(self, kernel):
-        """0 = matrix-core int8 dot product (default), 1 = xor / popcount: same results (orbfe_matcher_set_bf_kernel)"""
+        """0 = matrix-core FP4 dot product (default; every bit a +-1, exact), 1 = xor / popcount: same results (orbfe_matcher_set_bf_kernel)"""
         check(self._L.orbfe_matcher_set_bf_kernel(self._m, int(kernel)), "orbfe_matcher_set_bf_kernel")
 
     def set_bf_tiles(self, tiles):
