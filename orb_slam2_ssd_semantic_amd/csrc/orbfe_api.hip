@@ -711,9 +711,9 @@ static orbfe_status extract_host(orbfe_handle *h, const uint8_t *const *grays, i
     // Output set k on the device.  When the results go through the handle's pinned staging (the online call), the three
     // arrays are pieces of ONE block -- keypoints | descriptors | counts -- so that they come back in one D2H copy instead
     // of three (each copy is a ~7 us round trip on the stream of a call that takes 0.25 ms in all).
-    const size_t kb = (sizeof(orbfe_keypoint) * (size_t)cap * nbmax + 255) & ~(size_t)255;
-    const size_t db = ((size_t)32 * cap * nbmax + 255) & ~(size_t)255;
-    const size_t cb = (sizeof(int32_t) * nbmax + 255) & ~(size_t)255;
+    const size_t kb = orb_align256(sizeof(orbfe_keypoint) * (size_t)cap * nbmax);
+    const size_t db = orb_align256((size_t)32 * cap * nbmax);
+    const size_t cb = orb_align256(sizeof(int32_t) * nbmax);
     // ORBFE_OPT_REUSE_IDENTICAL_INPUT: perfect/src/Tracking.cc:685 and :716 build two Frames from the SAME mImGray with the same
     // extractor (the second with the dynamic-object mask, which operator() ignores): the second extraction is the first one's
     // result.  The previous frame sits in the pinned staging block (pitch-aligned rows) and its results in the pinned result

@@ -297,12 +297,8 @@ extern "C" orbfe_status orbfe_features_in_area(orbfe_matcher *m, const float *xy
         orbfe_set_error("bad argument to orbfe_features_in_area");
         return ORBFE_ERR_ARG;
     }
+    if (!orb_grid_csr_ok(cell_off, cell_idx, n, "n")) return ORBFE_ERR_ARG;
     const uint32_t nin = cell_off[GRID_NC];
-    if (nin > (uint32_t)n) { orbfe_set_error("cell_off inconsistent with n"); return ORBFE_ERR_ARG; }
-    for (int c = 0; c < GRID_NC; ++c)
-        if (cell_off[c + 1] < cell_off[c]) { orbfe_set_error("cell_off must not decrease"); return ORBFE_ERR_ARG; }
-    for (uint32_t k = 0; k < nin; ++k)
-        if (cell_idx[k] >= (uint32_t)n) { orbfe_set_error("cell_idx out of range"); return ORBFE_ERR_ARG; }
     off[0] = 0;
     if (nq == 0) return ORBFE_OK;
     DeviceGuard g(m->device);

@@ -54,6 +54,9 @@ static inline orbfe_status orb_resolve_device(int32_t *device)
     return ORBFE_OK;
 }
 
+// the allocation step of the device buffers, and the alignment of the pieces packed into one
+static inline size_t orb_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 // device buffer that only grows (in steps of 256 bytes)
 struct DevBuf {
     void *p = nullptr;
@@ -71,7 +74,7 @@ struct DevBuf {
             bytes = 0;
             if (e != hipSuccess) return e;
         }
-        need = (need + 255) & ~(size_t)255;
+        need = orb_align256(need);
         hipError_t e = hipMalloc(&p, need);
         if (e == hipSuccess) bytes = need;
         return e;

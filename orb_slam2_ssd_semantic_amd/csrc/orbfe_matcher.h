@@ -1,6 +1,7 @@
 // orbfe_matcher.h -- the matcher handle, shared by the translation units that implement its entry points (orbfe_match.hip,
-// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip.
-// Host only.
+// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip,
+// with what more than one of them does to it: the scratch hand-over between streams, the pinned input staging (stage_upload) and
+// the check of a caller's grid (orb_grid_csr_ok).  Host only; the device side the projection searches share is orbfe_proj_dev.h.
 #pragma once
 
 #include "orbfe_common.h"
@@ -39,6 +40,46 @@ static inline hipError_t scratch_release(orbfe_matcher *m, hipStream_t st)
     m->scratch_stream = st;
     m->scratch_used = true;
     return hipEventRecord(m->ev_scratch, st);
+}
+
+// The input staging of the latency-bound host-buffer calls (one pageable copy per array costs more than their kernels): the N
+// pieces are packed into pin_in at 256-byte aligned offsets in list order, go to b[0] in ONE upload on `st`, and dev[i] is the
+// device address of piece i.  A piece of 0 bytes takes no room and is not copied; its address is not to be used.
+struct StagePiece {
+    const void *src;
+    size_t bytes;
+    const void *src2 = nullptr;   // a second array right behind the first, in the same piece
+    size_t bytes2 = 0;
+};
+template <int N>
+static inline hipError_t stage_upload(orbfe_matcher *m, hipStream_t st, const StagePiece (&piece)[N], const char *(&dev)[N])
+{
+    size_t at[N + 1];
+    at[0] = 0;
+    for (int i = 0; i < N; ++i) at[i + 1] = orb_align256(at[i] + piece[i].bytes + piece[i].bytes2);
+    hipError_t e = m->pin_in.ensure(at[N]);
+    if (e == hipSuccess) e = m->b[0].ensure(at[N]);
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < N; ++i) {
+        if (piece[i].bytes) memcpy(m->pin_in.as<char>() + at[i], piece[i].src, piece[i].bytes);
+        if (piece[i].bytes2) memcpy(m->pin_in.as<char>() + at[i] + piece[i].bytes, piece[i].src2, piece[i].bytes2);
+        dev[i] = m->b[0].as<const char>() + at[i];
+    }
+    return hipMemcpyAsync(m->b[0].p, m->pin_in.p, at[N], hipMemcpyHostToDevice, st);
+}
+
+// A caller's grid in CSR form (cell_off[cells + 1], cell_idx[cell_off[cells]]) over n features: false, with the error text
+// set, when a kernel could leave the arrays through it.  `n_name` is the name of n in the caller's argument list.
+static inline bool orb_grid_csr_ok(const uint32_t *cell_off, const uint32_t *cell_idx, int32_t n, const char *n_name)
+{
+    const int nc = ORBFE_GRID_COLS * ORBFE_GRID_ROWS;
+    const uint32_t nin = cell_off[nc];
+    if (nin > (uint32_t)n) { orbfe_set_error("cell_off inconsistent with %s", n_name); return false; }
+    for (int c = 0; c < nc; ++c)
+        if (cell_off[c + 1] < cell_off[c]) { orbfe_set_error("cell_off must not decrease"); return false; }
+    for (uint32_t k = 0; k < nin; ++k)
+        if (cell_idx[k] >= (uint32_t)n) { orbfe_set_error("cell_idx out of range"); return false; }
+    return true;
 }
 
 // a matcher for a pipe of orbfe_pipeline: `st` (the pipe's stream) is its own stream and stays the pipeline's

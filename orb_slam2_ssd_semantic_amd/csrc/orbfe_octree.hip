@@ -1,5 +1,6 @@
 // orbfe_octree.hip -- K3, DistributeOctTree on the device (k_octree).
 #include "orbfe_kernels_dev.h"
+#include "orbfe_host.h"
 
 // ---------------------------------------------------------------------------------------------------
 // K3  DistributeOctTree on the device.  One workgroup per (frame, level).
@@ -101,7 +102,7 @@ __device__ __forceinline__ void qt_carve(char *lds, char *nodes, int M, int nroo
     q.cflag = (uint32_t *)p;
 }
 
-size_t orbk_octree_node_bytes(int M) { return (((size_t)qt_pow2(M) * 8 + (size_t)M * (16 + 8 + 8 + 20)) + 255) & ~(size_t)255; }
+size_t orbk_octree_node_bytes(int M) { return orb_align256((size_t)qt_pow2(M) * 8 + (size_t)M * (16 + 8 + 8 + 20)); }
 static size_t octree_table_bytes(int nroots, int w, int h, int ncells)
 {
     return (size_t)nroots * FF_PER_ROOT * 4 + 64 * 4 + (size_t)(((w + 1) & ~1) + ((h + 1) & ~1)) * 2 + (size_t)((ncells + 31) / 32) * 4;

@@ -1,6 +1,9 @@
-// orbfe_proj_dev.h -- the device side of the projection-gated search that orbfe_projection.hip (one frame, host buffers) and
-// orbfe_track.hip (a batch of frames, device-resident) share: the argument block, the cell rectangle of GetFeaturesInArea and the
-// walk over it.  The library is built without relocatable device code, so every kernel gets its own inlined copy.
+// orbfe_proj_dev.h -- the device side of the projection-gated search, once, for orbfe_projection.hip (one frame, host buffers) and
+// orbfe_track.hip (a batch of frames, device-resident), in the order it runs: the argument block, the cell rectangle
+// (proj_rect), the walk (proj_walk), the count (proj_count), the gates (proj_gate_skip) and the distance (proj_dist), the
+// two-smallest merge (proj_reduce2), the acceptance rule (proj_decide).  NOT the relaxation rounds: k_proj_resolve and
+// k_trk_resolve each keep their loop, which inside a shared inlined function compiled to a candidate scan 3 us slower
+// (profiles/proj_core_shared.md).  No relocatable device code: every kernel gets its own inlined copy.
 #pragma once
 
 #include "orbfe_common.h"
@@ -10,6 +13,7 @@
 #define PJ_L 16                  // lanes per query in the relaxation rounds
 #define PJ_LC 64                 // lanes per query in the candidate search (one wave: a search window covers ~100 grid cells)
 #define PJ_SKIP 0x1FFu           // distance field of an entry whose slot is blocked before the call / fails the right-image gate
+#define PJ_NOKEY 0xFFFFFFFFu     // "no candidate" in the reductions; a key is distance (9 bits) << 16 | position in the query's list
 #define PJ_MAX_NF 15360          // owner table in LDS (int32 per frame feature)
 struct ProjArgs {
     const uint8_t *descF;
@@ -19,7 +23,7 @@ struct ProjArgs {
     const uint32_t *cell_off, *cell_idx;
     float minx, miny, gwi, ghi;
     const float *uRight;         // may be null
-    const uint8_t *blocked;      // may be null
+    const uint8_t *blocked;      // per feature, may be null; which values block is the form's (proj_gate_skip)
     const float *inv_sigma2;     // per level, may be null (ORBFE_PROJ_CHI2_GATE then never applies)
     int32_t nlevels;
     const orbfe_proj_query *q;
@@ -91,4 +95,102 @@ __device__ __forceinline__ int wave_incl_scan_m(int v)
         if (lane >= d) v += t;
     }
     return v;
+}
+
+// the candidates lane `sub` of the query's wave finds (none when the query has no rectangle)
+__device__ __forceinline__ int proj_walk_count(const ProjArgs &a, const orbfe_proj_query &Q, const ProjRect &R, bool any, int sub)
+{
+    int n = 0;
+    if (any) proj_walk(a, Q, R, sub, [&](uint32_t) { ++n; });
+    return n;
+}
+
+// The count pass of the wave of query g (size_t or int64_t): every lane's count goes to lcnt[g * PJ_LC + sub] (the fill pass
+// places the lane's entries from them), the wave's total to cnt[g].
+template <typename I>
+__device__ __forceinline__ void proj_count(const ProjArgs &a, const orbfe_proj_query &Q, const ProjRect &R, bool any, int sub,
+                                           uint16_t *lcnt, uint32_t *cnt, I g)
+{
+    const int n = proj_walk_count(a, Q, R, any, sub);
+    lcnt[g * PJ_LC + sub] = (uint16_t)n;
+    int tot = n;
+#pragma unroll
+    for (int o = PJ_LC / 2; o > 0; o >>= 1) tot += __shfl_xor(tot, o, PJ_LC);
+    if (sub == 0) cnt[g] = (uint32_t)tot;
+}
+
+__device__ __forceinline__ Desc8 proj_load_desc(const uint8_t *row)
+{
+    Desc8 d;
+    const uint32_t *p = (const uint32_t *)row;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d.w[k] = p[k];
+    return d;
+}
+
+// Does candidate f of query Q get PJ_SKIP for a distance?  When its slot is blocked before the call (a.blocked[f] >= blocks_from:
+// 1 for a table of flags, 2 for the tracker's slot states, where 1 is a MapPoint without observations) or a gate rejects it.
+// inv_sigma2(level) reads the chi2 gate's table, a pointer in one form and a kernel-argument array in the other.
+template <typename S>
+__device__ __forceinline__ bool proj_gate_skip(const ProjArgs &a, const orbfe_proj_query &Q, uint32_t f, int blocks_from, bool has_sigma2,
+                                               S inv_sigma2)
+{
+    bool skip = a.blocked && a.blocked[f] >= blocks_from;             // :108-110 / :1647-1649, state before the call
+    if (!skip && (Q.flags & ORBFE_PROJ_RIGHT_GATE) && a.uRight) {     // :114-119 / :1654-1660
+        const float ur = a.uRight[f];
+        skip = ur > 0.f && fabsf(__fsub_rn(Q.ur, ur)) > Q.r;
+    }
+    if (!skip && (Q.flags & ORBFE_PROJ_CHI2_GATE) && has_sigma2) {    // Fuse :1112-1139: reprojection error against the level's sigma
+        const float ex = __fsub_rn(Q.u, a.xyF[(size_t)a.xs * f]), ey = __fsub_rn(Q.v, a.xyF[(size_t)a.xs * f + 1]);
+        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+        const float kr = a.uRight ? a.uRight[f] : -1.f;
+        const int lv = min(max(a.octF[(size_t)a.os * f], 0), a.nlevels - 1);
+        double bound = 5.99;
+        if (kr >= 0.f) {
+            const float er = __fsub_rn(Q.ur, kr);
+            e2 = __fadd_rn(e2, __fmul_rn(er, er));
+            bound = 7.8;
+        }
+        skip = (double)__fmul_rn(e2, inv_sigma2(lv)) > bound;
+    }
+    return skip;
+}
+
+__device__ __forceinline__ uint32_t proj_dist(const ProjArgs &a, const Desc8 &dq, uint32_t f, bool skip)
+{
+    return skip ? PJ_SKIP : (uint32_t)hamming8(dq, (const uint32_t *)(a.descF + (int64_t)f * 32));
+}
+
+// merge (k1, f1, k2, f2) with a partner's over `width` lanes: the two smallest keys and their features
+template <int WIDTH>
+__device__ __forceinline__ void proj_reduce2(uint32_t &k1, int &f1, uint32_t &k2, int &f2)
+{
+#pragma unroll
+    for (int s = WIDTH / 2; s > 0; s >>= 1) {
+        const uint32_t o1 = __shfl_xor(k1, s, WIDTH), o2 = __shfl_xor(k2, s, WIDTH);
+        const int g1 = __shfl_xor(f1, s, WIDTH), g2 = __shfl_xor(f2, s, WIDTH);
+        // keys are unique inside a query (the position is part of them), NOKEY excepted
+        uint32_t hi;
+        int fh;
+        if (o1 < k1) { hi = k1; fh = f1; k1 = o1; f1 = g1; } else { hi = o1; fh = g1; }
+        const uint32_t m2 = min(k2, o2);
+        const int fm = k2 <= o2 ? f2 : g2;
+        if (hi <= m2) { k2 = hi; f2 = fh; } else { k2 = m2; f2 = fm; }
+    }
+}
+
+// The decision of :128-148 / :1673 from the two smallest keys of the free candidates and their features (read only where
+// the key is not PJ_NOKEY): bestDist = the smallest distance, first in list order; bestDist2 = the smallest among the others,
+// first in list order.  Returns the match or -1.
+__device__ __forceinline__ int proj_decide(const ProjArgs &a, uint32_t k1, uint32_t k2, int f1, int f2, int &bestDist, int &bestDist2)
+{
+    bestDist = k1 == PJ_NOKEY ? 256 : (int)(k1 >> 16);
+    bestDist2 = k2 == PJ_NOKEY ? 256 : (int)(k2 >> 16);
+    if (bestDist > a.th) return -1;
+    if (a.ratio_rule) {
+        const int bestLevel = a.octF[(size_t)a.os * f1];
+        const int bestLevel2 = k2 == PJ_NOKEY ? -1 : a.octF[(size_t)a.os * f2];
+        if (bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(a.nnratio, (float)bestDist2)) return -1;
+    }
+    return f1;
 }

@@ -1,5 +1,6 @@
 // orbfe_projection.hip -- the projection-gated searches of the matcher handle (include/orbfe.h "Matcher"): orbfe_search_by_projection*,
-// orbfe_window_distances, orbfe_search_for_triangulation.
+// orbfe_window_distances, orbfe_search_for_triangulation, on host buffers.  The search's arithmetic is csrc/orbfe_proj_dev.h (shared
+// with the batched device-resident form, orbfe_track.hip); the input staging and the grid check are csrc/orbfe_matcher.h.
 #include <algorithm>
 #include <vector>
 
@@ -15,15 +16,17 @@
 //   (+ the perfect/ overload that also returns the 2-D point pairs, perfect/src/ORBmatcher.cc:1727-1911)
 // The pose projection and its gates stay on the host (they run on cv::Mat in the caller's arithmetic); what comes here is
 // one query per surviving MapPoint: GetFeaturesInArea on the frame's grid, the right-image gate, best / second-best Hamming
-// over the candidates whose slot is free, the acceptance rule.  The reference's loop is NOT a map over the queries: an
-// accepted query writes its MapPoint into F.mvpMapPoints[bestIdx], and later queries skip a slot that holds a point with
-// Observations() > 0 (:108-110 / :1647-1649).  That dependency only points backwards (query i sees the assignments of
-// j < i), so the sequential result is the unique fixed point of "every query picks its best among the slots no EARLIER
-// claiming query took", and it is reached by relaxation: all queries choose in parallel against the owner table of the
-// previous round (owner[f] = lowest claiming query matched to f), the table is rebuilt, until no choice changes.  Query i
-// is final one round after all j < i are -- rounds = longest dependency chain + 1 (2-4 on real frames, <= nq + 1 always).
+// over the candidates whose slot is free, the acceptance rule (all of these: csrc/orbfe_proj_dev.h).  The reference's loop
+// is NOT a map over the queries: an accepted query writes its MapPoint into F.mvpMapPoints[bestIdx], and later queries skip a
+// slot that holds a point with Observations() > 0 (:108-110 / :1647-1649).  That dependency only points backwards (query i
+// sees the assignments of j < i), so the sequential result is the unique fixed point of "every query picks its best among the
+// slots no EARLIER claiming query took", and it is reached by relaxation: all queries choose in parallel against the owner
+// table of the previous round (owner[f] = lowest claiming query matched to f), the table is rebuilt, until no choice changes.
+// Query i is final one round after all j < i are -- rounds = longest dependency chain + 1 (2-4 on real frames, <= nq + 1).
+// This form's layout: packed points (2 floats / 1 int apart), query i's descriptor at qdesc + 32 i, `blocked` a table of flags,
+// the level table a device pointer of up to 64 entries.
 // Launch structure: the candidate lists (GetFeaturesInArea) and the Hamming distances are independent per query and are
-// spread over the chip with 16 lanes per query (k_proj_count -> k_scan_u32 -> k_proj_fill; every (cand | dist << 16) entry is
+// spread over the chip with one wave per query (k_proj_count -> k_scan_u32 -> k_proj_fill; every (cand | dist << 16) entry is
 // materialised once); the relaxation rounds only re-scan those entries and run in ONE workgroup (k_proj_resolve, 16 lanes
 // per query, owner table in LDS).
 // ---------------------------------------------------------------------------------------------------
@@ -34,13 +37,8 @@ __global__ __launch_bounds__(256) void k_proj_count(ProjArgs a)
     if (i >= a.nq) return;   // whole waves leave together
     const orbfe_proj_query Q = a.q[i];
     ProjRect R;
-    int n = 0;
-    if (proj_rect(a, Q, R)) proj_walk(a, Q, R, sub, [&](uint32_t) { ++n; });
-    a.lcnt[(size_t)i * PJ_LC + sub] = (uint16_t)n;
-    int tot = n;
-#pragma unroll
-    for (int o = PJ_LC / 2; o > 0; o >>= 1) tot += __shfl_xor(tot, o, PJ_LC);
-    if (sub == 0) a.cnt[i] = (uint32_t)tot;
+    const bool any = proj_rect(a, Q, R);
+    proj_count(a, Q, R, any, sub, a.lcnt, a.cnt, (size_t)i);
 }
 
 __global__ __launch_bounds__(256) void k_proj_fill(ProjArgs a)
@@ -52,38 +50,14 @@ __global__ __launch_bounds__(256) void k_proj_fill(ProjArgs a)
     if (!proj_rect(a, Q, R)) return;   // wave-uniform
     const int mine = a.lcnt[(size_t)i * PJ_LC + sub];
     uint32_t o = a.off[i] + (uint32_t)(wave_incl_scan_m(mine) - mine);
-    Desc8 dq;
-    const uint32_t *p = (const uint32_t *)(a.qdesc + (int64_t)i * 32);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dq.w[k] = p[k];
-    const bool gate = (Q.flags & ORBFE_PROJ_RIGHT_GATE) && a.uRight;
-    const bool chi2 = (Q.flags & ORBFE_PROJ_CHI2_GATE) && a.inv_sigma2;
+    const Desc8 dq = proj_load_desc(a.qdesc + (int64_t)i * 32);
     proj_walk(a, Q, R, sub, [&](uint32_t f) {
-        bool skip = a.blocked && a.blocked[f];                        // :108-110 / :1647-1649, state before the call
-        if (!skip && gate) {                                          // :114-119 / :1654-1660
-            const float ur = a.uRight[f];
-            skip = ur > 0.f && fabsf(__fsub_rn(Q.ur, ur)) > Q.r;
-        }
-        if (!skip && chi2) {                                          // Fuse :1112-1139: reprojection error against the level's sigma
-            const float ex = __fsub_rn(Q.u, a.xyF[(size_t)a.xs * f]), ey = __fsub_rn(Q.v, a.xyF[(size_t)a.xs * f + 1]);
-            float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-            const float kr = a.uRight ? a.uRight[f] : -1.f;
-            const int lv = min(max(a.octF[(size_t)a.os * f], 0), a.nlevels - 1);
-            double bound = 5.99;
-            if (kr >= 0.f) {
-                const float er = __fsub_rn(Q.ur, kr);
-                e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                bound = 7.8;
-            }
-            skip = (double)__fmul_rn(e2, a.inv_sigma2[lv]) > bound;
-        }
-        const uint32_t d = skip ? PJ_SKIP : (uint32_t)hamming8(dq, (const uint32_t *)(a.descF + (int64_t)f * 32));
+        const bool skip = proj_gate_skip(a, Q, f, 1, a.inv_sigma2 != nullptr, [&](int lv) { return a.inv_sigma2[lv]; });
+        const uint32_t d = proj_dist(a, dq, f, skip);
         a.ent[o++] = f | (d << 16);
     });
 }
 
-// key of an entry in the reduction: distance (9 bits) above the position in the query's list (first in list order wins ties)
-#define PJ_NOKEY 0xFFFFFFFFu
 __global__ __launch_bounds__(PJ_T) void k_proj_resolve(ProjArgs a)
 {
     extern __shared__ int32_t s_owner[];   // [nF]
@@ -178,7 +152,7 @@ __global__ __launch_bounds__(PJ_T) void k_proj_resolve(ProjArgs a)
 //   * results go straight to page-locked host memory (match | best | second | status): two launches, no copy back, one wait.
 // ---------------------------------------------------------------------------------------------------
 #define PJ_SLAB 512
-#define PJ_FT 256                // threads per workgroup: one wave per query in the fill, 16 lanes per query in the rounds
+#define PJ_FT 256                // threads per workgroup of k_proj_fused: one wave per query
 struct ProjFusedArgs {
     ProjArgs a;
     int32_t *f12;                // [2 * nq] feature of the best / second-best free candidate (-1: none)
@@ -186,38 +160,6 @@ struct ProjFusedArgs {
     uint32_t *done;              // [1] largest candidate count above PJ_SLAB (0: none); reset by k_proj_rounds
     int32_t *h_out;              // mapped host: match[nq] | best[nq] | second[nq] | status[2]
 };
-
-// the decision of :128-148 / :1673 from the two smallest keys of the free candidates and their features
-__device__ __forceinline__ int proj_decide(const ProjArgs &a, uint32_t k1, uint32_t k2, int f1, int f2, int &bestDist, int &bestDist2)
-{
-    bestDist = k1 == PJ_NOKEY ? 256 : (int)(k1 >> 16);
-    bestDist2 = k2 == PJ_NOKEY ? 256 : (int)(k2 >> 16);
-    if (bestDist > a.th) return -1;
-    if (a.ratio_rule) {
-        const int bestLevel = a.octF[(size_t)a.os * f1];
-        const int bestLevel2 = k2 == PJ_NOKEY ? -1 : a.octF[(size_t)a.os * f2];
-        if (bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(a.nnratio, (float)bestDist2)) return -1;
-    }
-    return f1;
-}
-
-// merge (k1, f1, k2, f2) with a partner's over `width` lanes: the two smallest keys and their features
-template <int WIDTH>
-__device__ __forceinline__ void proj_reduce2(uint32_t &k1, int &f1, uint32_t &k2, int &f2)
-{
-#pragma unroll
-    for (int s = WIDTH / 2; s > 0; s >>= 1) {
-        const uint32_t o1 = __shfl_xor(k1, s, WIDTH), o2 = __shfl_xor(k2, s, WIDTH);
-        const int g1 = __shfl_xor(f1, s, WIDTH), g2 = __shfl_xor(f2, s, WIDTH);
-        // keys are unique inside a query (the position is part of them), NOKEY excepted
-        uint32_t hi;
-        int fh;
-        if (o1 < k1) { hi = k1; fh = f1; k1 = o1; f1 = g1; } else { hi = o1; fh = g1; }
-        const uint32_t m2 = min(k2, o2);
-        const int fm = k2 <= o2 ? f2 : g2;
-        if (hi <= m2) { k2 = hi; f2 = fh; } else { k2 = m2; f2 = fm; }
-    }
-}
 
 __global__ __launch_bounds__(PJ_FT) void k_proj_fused(ProjFusedArgs p)
 {
@@ -230,8 +172,7 @@ __global__ __launch_bounds__(PJ_FT) void k_proj_fused(ProjFusedArgs p)
             const orbfe_proj_query Q = a.q[i];
             ProjRect R;
             const bool any = proj_rect(a, Q, R);
-            int n = 0;
-            if (any) proj_walk(a, Q, R, lane, [&](uint32_t) { ++n; });
+            const int n = proj_walk_count(a, Q, R, any, lane);
             const int incl = wave_incl_scan_m(n);
             const int tot = __shfl(incl, 63, 64);
             uint32_t k1 = PJ_NOKEY, k2 = PJ_NOKEY;
@@ -241,32 +182,10 @@ __global__ __launch_bounds__(PJ_FT) void k_proj_fused(ProjFusedArgs p)
             } else if (tot > 0) {
                 uint32_t o = (uint32_t)(incl - n);
                 uint32_t *ent = a.ent + (size_t)i * PJ_SLAB;
-                Desc8 dq;
-                const uint32_t *pq = (const uint32_t *)(a.qdesc + (int64_t)i * 32);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) dq.w[k] = pq[k];
-                const bool gate = (Q.flags & ORBFE_PROJ_RIGHT_GATE) && a.uRight;
-                const bool chi2 = (Q.flags & ORBFE_PROJ_CHI2_GATE) && a.inv_sigma2;
+                const Desc8 dq = proj_load_desc(a.qdesc + (int64_t)i * 32);
                 proj_walk(a, Q, R, lane, [&](uint32_t f) {
-                    bool skip = a.blocked && a.blocked[f];
-                    if (!skip && gate) {
-                        const float ur = a.uRight[f];
-                        skip = ur > 0.f && fabsf(__fsub_rn(Q.ur, ur)) > Q.r;
-                    }
-                    if (!skip && chi2) {
-                        const float ex = __fsub_rn(Q.u, a.xyF[(size_t)a.xs * f]), ey = __fsub_rn(Q.v, a.xyF[(size_t)a.xs * f + 1]);
-                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        const float kr = a.uRight ? a.uRight[f] : -1.f;
-                        const int lv = min(max(a.octF[(size_t)a.os * f], 0), a.nlevels - 1);
-                        double bound = 5.99;
-                        if (kr >= 0.f) {
-                            const float er = __fsub_rn(Q.ur, kr);
-                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                            bound = 7.8;
-                        }
-                        skip = (double)__fmul_rn(e2, a.inv_sigma2[lv]) > bound;
-                    }
-                    const uint32_t d = skip ? PJ_SKIP : (uint32_t)hamming8(dq, (const uint32_t *)(a.descF + (int64_t)f * 32));
+                    const bool skip = proj_gate_skip(a, Q, f, 1, a.inv_sigma2 != nullptr, [&](int lv) { return a.inv_sigma2[lv]; });
+                    const uint32_t d = proj_dist(a, dq, f, skip);
                     ent[o] = f | (d << 16);
                     if (!skip) {
                         const uint32_t key = (d << 16) | o;
@@ -413,51 +332,38 @@ extern "C" orbfe_status orbfe_search_by_projection_chi2(orbfe_matcher *m, const 
     }
     if (nF > PJ_MAX_NF) { orbfe_set_error("orbfe_search_by_projection: at most %d frame features", PJ_MAX_NF); return ORBFE_ERR_SIZE; }
     if (th > 255) { orbfe_set_error("orbfe_search_by_projection: th must be below 256 (256 is the 'no candidate' distance)"); return ORBFE_ERR_ARG; }
-    const uint32_t nin = cell_off[GRID_NC];
-    if (nin > (uint32_t)nF) { orbfe_set_error("cell_off inconsistent with nF"); return ORBFE_ERR_ARG; }
-    for (int c = 0; c < GRID_NC; ++c)
-        if (cell_off[c + 1] < cell_off[c]) { orbfe_set_error("cell_off must not decrease"); return ORBFE_ERR_ARG; }
-    for (uint32_t k = 0; k < nin; ++k)
-        if (cell_idx[k] >= (uint32_t)nF) { orbfe_set_error("cell_idx out of range"); return ORBFE_ERR_ARG; }
+    if (!orb_grid_csr_ok(cell_off, cell_idx, nF, "nF")) return ORBFE_ERR_ARG;
     if (nq == 0) return ORBFE_OK;
     DeviceGuard g(m->device);
     hipStream_t st = m->stream;
     ORBFE_HIP(scratch_acquire(m, st));
-    // One pinned staging block in, one out: the per-frame call is latency-bound, nine pageable copies cost more than the
-    // kernels.  Layout (256-byte aligned pieces): descF | xyF | octF | cell_off | cell_idx | uRight | blocked | q | qdesc
-    const size_t sz[10] = {(size_t)nF * 32, (size_t)nF * 8, (size_t)nF * 4, (size_t)(GRID_NC + 1) * 4, (size_t)nin * 4,
-                           uRight ? (size_t)nF * 4 : 0, blocked ? (size_t)nF : 0, (size_t)nq * sizeof(orbfe_proj_query), (size_t)nq * 32,
-                           inv_level_sigma2 ? (size_t)nlevels * 4 : 0};
-    const void *src[10] = {descF, xyF, octF, cell_off, cell_idx, uRight, blocked, q, qdesc, inv_level_sigma2};
-    size_t at[11];
-    at[0] = 0;
-    for (int i = 0; i < 10; ++i) at[i + 1] = (at[i] + sz[i] + 255) & ~(size_t)255;
+    // One pinned staging block in, one out: the per-frame call is latency-bound, nine pageable copies cost more than the kernels
+    const StagePiece in[10] = {{descF, (size_t)nF * 32}, {xyF, (size_t)nF * 8}, {octF, (size_t)nF * 4}, {cell_off, (size_t)(GRID_NC + 1) * 4},
+                               {cell_idx, (size_t)cell_off[GRID_NC] * 4}, {uRight, uRight ? (size_t)nF * 4 : 0}, {blocked, blocked ? (size_t)nF : 0},
+                               {q, (size_t)nq * sizeof(orbfe_proj_query)}, {qdesc, (size_t)nq * 32},
+                               {inv_level_sigma2, inv_level_sigma2 ? (size_t)nlevels * 4 : 0}};
+    const char *din[10];
     const size_t out_bytes = (size_t)nq * 12 + 8;   // match | best | second | status[2]
-    ORBFE_HIP(m->pin_in.ensure(at[10]));
     ORBFE_HIP(m->pin_out.ensure(out_bytes));
-    ORBFE_HIP(m->b[0].ensure(at[10]));
     ORBFE_HIP(m->b[1].ensure(out_bytes));
     ORBFE_HIP(m->b[2].ensure((size_t)nq * 4));                 // cnt
     ORBFE_HIP(m->b[3].ensure((size_t)nq * PJ_LC * 2));         // lcnt
     ORBFE_HIP(m->b[4].ensure((size_t)(nq + 1) * 4));           // off
-    for (int i = 0; i < 10; ++i)
-        if (sz[i]) memcpy(m->pin_in.as<char>() + at[i], src[i], sz[i]);
-    ORBFE_HIP(hipMemcpyAsync(m->b[0].p, m->pin_in.p, at[10], hipMemcpyHostToDevice, st));
-    const char *din = m->b[0].as<const char>();
+    ORBFE_HIP(stage_upload(m, st, in, din));
     ProjArgs a;
-    a.descF = (const uint8_t *)(din + at[0]);
-    a.xyF = (const float *)(din + at[1]);
-    a.octF = (const int32_t *)(din + at[2]);
+    a.descF = (const uint8_t *)din[0];
+    a.xyF = (const float *)din[1];
+    a.octF = (const int32_t *)din[2];
     a.nF = nF; a.xs = 2; a.os = 1;
-    a.cell_off = (const uint32_t *)(din + at[3]);
-    a.cell_idx = (const uint32_t *)(din + at[4]);
+    a.cell_off = (const uint32_t *)din[3];
+    a.cell_idx = (const uint32_t *)din[4];
     a.minx = minx; a.miny = miny; a.gwi = gw_inv; a.ghi = gh_inv;
-    a.uRight = uRight ? (const float *)(din + at[5]) : nullptr;
-    a.blocked = blocked ? (const uint8_t *)(din + at[6]) : nullptr;
-    a.inv_sigma2 = inv_level_sigma2 ? (const float *)(din + at[9]) : nullptr;
+    a.uRight = uRight ? (const float *)din[5] : nullptr;
+    a.blocked = blocked ? (const uint8_t *)din[6] : nullptr;
+    a.inv_sigma2 = inv_level_sigma2 ? (const float *)din[9] : nullptr;
     a.nlevels = nlevels;
-    a.q = (const orbfe_proj_query *)(din + at[7]);
-    a.qdesc = (const uint8_t *)(din + at[8]);
+    a.q = (const orbfe_proj_query *)din[7];
+    a.qdesc = (const uint8_t *)din[8];
     a.nq = nq; a.th = th; a.ratio_rule = ratio_rule ? 1 : 0; a.nnratio = nnratio;
     a.match = m->b[1].as<int32_t>();
     a.best = a.match + nq;
@@ -467,6 +373,12 @@ extern "C" orbfe_status orbfe_search_by_projection_chi2(orbfe_matcher *m, const 
     a.lcnt = m->b[3].as<uint16_t>();
     a.off = m->b[4].as<uint32_t>();
     const int32_t *hout = m->pin_out.as<const int32_t>();
+    auto results_out = [&] {
+        memcpy(match, hout, (size_t)nq * 4);
+        if (best) memcpy(best, hout + nq, (size_t)nq * 4);
+        if (second) memcpy(second, hout + 2 * (size_t)nq, (size_t)nq * 4);
+        return ORBFE_OK;
+    };
     // ONE launch (k_proj_fused) when the owner table and the re-scan list fit the LDS and no query overflows its slab; else (or on
     // overflow, reported in status[0]) the four-kernel path below
     const size_t fused_lds = ((size_t)std::max(nF, 1) + (size_t)PJ_ROUNDS_WORDS * (size_t)nq) * 4;
@@ -491,12 +403,7 @@ extern "C" orbfe_status orbfe_search_by_projection_chi2(orbfe_matcher *m, const 
         hipLaunchKernelGGL(k_proj_rounds, dim3(1), dim3(PJ_RT), fused_lds, st, fa);
         ORBFE_HIP(hipGetLastError());
         ORBFE_HIP(hipStreamSynchronize(st));
-        if (hout[3 * (size_t)nq] == 0) {
-            memcpy(match, hout, (size_t)nq * 4);
-            if (best) memcpy(best, hout + nq, (size_t)nq * 4);
-            if (second) memcpy(second, hout + 2 * (size_t)nq, (size_t)nq * 4);
-            return ORBFE_OK;
-        }
+        if (hout[3 * (size_t)nq] == 0) return results_out();
     }
     const int ngrp = (nq * PJ_LC + 255) / 256;
     size_t ent_cap = std::max<size_t>((size_t)nq * 96, 1 << 16);
@@ -518,10 +425,7 @@ extern "C" orbfe_status orbfe_search_by_projection_chi2(orbfe_matcher *m, const 
         if (attempt == 1) { orbfe_set_error("candidate scratch still too small (%d entries)", need); return ORBFE_ERR_NOMEM; }
         ent_cap = (size_t)need;   // the exact need: the second launch cannot fail on it
     }
-    memcpy(match, hout, (size_t)nq * 4);
-    if (best) memcpy(best, hout + nq, (size_t)nq * 4);
-    if (second) memcpy(second, hout + 2 * (size_t)nq, (size_t)nq * 4);
-    return ORBFE_OK;
+    return results_out();
 }
 
 // The first two stages of the projection search on their own: GetFeaturesInArea for every query and the Hamming distance of
@@ -538,44 +442,31 @@ extern "C" orbfe_status orbfe_window_distances(orbfe_matcher *m, const uint8_t *
         return ORBFE_ERR_ARG;
     }
     if (nF > 65535) { orbfe_set_error("orbfe_window_distances: at most 65535 features (16-bit index in an entry)"); return ORBFE_ERR_SIZE; }
-    const uint32_t nin = cell_off[GRID_NC];
-    if (nin > (uint32_t)nF) { orbfe_set_error("cell_off inconsistent with nF"); return ORBFE_ERR_ARG; }
-    for (int c = 0; c < GRID_NC; ++c)
-        if (cell_off[c + 1] < cell_off[c]) { orbfe_set_error("cell_off must not decrease"); return ORBFE_ERR_ARG; }
-    for (uint32_t k = 0; k < nin; ++k)
-        if (cell_idx[k] >= (uint32_t)nF) { orbfe_set_error("cell_idx out of range"); return ORBFE_ERR_ARG; }
+    if (!orb_grid_csr_ok(cell_off, cell_idx, nF, "nF")) return ORBFE_ERR_ARG;
     off[0] = 0;
     if (nq == 0) return ORBFE_OK;
     DeviceGuard g(m->device);
     hipStream_t st = m->stream;
     ORBFE_HIP(scratch_acquire(m, st));
-    const size_t sz[7] = {(size_t)nF * 32, (size_t)nF * 8, (size_t)nF * 4, (size_t)(GRID_NC + 1) * 4, (size_t)nin * 4,
-                          (size_t)nq * sizeof(orbfe_proj_query), (size_t)nq * 32};
-    const void *src[7] = {descF, xyF, octF, cell_off, cell_idx, q, qdesc};
-    size_t at[8];
-    at[0] = 0;
-    for (int i = 0; i < 7; ++i) at[i + 1] = (at[i] + sz[i] + 255) & ~(size_t)255;
-    ORBFE_HIP(m->pin_in.ensure(at[7]));
-    ORBFE_HIP(m->b[0].ensure(at[7]));
+    const StagePiece in[7] = {{descF, (size_t)nF * 32}, {xyF, (size_t)nF * 8}, {octF, (size_t)nF * 4}, {cell_off, (size_t)(GRID_NC + 1) * 4},
+                              {cell_idx, (size_t)cell_off[GRID_NC] * 4}, {q, (size_t)nq * sizeof(orbfe_proj_query)}, {qdesc, (size_t)nq * 32}};
+    const char *din[7];
     ORBFE_HIP(m->b[2].ensure((size_t)nq * 4));
     ORBFE_HIP(m->b[3].ensure((size_t)nq * PJ_LC * 2));
     ORBFE_HIP(m->b[4].ensure((size_t)(nq + 1) * 4));
     ORBFE_HIP(m->b[5].ensure(std::max<size_t>((size_t)cap, 1) * 4));
-    for (int i = 0; i < 7; ++i)
-        if (sz[i]) memcpy(m->pin_in.as<char>() + at[i], src[i], sz[i]);
-    ORBFE_HIP(hipMemcpyAsync(m->b[0].p, m->pin_in.p, at[7], hipMemcpyHostToDevice, st));
-    const char *din = m->b[0].as<const char>();
+    ORBFE_HIP(stage_upload(m, st, in, din));
     ProjArgs a;
     memset(&a, 0, sizeof(a));
-    a.descF = (const uint8_t *)(din + at[0]);
-    a.xyF = (const float *)(din + at[1]);
-    a.octF = (const int32_t *)(din + at[2]);
+    a.descF = (const uint8_t *)din[0];
+    a.xyF = (const float *)din[1];
+    a.octF = (const int32_t *)din[2];
     a.nF = nF; a.xs = 2; a.os = 1;
-    a.cell_off = (const uint32_t *)(din + at[3]);
-    a.cell_idx = (const uint32_t *)(din + at[4]);
+    a.cell_off = (const uint32_t *)din[3];
+    a.cell_idx = (const uint32_t *)din[4];
     a.minx = minx; a.miny = miny; a.gwi = gw_inv; a.ghi = gh_inv;
-    a.q = (const orbfe_proj_query *)(din + at[5]);
-    a.qdesc = (const uint8_t *)(din + at[6]);
+    a.q = (const orbfe_proj_query *)din[5];
+    a.qdesc = (const uint8_t *)din[6];
     a.nq = nq;
     a.cnt = m->b[2].as<uint32_t>();
     a.lcnt = m->b[3].as<uint16_t>();
@@ -635,10 +526,7 @@ __global__ __launch_bounds__(256) void k_triangulation(TriArgs a)
     int best = -1;
     const int lo = a.range1[2 * f1], hi = a.range1[2 * f1 + 1];
     if (hi > lo && a.elig1[f1]) {
-        Desc8 d1;
-        const uint32_t *p = (const uint32_t *)(a.desc1 + (int64_t)f1 * 32);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) d1.w[k] = p[k];
+        const Desc8 d1 = proj_load_desc(a.desc1 + (int64_t)f1 * 32);
         const bool st1 = a.stereo1[f1] != 0;
         const float x1 = a.xy1[2 * f1], y1 = a.xy1[2 * f1 + 1];
         // :175-182: a = kp1.x * F(0,0) + kp1.y * F(1,0) + F(2,0), every operation rounded separately
@@ -710,36 +598,27 @@ extern "C" orbfe_status orbfe_search_for_triangulation(orbfe_matcher *m, const u
     DeviceGuard g(m->device);
     hipStream_t st = m->stream;
     ORBFE_HIP(scratch_acquire(m, st));
-    const size_t sz[11] = {(size_t)n1 * 32, (size_t)n1 * 8, (size_t)n1, (size_t)n1, (size_t)n1 * 8, (size_t)n2 * 32, (size_t)n2 * 8, (size_t)n2 * 4,
-                           (size_t)n2, (size_t)n2, (size_t)total2 * 4};
-    const void *src[11] = {desc1, xy1, elig1, stereo1, range.data(), desc2, xy2, oct2, elig2, stereo2, idx2};
-    size_t at[13];
-    at[0] = 0;
-    for (int i = 0; i < 11; ++i) at[i + 1] = (at[i] + sz[i] + 255) & ~(size_t)255;
-    at[12] = at[11] + (((size_t)nlevels2 * 8 + 255) & ~(size_t)255);
-    ORBFE_HIP(m->pin_in.ensure(at[12]));
+    const StagePiece in[12] = {{desc1, (size_t)n1 * 32}, {xy1, (size_t)n1 * 8}, {elig1, (size_t)n1}, {stereo1, (size_t)n1},
+                               {range.data(), (size_t)n1 * 8}, {desc2, (size_t)n2 * 32}, {xy2, (size_t)n2 * 8}, {oct2, (size_t)n2 * 4},
+                               {elig2, (size_t)n2}, {stereo2, (size_t)n2}, {idx2, (size_t)total2 * 4},
+                               {scale_factors2, (size_t)nlevels2 * 4, level_sigma2_2, (size_t)nlevels2 * 4}};   // the level tables share a piece
+    const char *d[12];
     ORBFE_HIP(m->pin_out.ensure((size_t)n1 * 4));
-    ORBFE_HIP(m->b[0].ensure(at[12]));
     ORBFE_HIP(m->b[1].ensure((size_t)n1 * 4));
-    for (int i = 0; i < 11; ++i)
-        if (sz[i]) memcpy(m->pin_in.as<char>() + at[i], src[i], sz[i]);
-    memcpy(m->pin_in.as<char>() + at[11], scale_factors2, (size_t)nlevels2 * 4);
-    memcpy(m->pin_in.as<char>() + at[11] + (size_t)nlevels2 * 4, level_sigma2_2, (size_t)nlevels2 * 4);
-    ORBFE_HIP(hipMemcpyAsync(m->b[0].p, m->pin_in.p, at[12], hipMemcpyHostToDevice, st));
-    const char *d = m->b[0].as<const char>();
+    ORBFE_HIP(stage_upload(m, st, in, d));
     TriArgs a;
-    a.desc1 = (const uint8_t *)(d + at[0]);
-    a.xy1 = (const float *)(d + at[1]);
-    a.elig1 = (const uint8_t *)(d + at[2]);
-    a.stereo1 = (const uint8_t *)(d + at[3]);
-    a.range1 = (const int32_t *)(d + at[4]);
-    a.desc2 = (const uint8_t *)(d + at[5]);
-    a.xy2 = (const float *)(d + at[6]);
-    a.oct2 = (const int32_t *)(d + at[7]);
-    a.elig2 = (const uint8_t *)(d + at[8]);
-    a.stereo2 = (const uint8_t *)(d + at[9]);
-    a.idx2 = (const uint32_t *)(d + at[10]);
-    a.scale2 = (const float *)(d + at[11]);
+    a.desc1 = (const uint8_t *)d[0];
+    a.xy1 = (const float *)d[1];
+    a.elig1 = (const uint8_t *)d[2];
+    a.stereo1 = (const uint8_t *)d[3];
+    a.range1 = (const int32_t *)d[4];
+    a.desc2 = (const uint8_t *)d[5];
+    a.xy2 = (const float *)d[6];
+    a.oct2 = (const int32_t *)d[7];
+    a.elig2 = (const uint8_t *)d[8];
+    a.stereo2 = (const uint8_t *)d[9];
+    a.idx2 = (const uint32_t *)d[10];
+    a.scale2 = (const float *)d[11];
     a.sigma2_2 = a.scale2 + nlevels2;
     for (int k = 0; k < 9; ++k) a.F[k] = F12[k];
     a.ex = ex; a.ey = ey;

@@ -2,7 +2,7 @@
 //   orbfe_unproject_select_batch_device        Frame::UnprojectStereo + Tracking::UpdateLastFrame's close-point rule
 //   orbfe_gate_last_frame_batch_device         the gating of SearchByProjection(CurrentFrame, LastFrame, th, bMono)
 //   orbfe_gate_local_map_batch_device          Frame::isInFrustum + MapPoint::PredictScale + the gating of SearchByProjection(F, vpMapPoints, th)
-//   orbfe_search_by_projection_batch_device    count -> scan -> fill -> resolve of orbfe_projection.hip with a frame dimension
+//   orbfe_search_by_projection_batch_device    count -> scan -> fill -> resolve: the search of orbfe_proj_dev.h with a frame dimension
 //   orbfe_track_replay_batch_device            what the reference's loops leave in mvpMapPoints, the rotation histogram, the point pairs
 //   orbfe_track_last_frame_batch_device, orbfe_track_local_map_batch_device   the chains
 //   orbfe_frustum_points (host), orbfe_track_scratch_bytes (host)
@@ -235,7 +235,9 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_gate_map(TrkGateMapArgs a)
 // 4. the search core with a frame dimension.  Global query g = f * qcap + i; lanes of queries beyond nq[f] count zero
 // candidates, so ONE flat scan over nframes * qcap counts lays every frame's entries into one buffer (a scan per frame would
 // be nframes launches or a second level; the flat one is a single launch whatever the batch).  Features are read in place
-// from the keypoint records (stride 7), query descriptors are gathered as pool[qsrc].
+// from the keypoint records (stride 7), query descriptors are gathered as pool[qsrc], the slot table holds states (0 empty,
+// 1 a MapPoint without observations, 2 one with: only 2 blocks) and the level table (at most 16 entries) travels in the kernel
+// arguments.  The count, the gates and the distances are orbfe_proj_dev.h's, through the frame's view (trk_frame_args).
 // ---------------------------------------------------------------------------------------------------
 struct TrkCoreArgs {
     orbfe_track_frames F;
@@ -297,13 +299,9 @@ __global__ __launch_bounds__(256) void k_trk_count(TrkCoreArgs b)
     const ProjArgs a = trk_frame_args(b, f);
     orbfe_proj_query Q;
     ProjRect R;
-    int src, n = 0;
-    if (trk_query(b, f, i, a, Q, R, src)) proj_walk(a, Q, R, sub, [&](uint32_t) { ++n; });
-    b.lcnt[g * PJ_LC + sub] = (uint16_t)n;
-    int tot = n;
-#pragma unroll
-    for (int o = PJ_LC / 2; o > 0; o >>= 1) tot += __shfl_xor(tot, o, PJ_LC);
-    if (sub == 0) b.cnt[g] = (uint32_t)tot;
+    int src;
+    const bool any = trk_query(b, f, i, a, Q, R, src);
+    proj_count(a, Q, R, any, sub, b.lcnt, b.cnt, g);
 }
 
 __global__ __launch_bounds__(256) void k_trk_fill(TrkCoreArgs b)
@@ -320,38 +318,17 @@ __global__ __launch_bounds__(256) void k_trk_fill(TrkCoreArgs b)
     if (!trk_query(b, f, i, a, Q, R, src)) return;   // wave-uniform
     const int mine = b.lcnt[g * PJ_LC + sub];
     uint32_t o = b.off[g] + (uint32_t)(wave_incl_scan_m(mine) - mine);
-    Desc8 dq;
-    const uint32_t *p = (const uint32_t *)(b.pool + ((int64_t)f * b.pool_frame_rows + src) * 32);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dq.w[k] = p[k];
-    const bool gate = (Q.flags & ORBFE_PROJ_RIGHT_GATE) && a.uRight;
-    const bool chi2 = (Q.flags & ORBFE_PROJ_CHI2_GATE) && b.has_sigma2;
+    const Desc8 dq = proj_load_desc(b.pool + ((int64_t)f * b.pool_frame_rows + src) * 32);
+    // a slot blocks from state 2 on: a MapPoint with observations before the call
     proj_walk(a, Q, R, sub, [&](uint32_t k) {
-        bool skip = a.blocked && a.blocked[k] >= 2;                   // :108-110 / :1647-1649: a MapPoint with observations, before the call
-        if (!skip && gate) {                                          // :114-119 / :1654-1660
-            const float ur = a.uRight[k];
-            skip = ur > 0.f && fabsf(__fsub_rn(Q.ur, ur)) > Q.r;
-        }
-        if (!skip && chi2) {                                          // Fuse :1112-1139
-            const float ex = __fsub_rn(Q.u, a.xyF[(size_t)a.xs * k]), ey = __fsub_rn(Q.v, a.xyF[(size_t)a.xs * k + 1]);
-            float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-            const float kr = a.uRight ? a.uRight[k] : -1.f;
-            const int lv = min(max(a.octF[(size_t)a.os * k], 0), a.nlevels - 1);
-            double bound = 5.99;
-            if (kr >= 0.f) {
-                const float er = __fsub_rn(Q.ur, kr);
-                e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                bound = 7.8;
-            }
-            skip = (double)__fmul_rn(e2, b.inv_sigma2.v[lv]) > bound;
-        }
-        const uint32_t d = skip ? PJ_SKIP : (uint32_t)hamming8(dq, (const uint32_t *)(a.descF + (int64_t)k * 32));
+        const bool skip = proj_gate_skip(a, Q, k, 2, b.has_sigma2 != 0, [&](int lv) { return b.inv_sigma2.v[lv]; });
+        const uint32_t d = proj_dist(a, dq, k, skip);
         b.ent[o++] = k | (d << 16);
     });
 }
 
-// the relaxation rounds of k_proj_resolve, one workgroup per frame, the owner table (4 bytes per frame feature) in LDS
-#define TRK_NOKEY 0xFFFFFFFFu
+// the relaxation rounds of k_proj_resolve, one workgroup per frame, the owner table (4 bytes per frame feature) in LDS; the loop
+// is that kernel's, kept as a copy (orbfe_proj_dev.h says why)
 __global__ __launch_bounds__(PJ_T) void k_trk_resolve(TrkCoreArgs b)
 {
     extern __shared__ int32_t s_owner[];   // [cap]
@@ -378,7 +355,7 @@ __global__ __launch_bounds__(PJ_T) void k_trk_resolve(TrkCoreArgs b)
         bool changed = false;
         for (int i0 = 0; i0 < nq; i0 += PJ_T / PJ_L) {
             const int i = i0 + grp;
-            uint32_t k1 = TRK_NOKEY, k2 = TRK_NOKEY;   // the two smallest keys (dist << 16 | position) among the free slots
+            uint32_t k1 = PJ_NOKEY, k2 = PJ_NOKEY;   // the two smallest keys (dist << 16 | position) among the free slots
             uint32_t o = 0, e = 0;
             if (i < nq) { o = off[i]; e = off[i + 1]; }
             for (uint32_t k = o + sub; k < e; k += PJ_L) {
@@ -397,14 +374,14 @@ __global__ __launch_bounds__(PJ_T) void k_trk_resolve(TrkCoreArgs b)
                 k1 = lo;
             }
             if (i < nq && sub == 0) {
-                const int bestDist = k1 == TRK_NOKEY ? 256 : (int)(k1 >> 16), bestDist2 = k2 == TRK_NOKEY ? 256 : (int)(k2 >> 16);
+                const int bestDist = k1 == PJ_NOKEY ? 256 : (int)(k1 >> 16), bestDist2 = k2 == PJ_NOKEY ? 256 : (int)(k2 >> 16);
                 int mt = -1;
                 if (bestDist <= b.th) {            // :143-148 / :1673
                     const int bestIdx = (int)(b.ent[o + (k1 & 0xFFFFu)] & 0xFFFFu);
                     bool reject = false;
                     if (b.ratio_rule) {
                         const int bestLevel = a.octF[(size_t)a.os * bestIdx];
-                        const int bestLevel2 = k2 == TRK_NOKEY ? -1 : a.octF[(size_t)a.os * (b.ent[o + (k2 & 0xFFFFu)] & 0xFFFFu)];
+                        const int bestLevel2 = k2 == PJ_NOKEY ? -1 : a.octF[(size_t)a.os * (b.ent[o + (k2 & 0xFFFFu)] & 0xFFFFu)];
                         reject = bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(b.nnratio, (float)bestDist2);
                     }
                     if (!reject) mt = bestIdx;
@@ -532,8 +509,6 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_replay(TrkReplayArgs a)
 // ---------------------------------------------------------------------------------------------------
 namespace
 {
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 bool frames_ok(const orbfe_track_frames *F, int32_t nframes)
 {
     return F && F->cap >= 0 && (nframes == 0 || (F->d_kps && F->d_desc && F->d_n && F->d_cell_off && F->d_cell_idx));
@@ -670,8 +645,8 @@ extern "C" int64_t orbfe_track_scratch_bytes(int32_t nframes, int32_t qcap, int6
     if (nframes < 0 || qcap < 1 || ent_cap < 0 || (int64_t)nframes * qcap >= (int64_t)1 << 25 || ent_cap > 0xFFFFFFFFll) return -1;
     const size_t ng = (size_t)nframes * (size_t)qcap;
     // counts | per-lane counts | offsets | entries: the blocks core_launch asks the matcher's scratch for
-    return (int64_t)(al256(std::max<size_t>(ng * 4, 4)) + al256(std::max<size_t>(ng * PJ_LC * 2, 4)) + al256((ng + 1) * 4) +
-                     al256((size_t)std::max<int64_t>(ent_cap, 1) * 4));
+    return (int64_t)(orb_align256(std::max<size_t>(ng * 4, 4)) + orb_align256(std::max<size_t>(ng * PJ_LC * 2, 4)) + orb_align256((ng + 1) * 4) +
+                     orb_align256((size_t)std::max<int64_t>(ent_cap, 1) * 4));
 }
 
 extern "C" orbfe_status orbfe_frustum_points(const float *Tcw, const orbfe_track_camera *cam, float log_scale_factor, int32_t nlevels,

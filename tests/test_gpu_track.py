@@ -216,14 +216,15 @@ def _core_groups():
     return groups
 
 
-def _run_core_batch(trk, key, members, ent_cap):
-    """one batched call over `members`; returns per member (match, best, second) and the status"""
+def _run_core_batch(trk, key, members, ent_cap, free_slot=0):
+    """one batched call over `members`; returns per member (match, best, second) and the status.  A blocked slot is planted as
+    state 2 (a MapPoint with observations), a free one as `free_slot`: 0 (empty) or 1 (a MapPoint without observations)"""
     bounds4, th, nnratio, rule, is2 = key
     frames = []
     for _, c, _, _ in members:
         ci = c["ci"]
         frames.append(dict(xy=ci["xyF"], octave=ci["octF"], desc=ci["descF"], uRight=ci["uRight"],
-                           slot=None if ci["blocked"] is None else 2 * ci["blocked"]))
+                           slot=None if ci["blocked"] is None else free_slot + (2 - free_slot) * ci["blocked"]))
     fr = Frames(trk, frames, bounds4)
     B = len(members)
     qcap = max(max(len(c["q"]) for _, c, _, _ in members), 1) + 2
@@ -291,6 +292,25 @@ def test_core_entry_buffer_one_short(trk):
     got, status = _run_core_batch(trk, key, members, sum(m[3] for m in members))
     assert status[0] == 0
     _check_core(members, got, "after-overflow")
+
+
+def test_core_slot_state_one_does_not_block(trk):
+    """slot state 1 is a MapPoint without observations: the search may take it (:108-110 asks for Observations() > 0).  Every
+    planted call with a blocked table runs with its free slots planted as 1 instead of 0 and must give the same oracle result;
+    a core that blocked from state 1 on would match nothing here, and some expected match does land on such a slot"""
+    on_state_one = 0
+    for key, members in _core_groups().items():
+        part = [m for m in members if m[1]["ci"]["blocked"] is not None]
+        if not part:
+            continue
+        got, status = _run_core_batch(trk, key, part, sum(m[3] for m in part), free_slot=1)
+        assert status[0] == 0, (key, status)
+        _check_core(part, got, "slot-state-1")
+        for _, c, want, _ in part:
+            hit = want[0][want[0] >= 0]
+            assert (c["ci"]["blocked"][hit] == 0).all()   # the oracle never matches a blocked slot: every hit was planted as 1
+            on_state_one += len(hit)
+    assert on_state_one > 0
 
 
 # ------------------------------------------------------------------------------------------------ end to end, last frame
