@@ -620,6 +620,72 @@ orbfe_status orbfe_track_local_map_batch_device(orbfe_matcher *m, const orbfe_tr
 /* bytes of matcher scratch the search takes for (nframes, qcap, ent_cap); -1 outside the limits.  No device needed. */
 int64_t orbfe_track_scratch_bytes(int32_t nframes, int32_t qcap, int64_t ent_cap);
 
+/* SearchForInitialization: ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:523-651, Tracking::MonocularInitialization) for
+ * a batch of frame pairs, device-resident (csrc/orbfe_init_search.hip), so that extractor -> grid -> this call ->
+ * orbfe_initializer_initialize_device runs on one stream without a host read.  Bit for bit the reference's loop:
+ *   For every feature i1 of frame 1 with octave == 0, in index order:
+ *   1. GetFeaturesInArea(prev[i1].x, prev[i1].y, window, 0, 0) on frame 2's grid gives the candidates, in the cell-walk order.
+ *   2. A candidate i2 at Hamming distance d is SKIPPED when held[i2] <= d; held[i2] is the distance at which an earlier query
+ *      was accepted on i2 (INT_MAX if none).  Every acceptance lowers it, so it is the minimum over the accepted earlier queries.
+ *   3. Over the rest, best and second-best by the `dist < bestDist ... else if dist < bestDist2` idiom: the first in list order
+ *      wins a tie.
+ *   4. Accepted when bestDist <= th_low and (float)bestDist < (float)bestDist2 * nnratio (one float multiply; bestDist2 = INT_MAX
+ *      without a second candidate).
+ *   5. Acceptance takes the feature over: the previous holder's matches12 entry goes back to -1 (nmatches - 1), the new query
+ *      holds it (nmatches + 1).
+ *   6. With check_ori every ACCEPTED query votes in the 30-bin rotation histogram (angle of frame 1's keypoint minus frame 2's,
+ *      times 1/30, rounded, 30 -> 0), whether or not it is taken over later.
+ *   7. After ComputeThreeMaxima a vote in a dropped bin clears matches12[i1] and decrements nmatches only if that entry still
+ *      stands.
+ *   8. prev[i1] = keys2[matches12[i1]].pt for the matches that stand; every other prev entry keeps its value.
+ * The sequential result is the unique fixed point of "every query decides against the claims of the earlier queries"; the device
+ * reaches it by rounds over per-feature claim lists (a single word per feature -- the smallest distance, or the lowest query --
+ * decides some legal inputs wrongly: DESIGN.md 8l).
+ * Batch layout = the Tracker's: pair p's first frame is first->d_kps[p * cap .. p * cap + d_n[p]) with descriptors d_desc[(p * cap
+ * + i) * 32], its second frame `second` (grid of orbfe_assign_grid_batch_device; d_uright and d_slot are not read).  Counts are
+ * clamped into [0, cap].  d_prev_in [npairs][cap1][2] is vbPrevMatched; NULL = the features' own positions (Tracking :622-624).
+ * Limits: cap <= 15360 in both frames, th_low <= 255, npairs * first->cap < 2^25. */
+typedef struct orbfe_init_search_first {
+    const orbfe_keypoint *d_kps;     /* [npairs][cap], mvKeysUn: x, y, angle, octave are read */
+    const uint8_t *d_desc;           /* [npairs][cap][32] */
+    const int32_t *d_n;              /* [npairs] */
+    int32_t cap;                     /* cap1 >= 1 */
+} orbfe_init_search_first;
+typedef struct orbfe_init_search_out {
+    int32_t *d_matches12;            /* [npairs][cap1]: vnMatches12; -1 for features that are not level-0, unmatched, taken over,
+                                      * dropped, or >= n1 */
+    int32_t *d_nmatches;             /* [npairs] the reference's return value */
+    float *d_prev_out;               /* [npairs][cap1][2] or NULL: vbPrevMatched after the call; may equal d_prev_in */
+    /* The pairs packed by their counts, as orbfe_initializer_initialize_device takes them (its Normalize runs over ALL keys of
+     * a frame, so rows padded to cap would change T1 / T2).  Each may be NULL; the packed arrays need their offsets.  Room for
+     * npairs * cap entries; what lies past d_offsets[npairs] keeps what it held. */
+    int32_t *d_offsets1, *d_offsets2; /* [npairs + 1]: prefix sums of the clamped counts of the first / second frames */
+    int32_t *d_matches12_csr;        /* pair p's d_matches12 row [0, n1) from d_offsets1[p] on */
+    float *d_keys1_xy;               /* [.][2] mvKeysUn[i].pt of the first frames, by d_offsets1 ... */
+    float *d_keys2_xy;               /* [.][2] ... and of the second frames, by d_offsets2 */
+    int32_t *d_status;               /* [2]: entries needed when ent_cap was too small (else 0); most rounds any pair ran */
+} orbfe_init_search_out;
+/* Enqueued on `stream`: no wait, no host writes; scratch is the matcher's.  min_matches: 0 = off (Tracking uses 100); a pair
+ * with nmatches < min_matches gets its d_matches12 row (and its part of d_matches12_csr) all -1, so that the Initializer reports ORBFE_INIT_FEW_MATCHES for it,
+ * while d_nmatches and d_prev_out keep the reference's values.  When the candidate entries of all pairs exceed ent_cap every
+ * row is -1, d_nmatches is 0, d_prev_out is a copy of the input and d_status[0] holds the exact need: call again with it. */
+orbfe_status orbfe_search_for_initialization_batch_device(orbfe_matcher *m, const orbfe_init_search_first *first,
+                                                          const orbfe_track_frames *second, int32_t npairs, const float *d_prev_in,
+                                                          int32_t window, int32_t th_low, float nnratio, int32_t check_ori,
+                                                          int32_t min_matches, int64_t ent_cap, const orbfe_init_search_out *out,
+                                                          void *stream);
+/* One pair on HOST arrays, synchronous on the matcher's stream: upload, the same launches, download (the entry buffer is grown
+ * and the call repeated inside when it was short).  xy = mvKeysUn[i].pt, octave, angle, descriptors of both frames, frame 2's
+ * grid as orbfe_assign_grid lays it out; prev [n1][2] is vbPrevMatched, read and written; matches12 [n1]; *nmatches = the
+ * reference's return value. */
+orbfe_status orbfe_search_for_initialization(orbfe_matcher *m, const float *xy1, const int32_t *oct1, const float *ang1,
+                                             const uint8_t *desc1, int32_t n1, const float *xy2, const int32_t *oct2, const float *ang2,
+                                             const uint8_t *desc2, int32_t n2, const uint32_t *cell_off, const uint32_t *cell_idx,
+                                             float minx, float miny, float gw_inv, float gh_inv, float *prev, int32_t window,
+                                             int32_t th_low, float nnratio, int32_t check_ori, int32_t *matches12, int32_t *nmatches);
+/* bytes of matcher scratch the batch form takes for (npairs, cap1, ent_cap); -1 outside the limits.  No device needed. */
+int64_t orbfe_init_search_scratch_bytes(int32_t npairs, int32_t cap1, int64_t ent_cap);
+
 /* Frame::ComputeStereoMatches (src/Frame.cc:642-846): row-band descriptor search in the right image,
  * 11 x 11 SAD refinement over 11 shifts on the two extractors' device-resident pyramids (mvImagePyramid of the LAST
  * call of `left` / `right`, frame 0), parabola fit, disparity -> depth, and the median-based outlier rejection.

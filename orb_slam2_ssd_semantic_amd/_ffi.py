@@ -63,7 +63,8 @@ SYMBOLS = (
     "orbfe_objects_create", "orbfe_objects_destroy", "orbfe_objects_merge", "orbfe_objects_size", "orbfe_objects_get", "orbfe_objects_clear",
     "orbfe_unproject_select_batch_device", "orbfe_gate_last_frame_batch_device", "orbfe_gate_local_map_batch_device", "orbfe_frustum_points",
     "orbfe_search_by_projection_batch_device", "orbfe_track_replay_batch_device", "orbfe_track_last_frame_batch_device",
-    "orbfe_track_local_map_batch_device", "orbfe_track_scratch_bytes",
+    "orbfe_track_local_map_batch_device", "orbfe_track_scratch_bytes", "orbfe_search_for_initialization_batch_device",
+    "orbfe_search_for_initialization", "orbfe_init_search_scratch_bytes",
 )
 
 # orbfe_set_option (include/orbfe.h ORBFE_OPT_*)
@@ -123,6 +124,18 @@ class TrackOut(C.Structure):
     _fields_ = [("d_q", C.c_void_p), ("d_qsrc", C.c_void_p), ("d_nq", C.c_void_p), ("qcap", C.c_int32), ("d_match", C.c_void_p),
                 ("d_best", C.c_void_p), ("d_second", C.c_void_p), ("d_status", C.c_void_p), ("d_assigned", C.c_void_p),
                 ("d_nmatches", C.c_void_p), ("d_pairs", C.c_void_p), ("d_npairs", C.c_void_p)]
+
+
+class InitSearchFirst(C.Structure):
+    """orbfe_init_search_first: the first frames of SearchForInitialization's pairs (device pointers)"""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_n", C.c_void_p), ("cap", C.c_int32)]
+
+
+class InitSearchOut(C.Structure):
+    """orbfe_init_search_out: results of orbfe_search_for_initialization_batch_device"""
+    _fields_ = [("d_matches12", C.c_void_p), ("d_nmatches", C.c_void_p), ("d_prev_out", C.c_void_p), ("d_offsets1", C.c_void_p),
+                ("d_offsets2", C.c_void_p), ("d_matches12_csr", C.c_void_p), ("d_keys1_xy", C.c_void_p), ("d_keys2_xy", C.c_void_p),
+                ("d_status", C.c_void_p)]
 
 
 TRACK_PROJ_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("view_cos", "<f4"), ("level", "<i4")])   # orbfe_track_proj
@@ -441,6 +454,12 @@ def _configure(L):
                                                      vp, vp, vp]
     L.orbfe_track_scratch_bytes.argtypes = [i32, i32, i64]
     L.orbfe_track_scratch_bytes.restype = i64
+    L.orbfe_search_for_initialization_batch_device.argtypes = [vp, C.POINTER(InitSearchFirst), tfr, i32, vp, i32, i32, f32, i32, i32, i64,
+                                                               C.POINTER(InitSearchOut), vp]
+    L.orbfe_search_for_initialization.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, f32, f32, f32, f32, vp, i32, i32,
+                                                  f32, i32, vp, vp]
+    L.orbfe_init_search_scratch_bytes.argtypes = [i32, i32, i64]
+    L.orbfe_init_search_scratch_bytes.restype = i64
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default -> orbfe_status / int32

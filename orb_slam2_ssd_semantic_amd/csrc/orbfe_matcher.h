@@ -1,5 +1,5 @@
 // orbfe_matcher.h -- the matcher handle, shared by the translation units that implement its entry points (orbfe_match.hip,
-// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip,
+// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_init_search.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip,
 // with what more than one of them does to it: the scratch hand-over between streams, the pinned input staging (stage_upload) and
 // the check of a caller's grid (orb_grid_csr_ok).  Host only; the device side the projection searches share is orbfe_proj_dev.h.
 #pragma once

@@ -15,42 +15,14 @@
 #include "orbfe_matcher.h"
 #include "orbfe_match_dev.h"
 #include "orbfe_proj_dev.h"
+#include "orbfe_track_dev.h"
 #include "orbfe_track_geom.h"
 
 static_assert(sizeof(orbfe_keypoint) == 7 * sizeof(float) && offsetof(orbfe_keypoint, octave) == 20 && offsetof(orbfe_keypoint, angle) == 12,
               "keypoint record = 7 floats: (x, y) first, angle fourth, octave sixth");
 static_assert(sizeof(TrkCam) == sizeof(orbfe_track_camera), "TrkCam is orbfe_track_camera");
 
-#define TRK_MAX_LEVELS 16        // orbfe_params.nlevels is 1..16: the per-level tables travel in the kernel arguments
-#define TRK_GT 256               // threads of the gating and replay workgroups
 #define TRK_UT 1024              // threads of the unproject / selection workgroup
-
-struct TrkLevels {
-    float v[TRK_MAX_LEVELS];
-};
-
-// Order-preserving compaction inside one workgroup of TRK_GT threads: the position of this lane's item among the items of the
-// chunk (ballot + prefix inside the wave, the waves' totals through LDS) above the running base of the chunks before it.  No
-// atomic takes a slot, so item order = lane order = the reference's loop order.  Returns the position; *total = the chunk's
-// count.  All threads of the workgroup call it.
-__device__ __forceinline__ int trk_compact_pos(bool ok, int *s_wave /* [TRK_GT / 64] */, int *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long mask = __ballot(ok);
-    const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[w] = __popcll(mask);
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < TRK_GT / 64; ++k) {
-        const int c = s_wave[k];
-        if (k < w) base += c;
-        tot += c;
-    }
-    __syncthreads();   // s_wave is free again
-    *total = tot;
-    return base + prefix;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // 1. Frame::UnprojectStereo (src/Frame.cc:879-899) for every keypoint with depth > 0, and the selection of
@@ -232,63 +204,8 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_gate_map(TrkGateMapArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 4. the search core with a frame dimension.  Global query g = f * qcap + i; lanes of queries beyond nq[f] count zero
-// candidates, so ONE flat scan over nframes * qcap counts lays every frame's entries into one buffer (a scan per frame would
-// be nframes launches or a second level; the flat one is a single launch whatever the batch).  Features are read in place
-// from the keypoint records (stride 7), query descriptors are gathered as pool[qsrc], the slot table holds states (0 empty,
-// 1 a MapPoint without observations, 2 one with: only 2 blocks) and the level table (at most 16 entries) travels in the kernel
-// arguments.  The count, the gates and the distances are orbfe_proj_dev.h's, through the frame's view (trk_frame_args).
+// 4. the search core with a frame dimension (TrkCoreArgs and a frame's view of it: orbfe_track_dev.h)
 // ---------------------------------------------------------------------------------------------------
-struct TrkCoreArgs {
-    orbfe_track_frames F;
-    int32_t nframes;
-    TrkLevels inv_sigma2;
-    int32_t has_sigma2, nlevels;
-    const orbfe_proj_query *q;
-    const int32_t *qsrc, *nq;
-    int32_t qcap;
-    const uint8_t *pool;
-    int32_t pool_rows, pool_frame_rows;   // rows a query may address; rows between consecutive frames' pools (0: one pool)
-    int32_t th, ratio_rule;
-    float nnratio;
-    int32_t *match, *best, *second;
-    uint32_t *cnt;
-    uint16_t *lcnt;
-    uint32_t *off, *ent;
-    uint32_t ent_cap;
-    int32_t *status;
-};
-
-// the walk's view of frame f
-__device__ __forceinline__ ProjArgs trk_frame_args(const TrkCoreArgs &b, int f)
-{
-    ProjArgs a;
-    const int64_t fb = (int64_t)f * b.F.cap;
-    a.descF = b.F.d_desc + fb * 32;
-    a.xyF = (const float *)b.F.d_kps + fb * 7;
-    a.octF = (const int32_t *)b.F.d_kps + fb * 7 + 5;
-    a.nF = min(max(b.F.d_n[f], 0), b.F.cap);
-    a.xs = 7; a.os = 7;
-    a.cell_off = b.F.d_cell_off + (int64_t)f * (GRID_NC + 1);
-    a.cell_idx = b.F.d_cell_idx + fb;
-    a.minx = b.F.minx; a.miny = b.F.miny; a.gwi = b.F.gw_inv; a.ghi = b.F.gh_inv;
-    a.uRight = b.F.d_uright ? b.F.d_uright + fb : nullptr;
-    a.blocked = b.F.d_slot ? b.F.d_slot + fb : nullptr;
-    a.nlevels = b.nlevels;
-    a.th = b.th; a.ratio_rule = b.ratio_rule; a.nnratio = b.nnratio;
-    return a;
-}
-
-// query g of the batch: false = it has no candidates (a lane beyond nq[f], a descriptor row outside the pool, an empty window)
-__device__ __forceinline__ bool trk_query(const TrkCoreArgs &b, int f, int i, const ProjArgs &a, orbfe_proj_query &Q, ProjRect &R, int &src)
-{
-    if (i >= min(max(b.nq[f], 0), b.qcap)) return false;
-    src = b.qsrc[(int64_t)f * b.qcap + i];
-    if (src < 0 || src >= b.pool_rows) return false;
-    Q = b.q[(int64_t)f * b.qcap + i];
-    return proj_rect(a, Q, R);
-}
-
 __global__ __launch_bounds__(256) void k_trk_count(TrkCoreArgs b)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, g = t / PJ_LC;
@@ -459,24 +376,7 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_replay(TrkReplayArgs a)
     }
     __syncthreads();
     if (a.check_ori) {
-        if (tid == 0) {  // ComputeThreeMaxima (:1912-1957)
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; ++i) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s; i3 = i;
-                }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
-            s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
-        }
+        if (tid == 0) trk_three_maxima(s_hist, s_keep);
         __syncthreads();
         int dropped = 0;
         for (int i = tid; i < nq; i += TRK_GT) {
@@ -507,6 +407,27 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_replay(TrkReplayArgs a)
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
+// count -> scan -> fill (orbfe_track_dev.h), for the chains below and for orbfe_init_search.hip
+orbfe_status orbfe_internal_track_lists_launch(orbfe_matcher *m, TrkCoreArgs &b, int64_t ent_cap, hipStream_t st)
+{
+    const int64_t ng = (int64_t)b.nframes * b.qcap;
+    ORBFE_HIP(m->b[2].ensure((size_t)ng * 4));
+    ORBFE_HIP(m->b[3].ensure((size_t)ng * PJ_LC * 2));
+    ORBFE_HIP(m->b[4].ensure((size_t)(ng + 1) * 4));
+    ORBFE_HIP(m->b[5].ensure((size_t)std::max<int64_t>(ent_cap, 1) * 4));
+    b.cnt = m->b[2].as<uint32_t>();
+    b.lcnt = m->b[3].as<uint16_t>();
+    b.off = m->b[4].as<uint32_t>();
+    b.ent = m->b[5].as<uint32_t>();
+    b.ent_cap = (uint32_t)ent_cap;
+    const unsigned ngrp = (unsigned)((ng * PJ_LC + 255) / 256);
+    hipLaunchKernelGGL(k_trk_count, dim3(ngrp), dim3(256), 0, st, b);
+    orbfe_internal_launch_scan_u32((const uint32_t *)b.cnt, (int)ng, b.off, st);
+    hipLaunchKernelGGL(k_trk_fill, dim3(ngrp), dim3(256), 0, st, b);
+    ORBFE_HIP(hipGetLastError());
+    return ORBFE_OK;
+}
+
 namespace
 {
 bool frames_ok(const orbfe_track_frames *F, int32_t nframes)
@@ -529,13 +450,12 @@ TrkCam cam_of(const orbfe_track_camera *c)
     return t;
 }
 
-// the launches of the search core on `st`; the scratch blocks are sized here (grow-only, no wait for the device)
+// the launches of the search core on `st`: the lists (orbfe_internal_track_lists_launch sizes the scratch blocks), then the rounds
 orbfe_status core_launch(orbfe_matcher *m, const orbfe_track_frames *F, int32_t nframes, const orbfe_proj_query *d_q, const int32_t *d_qsrc,
                          const int32_t *d_nq, int32_t qcap, const uint8_t *d_qpool, int32_t pool_rows, int32_t pool_frame_rows,
                          const float *inv_level_sigma2, int32_t nlevels, int32_t th, float nnratio, int32_t ratio_rule,
                          int64_t ent_cap, int32_t *d_match, int32_t *d_best, int32_t *d_second, int32_t *d_status, hipStream_t st)
 {
-    const int64_t ng = (int64_t)nframes * qcap;
     TrkCoreArgs b;
     b.F = *F;
     b.nframes = nframes;
@@ -546,19 +466,8 @@ orbfe_status core_launch(orbfe_matcher *m, const orbfe_track_frames *F, int32_t 
     b.pool = d_qpool; b.pool_rows = pool_rows; b.pool_frame_rows = pool_frame_rows;
     b.th = th; b.ratio_rule = ratio_rule ? 1 : 0; b.nnratio = nnratio;
     b.match = d_match; b.best = d_best; b.second = d_second; b.status = d_status;
-    ORBFE_HIP(m->b[2].ensure((size_t)ng * 4));
-    ORBFE_HIP(m->b[3].ensure((size_t)ng * PJ_LC * 2));
-    ORBFE_HIP(m->b[4].ensure((size_t)(ng + 1) * 4));
-    ORBFE_HIP(m->b[5].ensure((size_t)std::max<int64_t>(ent_cap, 1) * 4));
-    b.cnt = m->b[2].as<uint32_t>();
-    b.lcnt = m->b[3].as<uint16_t>();
-    b.off = m->b[4].as<uint32_t>();
-    b.ent = m->b[5].as<uint32_t>();
-    b.ent_cap = (uint32_t)ent_cap;
-    const unsigned ngrp = (unsigned)((ng * PJ_LC + 255) / 256);
-    hipLaunchKernelGGL(k_trk_count, dim3(ngrp), dim3(256), 0, st, b);
-    orbfe_internal_launch_scan_u32((const uint32_t *)b.cnt, (int)ng, b.off, st);
-    hipLaunchKernelGGL(k_trk_fill, dim3(ngrp), dim3(256), 0, st, b);
+    const orbfe_status ls = orbfe_internal_track_lists_launch(m, b, ent_cap, st);
+    if (ls != ORBFE_OK) return ls;
     hipLaunchKernelGGL(k_trk_resolve, dim3(nframes), dim3(PJ_T), (size_t)std::max(F->cap, 1) * 4, st, b);
     ORBFE_HIP(hipGetLastError());
     return ORBFE_OK;

@@ -102,6 +102,40 @@ def initialize_device(handle, offsets1, offsets2, keys1, keys2, matches12, pairs
     return handle.initialize_device(offsets1, offsets2, keys1, keys2, matches12, pairs, draws, **kw)
 
 
+def monocular_initialization_device(tracker, handle, first, second, pairs, draws, window=100, d_prev_in=None, th_low=50, nnratio=0.9,
+                                    check_ori=True, min_matches=100, ent_cap=None):
+    """Tracking::MonocularInitialization's device work for a batch of frame pairs on torch's current stream, nothing read in between:
+    SearchForInitialization (tracking.Tracker.SearchForInitialization_batch_device) -> Initializer::Initialize (handle.initialize_device).
+    first = dict(kps, desc, n) of torch tensors [npairs, cap1, 7] float32 / [npairs, cap1, 32] uint8 / [npairs] int32; second =
+    (tensors kept alive by the caller, orbfe_track_frames from tracking.frames_struct) or the struct alone; pairs uint8
+    [npairs, 64] (PAIR_DTYPE bytes), draws int32.  A pair under min_matches (Tracking: 100) reaches the Initializer without
+    matches and comes back STATUS_FEW_MATCHES.  Returns a dict of device tensors: matches12 [npairs, cap1], nmatches [npairs],
+    prev [npairs, cap1, 2], status [2] (status[0] != 0: the entry buffer was short, no pair has matches; call again with ent_cap
+    = status[0]), offsets1 / offsets2 [npairs + 1] (the pairs packed by their counts: Initialize normalises over ALL keys of a
+    frame, so nothing is padded), and result, P3D, triangulated following offsets1.  No synchronisation."""
+    import torch
+    from . import tracking
+    frames = second[1] if isinstance(second, tuple) else second
+    kps1 = first["kps"]
+    dev = kps1.device
+    npairs, cap1, cap2 = int(first["n"].numel()), int(kps1.shape[1]), int(frames.cap)
+    if handle.max_matches < npairs * cap1:
+        raise ValueError("the Initializer handle holds %d keys of the first frames, the batch may have %d" % (handle.max_matches, npairs * cap1))
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    t = dict(matches12=torch.empty((npairs, cap1), **i32), nmatches=torch.empty((npairs,), **i32), status=torch.zeros((2,), **i32),
+             prev=torch.empty((npairs, cap1, 2), **f32), offsets1=torch.zeros((npairs + 1,), **i32), offsets2=torch.zeros((npairs + 1,), **i32),
+             matches12_csr=torch.full((npairs * cap1,), -1, **i32), keys1=torch.zeros((npairs * cap1, 2), **f32),
+             keys2=torch.zeros((max(npairs * cap2, 1), 2), **f32))
+    st = stream_arg(dev, None)
+    f, o = tracking.init_search_structs(kps1, first["desc"], first["n"], cap1, t["matches12"], t["nmatches"], t["status"], t["prev"],
+                                        t["offsets1"], t["offsets2"], t["matches12_csr"], t["keys1"], t["keys2"])
+    tracker.SearchForInitialization_batch_device(f, frames, npairs, d_prev_in, window, o, th_low=th_low, nnratio=nnratio, check_ori=check_ori,
+                                                 min_matches=min_matches, ent_cap=ent_cap, stream=st)
+    t["result"], t["P3D"], t["triangulated"] = handle.initialize_device(t["offsets1"], t["offsets2"], t["keys1"], t["keys2"], t["matches12_csr"],
+                                                                        pairs, draws, stream=st.value)
+    return t
+
+
 class Initializer:
     """Mirrors the reference's class: constructed on the reference frame's undistorted keypoints keys1 [n1, 2] and K [3, 3];
     initialize(keys2, matches12) is Initialize on the current frame.  Draws come from `draws` of each call, or from `rand` (a

@@ -213,6 +213,36 @@ class ORBmatcher(Handle):
         n = int(off[-1])
         return off, ent[:n] & 0xFFFF, ent[:n] >> 16
 
+    def SearchForInitialization(self, f1, f2, prev, window, grid=None, th_low=None):
+        """ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBmatcher.cc:523-651) on
+        host arrays, the whole rule on the device (orbfe_search_for_initialization).  f1 / f2: dict(xy, octave, angle, desc); f2
+        also bounds = (minx, maxx, miny, maxy), gw_inv, gh_inv; grid = f2's (cell_off, cell_idx), built here when None.
+        Returns (matches12[n1], prev_out[n1, 2], nmatches)."""
+        f32, i32, u8 = np.float32, np.int32, np.uint8
+        a = [np.ascontiguousarray(f1["xy"], f32).reshape(-1, 2), np.ascontiguousarray(f1["octave"], i32), np.ascontiguousarray(f1["angle"], f32),
+             np.ascontiguousarray(f1["desc"], u8).reshape(-1, 32)]
+        b = [np.ascontiguousarray(f2["xy"], f32).reshape(-1, 2), np.ascontiguousarray(f2["octave"], i32), np.ascontiguousarray(f2["angle"], f32),
+             np.ascontiguousarray(f2["desc"], u8).reshape(-1, 32)]
+        n1, n2 = len(a[0]), len(b[0])
+        gp = (float(f2["bounds"][0]), float(f2["bounds"][2]), float(f2["gw_inv"]), float(f2["gh_inv"]))
+        if grid is None:
+            g = FrameGrid(self, b[0], b[1], *gp)
+            grid = (g.cell_off, g.cell_idx)
+        goff, gidx = (np.ascontiguousarray(x, np.uint32) for x in grid)
+        if len(gidx) == 0:
+            gidx = np.zeros(1, np.uint32)
+        pm = np.ascontiguousarray(prev, f32).reshape(-1, 2).copy()
+        if len(pm) != n1:
+            raise ValueError("prev must hold one point per feature of the first frame")
+        m = np.full(max(n1, 1), -1, i32)
+        n = C.c_int32(0)
+        check(self._L.orbfe_search_for_initialization(self._m, ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), n1, ptr(b[0]), ptr(b[1]), ptr(b[2]),
+                                                      ptr(b[3]), n2, ptr(goff), ptr(gidx), *gp, ptr(pm), int(window),
+                                                      self.TH_LOW if th_low is None else int(th_low), self.mfNNratio,
+                                                      int(self.mbCheckOrientation), ptr(m), C.byref(n)),
+              "orbfe_search_for_initialization")
+        return m[:n1], pm, n.value
+
     def SearchForTriangulationCore(self, k1, k2, F12, ex, ey, th_low=50):
         """orbfe_search_for_triangulation (src/ORBmatcher.cc:827-1012): k1 = dict(desc, xy, elig, stereo, fv=(node, off, idx)),
         k2 = the same + octave, scale_factors, level_sigma2.  Returns match12[n1] (before the rotation check)."""

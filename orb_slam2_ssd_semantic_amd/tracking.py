@@ -11,9 +11,10 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import TRACK_PROJ_DTYPE, TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut, check, ptr, stream_arg
+from ._ffi import TRACK_PROJ_DTYPE, InitSearchFirst, InitSearchOut, TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut, check, ptr, stream_arg
 
 TH_HIGH = 100   # src/ORBmatcher.cc:39
+TH_LOW = 50     # src/ORBmatcher.cc:40
 
 
 def camera(fx, fy, cx, cy, bf, minx, maxx, miny, maxy):
@@ -57,6 +58,28 @@ def frames_struct(d_kps, d_desc, d_n, cap, d_cell_off, d_cell_idx, minx, miny, g
     """orbfe_track_frames from torch tensors (the caller keeps them alive)"""
     return TrackFrames(_dp(d_kps), _dp(d_desc), _dp(d_n), int(cap), _dp(d_cell_off), _dp(d_cell_idx), float(minx), float(miny), float(gw_inv),
                        float(gh_inv), _dp(d_uright), _dp(d_slot))
+
+
+def init_search_structs(d_kps1, d_desc1, d_n1, cap1, d_matches12, d_nmatches, d_status, d_prev_out=None, d_offsets1=None, d_offsets2=None,
+                        d_matches12_csr=None, d_keys1_xy=None, d_keys2_xy=None):
+    """(orbfe_init_search_first, orbfe_init_search_out) from torch tensors (the caller keeps them alive)"""
+    return (InitSearchFirst(_dp(d_kps1), _dp(d_desc1), _dp(d_n1), int(cap1)),
+            InitSearchOut(_dp(d_matches12), _dp(d_nmatches), _dp(d_prev_out), _dp(d_offsets1), _dp(d_offsets2), _dp(d_matches12_csr),
+                          _dp(d_keys1_xy), _dp(d_keys2_xy), _dp(d_status)))
+
+
+def init_search_scratch_bytes(npairs, cap1, ent_cap):
+    """bytes of matcher scratch SearchForInitialization_batch_device takes (orbfe_init_search_scratch_bytes); no GPU needed"""
+    n = _ffi.lib().orbfe_init_search_scratch_bytes(int(npairs), int(cap1), int(ent_cap))
+    if n < 0:
+        raise ValueError("outside the limits of the batched search: cap <= 15360, npairs * cap < 2^25, ent_cap < 2^32")
+    return int(n)
+
+
+def init_search_ent_cap(npairs):
+    """the first guess for the entry buffer of SearchForInitialization_batch_device: a 100 px window over 2000 features holds
+    about 150 candidates per level-0 query; d_status[0] tells the exact need when it is short"""
+    return max(int(npairs), 1) * 256 * 1024
 
 
 class Tracker:
@@ -117,6 +140,18 @@ class Tracker:
                                                          int(th_high), float(nnratio), int(ent_cap), int(nframes), C.byref(out), d_visible,
                                                          d_proj, stream),
               "orbfe_track_local_map_batch_device")
+
+    def SearchForInitialization_batch_device(self, first, second, npairs, d_prev_in, window, out, th_low=TH_LOW, nnratio=0.9,
+                                             check_ori=True, min_matches=0, ent_cap=None, stream=None):
+        """ORBmatcher::SearchForInitialization for npairs frame pairs (orbfe_search_for_initialization_batch_device): first /
+        out from init_search_structs, second from frames_struct, d_prev_in a device pointer (int) or None; asynchronous on
+        `stream`.  out.d_status[0] != 0 afterwards: the entry buffer was short, call again with that ent_cap."""
+        if ent_cap is None:
+            ent_cap = init_search_ent_cap(npairs)
+        check(self._L.orbfe_search_for_initialization_batch_device(self._mt._m, C.byref(first), C.byref(second), int(npairs), d_prev_in,
+                                                                   int(window), int(th_low), float(nnratio), int(bool(check_ori)),
+                                                                   int(min_matches), int(ent_cap), C.byref(out), stream),
+              "orbfe_search_for_initialization_batch_device")
 
     # ---- torch layer -------------------------------------------------------------------------------------------------
     @staticmethod
