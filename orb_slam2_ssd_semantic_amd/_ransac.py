@@ -8,8 +8,13 @@ import numpy as np
 from . import _ffi
 from ._ffi import Handle
 
-TAP_ITERATIONS, TAP_ERRORS = range(2)
-TAP_SETS, TAP_ITERS = 32, 512
+ABI = _ffi.ABI
+# include/orbfe.h names the tap stages and sizes once per handle type, with one set of values: the handles share these
+TAP_ITERATIONS, TAP_ERRORS = ABI.ORBFE_SIM3_TAP_ITERATIONS, ABI.ORBFE_SIM3_TAP_ERRORS
+TAP_SETS, TAP_ITERS = ABI.ORBFE_SIM3_TAP_SETS, ABI.ORBFE_SIM3_TAP_ITERS
+assert ABI.ORBFE_PNP_TAP_ERRORS == TAP_ERRORS and all(
+    ABI.constants[f"ORBFE_{p}_TAP_{k}"] == v for p in ("PNP", "INIT")
+    for k, v in (("ITERATIONS", TAP_ITERATIONS), ("SETS", TAP_SETS), ("ITERS", TAP_ITERS)))
 
 
 def check_tensor(t, dtype, name, kind=None, shape=None):

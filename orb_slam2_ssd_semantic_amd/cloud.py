@@ -9,17 +9,11 @@ import numpy as np
 from . import _ffi
 from ._ffi import Handle, stream_arg, tensor_ptr
 
-REC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("rgba", "<u4")])   # orbfe_cloud_point
-assert REC_DTYPE.itemsize == 16
-OBJECT_DTYPE = np.dtype([("status", "<i4"), ("n_in", "<i4"), ("n_kept", "<i4"), ("n_voxels", "<i4"), ("centroid", "<f4", 3), ("min", "<f4", 3),
-                         ("max", "<f4", 3), ("reserved_", "<i4"), ("threshold", "<f8"), ("mean", "<f8"), ("stddev", "<f8")])   # orbfe_object
-FILTER_DTYPE = np.dtype([("status", "<i4"), ("n_in", "<i4"), ("n_finite", "<i4"), ("n_kept", "<i4"), ("threshold", "<f8"), ("mean", "<f8"),
-                         ("stddev", "<f8")])   # orbfe_filter_stat
-PLAN_DTYPE = np.dtype([("used", "<i4"), ("dims", "<i4", 3), ("origin", "<f4", 3), ("inv_cell", "<f4"), ("n_finite", "<i4"), ("cells", "<i4")])
-CLUSTER_DTYPE = np.dtype([("class_id", "<i4"), ("prob", "<f4"), ("centroid", "<f4", 3), ("min", "<f4", 3), ("max", "<f4", 3)])   # orbfe_cluster
-assert (OBJECT_DTYPE.itemsize, FILTER_DTYPE.itemsize, PLAN_DTYPE.itemsize, CLUSTER_DTYPE.itemsize) == (80, 40, 40, 44)
-OBJECT_OK, OBJECT_TOO_FEW, OBJECT_EMPTY = 0, 1, 2
-KNN_AUTO, KNN_BRUTE, KNN_GRID = 0, 1, 2
+ABI, dtype = _ffi.ABI, _ffi.dtype
+REC_DTYPE, OBJECT_DTYPE, FILTER_DTYPE = dtype("orbfe_cloud_point"), dtype("orbfe_object"), dtype("orbfe_filter_stat")
+PLAN_DTYPE, CLUSTER_DTYPE = dtype("orbfe_knn_plan"), dtype("orbfe_cluster")
+OBJECT_OK, OBJECT_TOO_FEW, OBJECT_EMPTY = ABI.ORBFE_OBJECT_OK, ABI.ORBFE_OBJECT_TOO_FEW, ABI.ORBFE_OBJECT_EMPTY
+KNN_AUTO, KNN_BRUTE, KNN_GRID = ABI.ORBFE_KNN_AUTO, ABI.ORBFE_KNN_BRUTE, ABI.ORBFE_KNN_GRID
 PROB_GATE = 0.54   # the reference merges a detection only when prob > 0.54
 
 

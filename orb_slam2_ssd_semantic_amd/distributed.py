@@ -9,7 +9,7 @@ torch.distributed is plumbing: backend "nccl" is RCCL over xGMI on ROCm, "gloo" 
 import torch
 import torch.distributed as dist
 
-from ._ffi import Handle
+from ._ffi import ABI, Handle
 
 
 def shard_range(nframes, rank, world):
@@ -255,7 +255,7 @@ class KeyframeGroup(Handle):
     ONE process drives (ncclCommInitAll); `rank_of_world=(rank, world, id_bytes)` = one process per device."""
 
     _HANDLE, _LIB, _DESTROY = "handle", "L", "orbfe_group_destroy"
-    RCCL, COPY = 0, 1   # transports of the exchange step (include/orbfe.h ORBFE_GROUP_RCCL / ORBFE_GROUP_COPY)
+    RCCL, COPY = ABI.ORBFE_GROUP_RCCL, ABI.ORBFE_GROUP_COPY   # transports of the exchange step
 
     def __init__(self, nfeatures, scale_factor, nlevels, ini_th, min_th, max_width, max_height, max_batch, devices=(0,),
                  rank_of_world=None, device=None, transport=None):

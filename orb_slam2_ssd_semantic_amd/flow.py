@@ -8,7 +8,8 @@ import numpy as np
 from . import _ffi, _ransac
 from ._ffi import Handle, stream_arg, tensor_ptr
 
-TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY, TAP_WARP = range(7)
+TAP_HALF, TAP_FLOW, TAP_FLOW2, TAP_PRE, TAP_MASK, TAP_POLY, TAP_WARP = (
+    _ffi.ABI.constants["ORBFE_FLOW_TAP_" + k] for k in ("HALF", "FLOW", "FLOW2", "PRE", "MASK", "POLY", "WARP"))
 
 
 def plan(w, h):

@@ -8,9 +8,11 @@ import numpy as np
 from . import _ffi, _ransac
 from ._ffi import Handle, stream_arg, tensor_ptr
 
-RANSAC = 8
-TAP_RANSAC, TAP_INFO, TAP_REFIT = range(3)
-KAT_RNG, KAT_HYPOT, KAT_NUMITERS, KAT_JACOBI9, KAT_JACOBI8 = range(5)
+ABI = _ffi.ABI
+RANSAC = ABI.ORBFE_HOMOGRAPHY_RANSAC
+TAP_RANSAC, TAP_INFO, TAP_REFIT = ABI.ORBFE_HOMO_TAP_RANSAC, ABI.ORBFE_HOMO_TAP_INFO, ABI.ORBFE_HOMO_TAP_REFIT
+KAT_RNG, KAT_HYPOT, KAT_NUMITERS, KAT_JACOBI9, KAT_JACOBI8 = (ABI.ORBFE_HOMO_KAT_RNG, ABI.ORBFE_HOMO_KAT_HYPOT, ABI.ORBFE_HOMO_KAT_NUMITERS,
+                                                              ABI.ORBFE_HOMO_KAT_JACOBI9, ABI.ORBFE_HOMO_KAT_JACOBI8)
 
 
 def _pairs(a, n=None):

@@ -8,20 +8,17 @@ import numpy as np
 from . import _ffi, _ransac
 from ._ffi import stream_arg, tensor_ptr
 
-RESULT_DTYPE = np.dtype([("ok", "<i4"), ("status", "<i4"), ("model", "<i4"), ("n_matches", "<i4"), ("SH", "<f4"), ("SF", "<f4"),
-                         ("iterH", "<i4"), ("iterF", "<i4"), ("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3)), ("R21", "<f4", (3, 3)),
-                         ("t21", "<f4", (3,)), ("n_hyp", "<i4"), ("nGood", "<i4", (8,)), ("n_cos", "<i4", (8,)), ("sel_cos", "<f4", (8,)),
-                         ("best", "<i4"), ("second", "<i4"), ("n_inliers", "<i4"), ("parallax_ok", "<i4"), ("parallax_cos", "<f4"),
-                         ("parallax", "<f4"), ("reserved", "<i4", (3,))])
-PAIR_DTYPE = np.dtype([("K", "<f4", (3, 3)), ("sigma", "<f4"), ("iterations", "<i4"), ("draws_offset", "<i4"), ("reserved", "<i4", (4,))])
-ITER_DTYPE = np.dtype([("set", "<i4", (8,)), ("Hn", "<f4", (3, 3)), ("Fn", "<f4", (3, 3)), ("H21i", "<f4", (3, 3)), ("F21i", "<f4", (3, 3)),
-                       ("scoreH", "<f4"), ("scoreF", "<f4"), ("reserved", "<i4", (2,))])
-assert (RESULT_DTYPE.itemsize, PAIR_DTYPE.itemsize, ITER_DTYPE.itemsize) == (288, 64, 192)
-MAX_ITERATIONS = 512
-STATUS_OK, STATUS_FEW_MATCHES, STATUS_BAD_INDEX, STATUS_NO_MODEL, STATUS_BAD_SIZES = range(5)
-MODEL_NONE, MODEL_H, MODEL_F = range(3)
-TAP_ITERATIONS, TAP_MATCHES = range(2)
-(KAT_SVD16X9, KAT_SVD8X9, KAT_SVD3, KAT_SVD4, KAT_INV3, KAT_H21, KAT_F21, KAT_TRIANGULATE, KAT_PARALLAX) = range(9)
+ABI, dtype = _ffi.ABI, _ffi.dtype
+RESULT_DTYPE = dtype("orbfe_initializer_result", H21=(3, 3), F21=(3, 3), R21=(3, 3))
+PAIR_DTYPE = dtype("orbfe_initializer_pair", K=(3, 3))
+ITER_DTYPE = dtype("orbfe_initializer_iter", Hn=(3, 3), Fn=(3, 3), H21i=(3, 3), F21i=(3, 3))
+MAX_ITERATIONS = ABI.ORBFE_INIT_MAX_ITERATIONS
+STATUS_OK, STATUS_FEW_MATCHES, STATUS_BAD_INDEX, STATUS_NO_MODEL, STATUS_BAD_SIZES = (
+    ABI.ORBFE_INIT_OK, ABI.ORBFE_INIT_FEW_MATCHES, ABI.ORBFE_INIT_BAD_INDEX, ABI.ORBFE_INIT_NO_MODEL, ABI.ORBFE_INIT_BAD_SIZES)
+MODEL_NONE, MODEL_H, MODEL_F = range(3)   # orbfe_initializer_result.model; the header names no constants for it
+TAP_ITERATIONS, TAP_MATCHES = ABI.ORBFE_INIT_TAP_ITERATIONS, ABI.ORBFE_INIT_TAP_MATCHES
+(KAT_SVD16X9, KAT_SVD8X9, KAT_SVD3, KAT_SVD4, KAT_INV3, KAT_H21, KAT_F21, KAT_TRIANGULATE, KAT_PARALLAX) = (
+    ABI.constants["ORBFE_INIT_KAT_" + k] for k in ("SVD16X9", "SVD8X9", "SVD3", "SVD4", "INV3", "H21", "F21", "TRIANGULATE", "PARALLAX"))
 _KAT_IO = {KAT_SVD16X9: (144, 346), KAT_SVD8X9: (72, 153), KAT_SVD3: (9, 21), KAT_SVD4: (16, 36), KAT_INV3: (9, 9), KAT_H21: (32, 9),
            KAT_F21: (32, 9), KAT_TRIANGULATE: (28, 3), KAT_PARALLAX: (1, 1)}
 

@@ -27,9 +27,7 @@ def feature_vector_to_csr(fv):
 
 class ORBmatcher(Handle):
     _HANDLE, _DESTROY = "_m", "orbfe_matcher_destroy"
-    TH_HIGH = 100      # src/ORBmatcher.cc:39
-    TH_LOW = 50        # src/ORBmatcher.cc:40
-    HISTO_LENGTH = 30  # src/ORBmatcher.cc:41
+    TH_HIGH, TH_LOW, HISTO_LENGTH = _ffi.ABI.ORBFE_TH_HIGH, _ffi.ABI.ORBFE_TH_LOW, _ffi.ABI.ORBFE_HISTO_LENGTH   # src/ORBmatcher.cc:39-41
 
     def __init__(self, nnratio=0.6, checkOri=True, device=-1, _borrow=None):
         self._L = _ffi.lib()
@@ -329,7 +327,7 @@ class FrameGrid:
     `FrameGrid(matcher, keysUn_xy, octaves, minX, minY, gridElementWidthInv, gridElementHeightInv)`; then
     `GetFeaturesInArea(x, y, r, minLevel=-1, maxLevel=-1)` for one query or `query(qxyr, qlevels)` for a batch
     (CSR result to feed `ORBmatcher.HammingCSR`)."""
-    COLS, ROWS = 64, 48
+    COLS, ROWS = _ffi.ABI.ORBFE_GRID_COLS, _ffi.ABI.ORBFE_GRID_ROWS
 
     def __init__(self, matcher, xy, octave, minx, miny, gw_inv, gh_inv):
         self._mt = matcher

@@ -7,17 +7,15 @@ from . import _ffi, _ransac
 from ._ffi import stream_arg, tensor_ptr
 from ._ransac import TAP_ERRORS, TAP_ITERATIONS, TAP_ITERS, TAP_SETS  # noqa: F401
 
-PARAMS_DTYPE = np.dtype([("min_inliers", "<i4"), ("max_its", "<i4"), ("epsilon", "<f4"), ("th2", "<f4")])
-STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("reserved", "<i4", (2,)), ("best_Tcw", "<f4", (4, 4))])
-RESULT_DTYPE = np.dtype([("found", "<i4"), ("no_more", "<i4"), ("n_inliers", "<i4"), ("iterations_run", "<i4"), ("refined", "<i4"),
-                         ("refine_runs", "<i4"), ("reserved", "<i4", (2,)), ("Tcw", "<f4", (4, 4))])
-SET_DTYPE = np.dtype([("K", "<f4", (4,)), ("params", PARAMS_DTYPE), ("n_iterations", "<i4"), ("draws_offset", "<i4"), ("key_offset", "<i4"),
-                      ("n_keys", "<i4")])
-ITER_DTYPE = np.dtype([("quad", "<i4", (4,)), ("N", "<i4"), ("n_inliers", "<i4"), ("refine_ran", "<i4"), ("refine_inliers", "<i4"),
-                       ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])
-assert (PARAMS_DTYPE.itemsize, STATE_DTYPE.itemsize, RESULT_DTYPE.itemsize, SET_DTYPE.itemsize, ITER_DTYPE.itemsize) == (16, 80, 96, 48, 128)
+ABI, dtype = _ffi.ABI, _ffi.dtype
+PARAMS_DTYPE = dtype("orbfe_pnp_params")
+STATE_DTYPE = dtype("orbfe_pnp_state", best_Tcw=(4, 4))
+RESULT_DTYPE = dtype("orbfe_pnp_result", Tcw=(4, 4))
+SET_DTYPE = dtype("orbfe_pnp_set")
+ITER_DTYPE = dtype("orbfe_pnp_iter", R=(3, 3))
 (KAT_SVD3, KAT_SVD12, KAT_SVD6X3, KAT_SVD6X4, KAT_SVD6X5, KAT_SOLVE6X3, KAT_SOLVE6X4, KAT_SOLVE6X5, KAT_INVERT3, KAT_QR_SOLVE,
- KAT_COMPUTE_POSE) = range(11)
+ KAT_COMPUTE_POSE) = (ABI.constants["ORBFE_PNP_KAT_" + k] for k in (
+     "SVD3", "SVD12", "SVD6X3", "SVD6X4", "SVD6X5", "SOLVE6X3", "SOLVE6X4", "SOLVE6X5", "INVERT3", "QR_SOLVE", "COMPUTE_POSE"))
 _KAT_SHAPE = {KAT_SVD3: (3, 3), KAT_SVD12: (12, 12), KAT_SVD6X3: (6, 3), KAT_SVD6X4: (6, 4), KAT_SVD6X5: (6, 5), KAT_SOLVE6X3: (6, 3),
               KAT_SOLVE6X4: (6, 4), KAT_SOLVE6X5: (6, 5), KAT_INVERT3: (3, 3), KAT_QR_SOLVE: (6, 4)}
 

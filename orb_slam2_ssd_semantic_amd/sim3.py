@@ -7,14 +7,14 @@ from . import _ffi, _ransac
 from ._ffi import stream_arg, tensor_ptr
 from ._ransac import TAP_ERRORS, TAP_ITERATIONS, TAP_ITERS, TAP_SETS  # noqa: F401
 
-MODEL_DTYPE = np.dtype([("T12", "<f4", (4, 4)), ("R", "<f4", (3, 3)), ("t", "<f4", (3,)), ("s", "<f4"), ("reserved", "<f4", (3,))])
-STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("reserved", "<i4", (2,)), ("best", MODEL_DTYPE)])
-RESULT_DTYPE = np.dtype([("found", "<i4"), ("no_more", "<i4"), ("n_inliers", "<i4"), ("iterations_run", "<i4"), ("model", MODEL_DTYPE)])
-SET_DTYPE = np.dtype([("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("fix_scale", "<i4"), ("min_inliers", "<i4"), ("max_its", "<i4"),
-                      ("n_iterations", "<i4"), ("draws_offset", "<i4"), ("key_offset", "<i4"), ("n_keys", "<i4"), ("reserved", "<i4")])
-ITER_DTYPE = np.dtype([("triple", "<i4", (3,)), ("n_inliers", "<i4"), ("T12", "<f4", (4, 4))])
-assert (MODEL_DTYPE.itemsize, STATE_DTYPE.itemsize, RESULT_DTYPE.itemsize, SET_DTYPE.itemsize, ITER_DTYPE.itemsize) == (128, 144, 144, 64, 80)
-KAT_JACOBI4, KAT_ATAN2, KAT_SIN, KAT_COS, KAT_ROTATION = range(5)
+ABI, dtype = _ffi.ABI, _ffi.dtype
+MODEL_DTYPE = dtype("orbfe_sim3_model", T12=(4, 4), R=(3, 3))
+STATE_DTYPE = dtype("orbfe_sim3_state", best=MODEL_DTYPE)
+RESULT_DTYPE = dtype("orbfe_sim3_result", model=MODEL_DTYPE)
+SET_DTYPE = dtype("orbfe_sim3_set")
+ITER_DTYPE = dtype("orbfe_sim3_iter", T12=(4, 4))
+KAT_JACOBI4, KAT_ATAN2, KAT_SIN, KAT_COS, KAT_ROTATION = (ABI.ORBFE_SIM3_KAT_JACOBI4, ABI.ORBFE_SIM3_KAT_ATAN2, ABI.ORBFE_SIM3_KAT_SIN,
+                                                          ABI.ORBFE_SIM3_KAT_COS, ABI.ORBFE_SIM3_KAT_ROTATION)
 
 
 def ransac_iterations(probability, min_inliers, max_its, n):

@@ -13,8 +13,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import TRACK_PROJ_DTYPE, InitSearchFirst, InitSearchOut, TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut, check, ptr, stream_arg
 
-TH_HIGH = 100   # src/ORBmatcher.cc:39
-TH_LOW = 50     # src/ORBmatcher.cc:40
+TH_HIGH, TH_LOW = _ffi.ABI.ORBFE_TH_HIGH, _ffi.ABI.ORBFE_TH_LOW   # src/ORBmatcher.cc:39-40
 
 
 def camera(fx, fy, cx, cy, bf, minx, maxx, miny, maxy):

@@ -2,6 +2,7 @@
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 
@@ -32,6 +33,50 @@ def test_struct_layouts():
     assert _ffi.KP_DTYPE.itemsize == 28  # cv::KeyPoint
     assert C.sizeof(_ffi.OrbfeParams) == 40
     assert [n for n in _ffi.KP_DTYPE.names] == ["x", "y", "size", "angle", "response", "octave", "class_id"]
+
+
+def test_layouts_are_the_compilers(tmp_path):
+    """Every struct of include/orbfe.h, as the binding derives it (ctypes.Structure class and numpy dtype), has the size and the
+    member offsets the host C compiler gives it; the package's public mirrors are those records."""
+    from orb_slam2_ssd_semantic_amd import _ffi, cloud, initializer, pnp, sim3
+    structs = _ffi.ABI.structs
+    header = open(os.path.join(ROOT, "include", "orbfe.h")).read()
+    assert sorted(structs) == sorted(re.findall(r"typedef struct (\w+) \{", header)) and len(structs) >= 30
+    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "orbfe.h"', 'int main(void) {']
+    for name, cls in structs.items():
+        src.append(f'printf("{name} %zu", sizeof({name}));')
+        src += [f'printf(" %zu", offsetof({name}, {f}));' for f, _ in cls._fields_]
+        src.append('printf("\\n");')
+    (tmp_path / "layout.c").write_text("\n".join(src + ["return 0; }", ""]))
+    exe = str(tmp_path / "layout")
+    subprocess.check_call([os.environ.get("CC", "gcc"), "-std=c11", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", exe])
+    seen = set()
+    for line in subprocess.check_output([exe], text=True).splitlines():
+        name, *want = line.split()
+        want = [int(v) for v in want]
+        cls, d = structs[name], _ffi.dtype(name)
+        assert [f for f, _ in cls._fields_] == list(d.names)
+        assert [C.sizeof(cls)] + [getattr(cls, f).offset for f in d.names] == want, name
+        assert [d.itemsize] + [d.fields[f][1] for f in d.names] == want, name
+        seen.add(name)
+    assert seen == set(structs)
+    mirrors = {"orbfe_keypoint": _ffi.KP_DTYPE, "orbfe_proj_query": _ffi.PROJ_QUERY_DTYPE, "orbfe_track_proj": _ffi.TRACK_PROJ_DTYPE,
+               "orbfe_sim3_model": sim3.MODEL_DTYPE, "orbfe_sim3_state": sim3.STATE_DTYPE, "orbfe_sim3_result": sim3.RESULT_DTYPE,
+               "orbfe_sim3_set": sim3.SET_DTYPE, "orbfe_sim3_iter": sim3.ITER_DTYPE, "orbfe_pnp_params": pnp.PARAMS_DTYPE,
+               "orbfe_pnp_state": pnp.STATE_DTYPE, "orbfe_pnp_result": pnp.RESULT_DTYPE, "orbfe_pnp_set": pnp.SET_DTYPE,
+               "orbfe_pnp_iter": pnp.ITER_DTYPE, "orbfe_initializer_result": initializer.RESULT_DTYPE,
+               "orbfe_initializer_pair": initializer.PAIR_DTYPE, "orbfe_initializer_iter": initializer.ITER_DTYPE,
+               "orbfe_cloud_point": cloud.REC_DTYPE, "orbfe_object": cloud.OBJECT_DTYPE, "orbfe_filter_stat": cloud.FILTER_DTYPE,
+               "orbfe_knn_plan": cloud.PLAN_DTYPE, "orbfe_cluster": cloud.CLUSTER_DTYPE}
+    for name, m in mirrors.items():
+        d = _ffi.dtype(name)
+        assert (m.names, m.itemsize) == (d.names, d.itemsize), name
+        for f in d.names:   # a mirror may only give a member another shape: same place, same scalar type, same bytes
+            assert m.fields[f][1] == d.fields[f][1] and m.fields[f][0].itemsize == d.fields[f][0].itemsize, (name, f)
+            assert m.fields[f][0].names or m.fields[f][0].base == d.fields[f][0].base, (name, f)
+    for cls, name in zip((_ffi.OrbfeParams, _ffi.OrbfeCamera, _ffi.TrackCamera, _ffi.TrackFrames, _ffi.TrackLast, _ffi.TrackMap,
+                          _ffi.TrackOut, _ffi.InitSearchFirst, _ffi.InitSearchOut), _ffi.BYREF):
+        assert cls is structs[name]
 
 
 def test_host_hamming_without_device(oracle):
