@@ -1586,6 +1586,72 @@ enum {
 };
 orbfe_status orbfe_initializer_kat(int32_t what, int32_t n, const float *in, float *out);
 
+/* ---- the fork's multi-view geometry dynamic-point mask (csrc/orbfe_geometry.hip) -------------------------
+ * DynaSLAM::Geometry (perfect/src/Geometry.cc): the key-frame ring of DataBase::InsertFrame2DB (:532-550, 20 slots, mNumElem stops
+ * at 19 and GetRefFrames reads slots 0 .. mNumElem-1 whatever mIni / mFin say), GetRefFrames (:83-127, host only, rotm2euler's
+ * at<double> read of the CV_32F pose kept as it behaves), ExtractDynPoints (:136-471), RegionGrowing (:604-700),
+ * DepthRegionGrowing (:475-518, any w x h with w, h >= 45 instead of the hard-coded 640 x 480) and GeometricModelCorrection
+ * (:50-69).  Every operation in the reference's type and order, OpenCV 3.2's MatExpr / gemm / solve / meanStdDev arithmetic
+ * restated; acos is a fixed fp64 operation sequence (fdlibm's), not a C library's.  Bit-exact against tests/geometry_oracle.py
+ * (an unpinned restatement of OpenCV 3.2).  Depth planes are float, finite and >= 0: a non-finite depth is outside the contract.
+ * A key-frame keypoint outside its depth plane (x > -1 && x < w && y > -1 && y < h decides, in float) is dropped; the reference
+ * reads the plane unchecked.  Poses are 16 floats, row-major mTcw. */
+typedef struct orbfe_geometry orbfe_geometry;   /* one DynaSLAM::Geometry: own stream, the device-resident key-frame ring, scratch */
+#define ORBFE_GEOMETRY_DB_SIZE 20      /* MAX_DB_SIZE */
+#define ORBFE_GEOMETRY_REF_FRAMES 5    /* MAX_REF_FRAMES and ELEM_INITIAL_MAP */
+orbfe_status orbfe_geometry_create(int32_t device, int32_t max_w, int32_t max_h, int32_t max_keypoints, int32_t max_seeds,
+                                   orbfe_geometry **out);
+void orbfe_geometry_destroy(orbfe_geometry *g);
+orbfe_status orbfe_geometry_reset(orbfe_geometry *g);   /* an empty ring */
+void *orbfe_geometry_get_stream(orbfe_geometry *g);
+/* GeometricModelUpdateDB for a frame the caller declares a key frame: depth plane (w x h floats, rows depth_stride BYTES apart),
+ * mvKeys, mvKeysUn (n of each, n <= max_keypoints) and mTcw go into the ring slot InsertFrame2DB writes.  on_device != 0: depth,
+ * kps and kps_un are DEVICE pointers (Tcw is always host).  Synchronous; waits for the last correct call first. */
+orbfe_status orbfe_geometry_insert_keyframe(orbfe_geometry *g, const float *depth, int32_t w, int32_t h, size_t depth_stride,
+                                            const orbfe_keypoint *kps, const orbfe_keypoint *kps_un, int32_t n, const float *Tcw,
+                                            int32_t on_device);
+/* the ring's mNumElem, mIni, mFin and, per slot, how many inserts came before the one it holds (-1: never written; slot [20]) */
+orbfe_status orbfe_geometry_db_state(orbfe_geometry *g, int32_t *num_elem, int32_t *ini, int32_t *fin, int32_t *slot_insert);
+/* GetRefFrames, host only, no device needed: db_Tcw [n][16], n <= 20; idx receives min(5, n) slot numbers, most distant first
+ * (0.7 * |dt| / max + 0.3 * |deuler| / max, descending).  Equal scores are outside the contract (cv::sortIdx is not stable). */
+orbfe_status orbfe_geometry_select_ref_frames(const float *cur_Tcw, const float *db_Tcw, int32_t n, int32_t *idx, int32_t *nref);
+/* GeometricModelCorrection on one HOST depth plane: HOST mask (w x h, rows mask_stride bytes apart, 1 = static, 0 = dynamic).
+ * Fewer than 5 key frames, or Tcw == NULL (the empty pose): the mask is all ones and *computed = 0 (the reference leaves its
+ * mask alone); else *computed = 1.  Synchronous. */
+orbfe_status orbfe_geometry_correct(orbfe_geometry *g, const float *depth, int32_t w, int32_t h, size_t depth_stride, const float *Tcw,
+                                    float fx, float fy, float cx, float cy, uint8_t *mask, int32_t mask_stride, int32_t *computed);
+/* nframes current frames (DEVICE depth planes, frame f at d_depth + f * depth_frame_stride bytes; HOST poses [nframes][16], read
+ * before the call returns) against the ring as it stands.  d_mask [nframes] and d_mask_ones (the count of ones, may be NULL) in
+ * the layout orbfe_mask_keypoints_device reads; computed: HOST [nframes], written before the call returns (may be NULL).
+ * Enqueued on `stream`, no synchronisation and no host read between the stages: the dynamic-point count stays on the device,
+ * seeds beyond max_seeds are grown in ordered passes that carry the union. */
+orbfe_status orbfe_geometry_correct_batch_device(orbfe_geometry *g, const float *d_depth, int32_t nframes, int32_t w, int32_t h,
+                                                 size_t depth_stride, size_t depth_frame_stride, const float *Tcw, float fx, float fy,
+                                                 float cx, float cy, uint8_t *d_mask, int32_t mask_stride, size_t mask_frame_stride,
+                                                 int32_t *d_mask_ones, int32_t *computed, void *stream);
+/* DepthRegionGrowing alone on one HOST depth plane and n seeds (x, y) int32 pairs in order (n <= 5 * max_keypoints, every seed
+ * inside the plane): HOST mask out.  The taps below (frame 0) then show the accepted seeds, the union and the regions. */
+orbfe_status orbfe_geometry_depth_region_growing(orbfe_geometry *g, const float *depth, int32_t w, int32_t h, size_t depth_stride,
+                                                 const int32_t *seeds_xy, int32_t n, uint8_t *mask, int32_t mask_stride);
+/* Test taps of the last correct / region-growing call (synchronises its stream).  `frame` counts within the call's last chunk
+ * of frames (orbfe_geometry_chunk frames at most); ORBFE_ERR_STATE for a frame that chunk did not hold or did not compute.
+ *   0 ORBFE_GEOMETRY_TAP_COUNTS  int32 [8]: reference keypoints read, then the survivors of 0 < d < 6, of the parallax gate, of
+ *                                depth < 7, of IsInFrame and depth > 0, of the 41x41 search, of the 0.6 gate, of the variance gate
+ *   1 ORBFE_GEOMETRY_TAP_DYN     int32 [*count][3]: the dynamic points (x, y, label) in the reference's order
+ *   2 ORBFE_GEOMETRY_TAP_SEEDS   uint8 [*count]: 1 where DepthRegionGrowing grew the seed
+ *   3 ORBFE_GEOMETRY_TAP_UNION   uint8 [h][w]: the union before the dilation; *count = w * h
+ *   4 ORBFE_GEOMETRY_TAP_REGION  uint8 [h][w]: RegionGrowing's J of seed `index` of the LAST pass that had seeds (index <
+ *                                max_seeds; all zero for a seed DepthRegionGrowing skipped); *count = w * h */
+enum { ORBFE_GEOMETRY_TAP_COUNTS = 0, ORBFE_GEOMETRY_TAP_DYN = 1, ORBFE_GEOMETRY_TAP_SEEDS = 2, ORBFE_GEOMETRY_TAP_UNION = 3,
+       ORBFE_GEOMETRY_TAP_REGION = 4 };
+orbfe_status orbfe_geometry_tap(orbfe_geometry *g, int32_t frame, int32_t stage, int32_t index, void *dst, size_t cap, int32_t *count);
+int32_t orbfe_geometry_chunk(orbfe_geometry *g);   /* frames per internal pass of the batch form */
+/* host constants, no device needed: the half-widths of getStructuringElement(MORPH_ELLIPSE, (2r+1, 2r+1)), rows 0 .. 2r */
+orbfe_status orbfe_geometry_ellipse(int32_t r, int32_t *half_width);
+/* Known-answer runs on the caller's current device, n doubles in and out: 0 = the canonical acos */
+enum { ORBFE_GEOMETRY_KAT_ACOS = 0 };
+orbfe_status orbfe_geometry_kat(int32_t what, int32_t n, const double *in, double *out);
+
 #ifdef __cplusplus
 }
 #endif
