@@ -686,6 +686,82 @@ orbfe_status orbfe_search_for_initialization(orbfe_matcher *m, const float *xy1,
 /* bytes of matcher scratch the batch form takes for (npairs, cap1, ent_cap); -1 outside the limits.  No device needed. */
 int64_t orbfe_init_search_scratch_bytes(int32_t npairs, int32_t cap1, int64_t ent_cap);
 
+/* SearchForTriangulation, batched: ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:827-1019) for the neighbour loop of
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:349-422) -- one keyframe against all its covisible neighbours, or many
+ * keyframes of a replayed sequence against theirs -- device-resident (csrc/orbfe_tri_search.hip), so that extractor ->
+ * orbfe_frame_geometry_batch_device -> orbfe_bow_transform_batch_device -> orbfe_triangulation_pairs_batch_device -> this call run
+ * on one stream without a host read.  It stops at vMatchedPairs: the triangulation of the pairs (:424-610) and
+ * KeyFrame::ComputeSceneMedianDepth (the d_median_depth input of the monocular baseline gate) remain the caller's.
+ *
+ * The keyframe block, batch layout of the other *_batch_device calls: keyframe b owns `cap` slots of every array (cap + 1 of
+ * d_fv_off, 4 of d_counts); the FeatureVector arrays are exactly what orbfe_bow_transform_batch_device writes.  Pair p matches
+ * keyframe d_kf1[p] (the current keyframe, "1") against d_kf2[p]; the same keyframe may be keyframe 1 of many pairs and a pair
+ * (i, i) is legal.  Per pair, bit for bit what orbfe_search_for_triangulation + the reference's replay give:
+ *   - a feature of either keyframe takes part iff its slot holds no MapPoint (d_has_mp == 0) and, with only_stereo, uRight >= 0;
+ *   - every such keyframe-1 feature whose vocabulary node exists in keyframe 2 takes, among that node's keyframe-2 features that
+ *     pass dist <= th_low, the epipole gate (both keypoints monocular: (ex - x)^2 + (ey - y)^2 >= 100 * scale[octave]) and
+ *     CheckDistEpipolarLine (dsqr < 3.84 * sigma2[octave]; den == 0 fails), the smallest distance, the LAST in list order on ties;
+ *   - with check_ori the 30-bin histogram of kp1.angle - kp2.angle (times 1.0f / 30, sic) and ComputeThreeMaxima clear the matches
+ *     of the other bins.
+ * Counts (d_n, d_counts[1], the offsets) are clamped into [0, cap].  Three things cannot be rejected without reading device
+ * memory on the host, and each is simply not a candidate or not a query: a keyframe-2 feature whose octave is outside
+ * [0, nlevels), a d_fv_idx entry >= the keyframe's d_n, and a frame index outside [0, nframes) (that pair gets an all -1 row
+ * and 0 matches, like a skipped one).
+ * Limits: cap <= 8192 (the BoW block's), th_low <= 255, nlevels <= 16, npairs * cap < 2^25. */
+typedef struct orbfe_tri_keyframes {
+    const orbfe_keypoint *d_kps;     /* [nframes][cap], mvKeysUn: x, y, angle, octave are read */
+    const uint8_t *d_desc;           /* [nframes][cap][32] */
+    const int32_t *d_n;              /* [nframes] */
+    int32_t cap, nframes;
+    const float *d_uright;           /* [nframes][cap] mvuRight: stereo means >= 0; NULL = every keypoint is monocular */
+    const uint8_t *d_has_mp;         /* [nframes][cap] GetMapPoint(i) != NULL; NULL = no slot holds a MapPoint */
+    const uint32_t *d_fv_node, *d_fv_off, *d_fv_idx;   /* [nframes][cap], [nframes][cap + 1], [nframes][cap] */
+    const int32_t *d_counts;         /* [nframes][4]: [1] = number of nodes */
+} orbfe_tri_keyframes;
+typedef struct orbfe_tri_out {
+    int32_t *d_match12;              /* [npairs][cap]: keyframe-2 feature of keyframe-1 feature i after the rotation check, -1 none
+                                      * (also for i >= n1) */
+    int32_t *d_nmatches;             /* [npairs] the reference's return value */
+    int32_t *d_pairs;                /* [npairs][cap][2] (idx1, idx2) in ascending idx1 = vMatchedPairs; rows past d_npairs[p] keep
+                                      * what they held.  NULL together with d_npairs: not wanted */
+    int32_t *d_npairs;               /* [npairs] */
+} orbfe_tri_out;
+/* Enqueued on `stream`: no wait, no host writes; scratch is the matcher's.  d_F12 [npairs][9] row-major and d_epi [npairs][2]
+ * (ex, ey: the epipole of keyframe 1 in keyframe 2) are plain inputs -- orbfe_triangulation_pairs_batch_device makes them;
+ * d_pair_skip [npairs] (may be NULL): a pair with a non-zero byte gets an all -1 row and nmatches 0.  scale_factors / level_sigma2
+ * are HOST arrays of nlevels floats (mvScaleFactors / mvLevelSigma2 of keyframe 2). */
+orbfe_status orbfe_search_for_triangulation_batch_device(orbfe_matcher *m, const orbfe_tri_keyframes *kf, const int32_t *d_kf1,
+                                                         const int32_t *d_kf2, int32_t npairs, const float *d_F12, const float *d_epi,
+                                                         const uint8_t *d_pair_skip, const float *scale_factors,
+                                                         const float *level_sigma2, int32_t nlevels, int32_t th_low,
+                                                         int32_t only_stereo, int32_t check_ori, const orbfe_tri_out *out, void *stream);
+/* What CreateNewMapPoints computes per neighbour before the search (src/LocalMapping.cc:390-417, src/ORBmatcher.cc:833-843), one
+ * thread per pair: d_pair_skip = the baseline gate (|Ow2 - Ow1| accumulated in double, sqrt, stored as float; stereo / RGB-D:
+ * skipped iff baseline < mb; mono: iff baseline / d_median_depth[kf2] < 0.01), d_F12 = ComputeF12, d_epi = the epipole.  d_Tcw
+ * [nframes][12] row-major 3x4 (Rcw | tcw), d_Ow [nframes][3] = KeyFrame::GetCameraCenter (the caller's); d_median_depth [nframes]
+ * = ComputeSceneMedianDepth(2), required when mono; both keyframes share `cam` (fx, fy, cx, cy are read).  A pair with a frame
+ * index outside [0, nframes) is skipped, with zeros in d_F12 / d_epi. */
+orbfe_status orbfe_triangulation_pairs_batch_device(orbfe_matcher *m, const float *d_Tcw, const float *d_Ow, int32_t nframes,
+                                                    const orbfe_track_camera *cam, float mb, int32_t mono, const float *d_median_depth,
+                                                    const int32_t *d_kf1, const int32_t *d_kf2, int32_t npairs, float *d_F12,
+                                                    float *d_epi, uint8_t *d_pair_skip, void *stream);
+/* LocalMapping::ComputeF12 (:848-867) on the HOST, the function the kernel runs (csrc/orbfe_f12.h; no device, no handle):
+ * K1.t().inv() * t12x * R12 * K2.inv() with cv::invert's 3x3 case and cv::gemm's small-matrix rules.  Bit-exact against
+ * tests/f12_oracle.py, a restatement no compiled reference pins; K1.t().inv() * t12x is taken as invert-then-multiply, where
+ * OpenCV's MatExpr runs an LU solve.  Tcw1 / Tcw2 [12], F12 [9] row-major. */
+orbfe_status orbfe_compute_f12(const float *Tcw1, const float *Tcw2, const orbfe_track_camera *cam, float *F12);
+/* bytes of matcher scratch the batch form takes for (npairs, cap); -1 outside the limits.  No device needed. */
+int64_t orbfe_tri_search_scratch_bytes(int32_t npairs, int32_t cap);
+/* the constants of the search kernel (tests take their list lengths from here); -1 for an unknown `what`.  No device needed. */
+#define ORBFE_TRI_INFO_LANES 0             /* lanes that share one keyframe-1 feature */
+#define ORBFE_TRI_INFO_TILE 1              /* keyframe-2 features per LDS tile */
+#define ORBFE_TRI_INFO_QUERIES_PER_PASS 2  /* keyframe-1 features a workgroup handles at once */
+#define ORBFE_TRI_INFO_NODE_WORKGROUPS 3   /* workgroups per pair; the keyframe-1 nodes are dealt to them round robin */
+#define ORBFE_TRI_INFO_MAX_CAP 4
+int32_t orbfe_tri_search_info(int32_t what);
+/* 0 = k_tri_search (LDS tiles, a group of lanes per feature; default), 1 = one thread per keyframe-1 feature: same results */
+orbfe_status orbfe_matcher_set_triangulation_kernel(orbfe_matcher *m, int32_t kernel);
+
 /* Frame::ComputeStereoMatches (src/Frame.cc:642-846): row-band descriptor search in the right image,
  * 11 x 11 SAD refinement over 11 shifts on the two extractors' device-resident pyramids (mvImagePyramid of the LAST
  * call of `left` / `right`, frame 0), parabola fit, disparity -> depth, and the median-based outlier rejection.

@@ -1,5 +1,5 @@
 // orbfe_matcher.h -- the matcher handle, shared by the translation units that implement its entry points (orbfe_match.hip,
-// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_init_search.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip,
+// orbfe_grid.hip, orbfe_projection.hip, orbfe_track.hip, orbfe_init_search.hip, orbfe_tri_search.hip, orbfe_stereo.hip, orbfe_bow.hip, orbfe_frame.hip) and by orbfe_pipeline.hip,
 // with what more than one of them does to it: the scratch hand-over between streams, the pinned input staging (stage_upload) and
 // the check of a caller's grid (orb_grid_csr_ok).  Host only; the device side the projection searches share is orbfe_proj_dev.h.
 #pragma once
@@ -21,6 +21,7 @@ struct orbfe_matcher {
     hipEvent_t ev_scratch = nullptr;
     PinBuf pin_in, pin_out;  // page-locked staging of the latency-bound per-frame calls (orbfe_search_by_projection)
     bool proj_fused = true;   // orbfe_search_by_projection: the one-launch form (k_proj_fused); false = the four-kernel path (tests)
+    int tri_kernel = 0;       // orbfe_search_for_triangulation_batch_device: 0 = k_tri_search (LDS tiles), 1 = k_tri_search_flat
     DevBuf proj_done;        // k_proj_fused's arrival counter / overflow word (zero between calls)
     orbfe_matcher()
     {

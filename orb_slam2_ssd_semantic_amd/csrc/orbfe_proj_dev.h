@@ -3,7 +3,8 @@
 // (proj_rect), the walk (proj_walk), the count (proj_count), the gates (proj_gate_skip) and the distance (proj_dist), the
 // two-smallest merge (proj_reduce2), the acceptance rule (proj_decide).  NOT the relaxation rounds: k_proj_resolve and
 // k_trk_resolve each keep their loop, which inside a shared inlined function compiled to a candidate scan 3 us slower
-// (profiles/proj_core_shared.md).  No relocatable device code: every kernel gets its own inlined copy.
+// (profiles/proj_core_shared.md).  Behind them the per-candidate test of SearchForTriangulation (tri_line, tri_candidate), for
+// orbfe_projection.hip and orbfe_tri_search.hip.  No relocatable device code: every kernel gets its own inlined copy.
 #pragma once
 
 #include "orbfe_common.h"
@@ -159,6 +160,47 @@ __device__ __forceinline__ bool proj_gate_skip(const ProjArgs &a, const orbfe_pr
 __device__ __forceinline__ uint32_t proj_dist(const ProjArgs &a, const Desc8 &dq, uint32_t f, bool skip)
 {
     return skip ? PJ_SKIP : (uint32_t)hamming8(dq, (const uint32_t *)(a.descF + (int64_t)f * 32));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// SearchForTriangulation (src/ORBmatcher.cc:827-1012): the per-candidate test, once, for k_triangulation (orbfe_projection.hip,
+// one pair on host buffers) and k_tri_search / k_tri_search_flat (orbfe_tri_search.hip, a batch of pairs).
+// ---------------------------------------------------------------------------------------------------
+// The epipolar line of a keyframe-1 keypoint in keyframe 2 (:175-182), F12 row-major, every operation rounded separately
+struct TriLine {
+    float a, b, c, den;          // den = a * a + b * b
+};
+__device__ __forceinline__ TriLine tri_line(float x1, float y1, const float *F)
+{
+    TriLine l;
+    l.a = __fadd_rn(__fadd_rn(__fmul_rn(x1, F[0]), __fmul_rn(y1, F[3])), F[6]);
+    l.b = __fadd_rn(__fadd_rn(__fmul_rn(x1, F[1]), __fmul_rn(y1, F[4])), F[7]);
+    l.c = __fadd_rn(__fadd_rn(__fmul_rn(x1, F[2]), __fmul_rn(y1, F[5])), F[8]);
+    l.den = __fadd_rn(__fmul_rn(l.a, l.a), __fmul_rn(l.b, l.b));
+    return l;
+}
+
+// One candidate of one query: its Hamming distance when it passes every gate, -1 when it does not.  In the reference's order:
+// eligibility (no MapPoint; stereo if bOnlyStereo), dist > limit (:895; limit = the running bestDist, or th_low where the caller
+// takes the minimum itself), the epipole gate (:900-907) only when both keypoints are monocular -- closer than 100 * scale[octave]
+// to the epipole, strict, is out --, CheckDistEpipolarLine (:175-196) with den == 0 -> no, and the double comparison against
+// 3.84 * sigma2[octave].  The candidate `c` is read through its accessors -- elig(), desc(), x(), y(), stereo(), scale() and
+// sigma2() of its level -- only where the reference reads it: global memory in one kernel, an LDS tile in the other.
+template <typename C>
+__device__ __forceinline__ int tri_candidate(const Desc8 &d1, bool stereo1, const TriLine &l, float ex, float ey, int limit, const C &c)
+{
+    if (!c.elig()) return -1;
+    const int dist = hamming8(d1, c.desc());
+    if (dist > limit) return -1;
+    const float x2 = c.x(), y2 = c.y();
+    if (!stereo1 && !c.stereo()) {
+        const float dx = __fsub_rn(ex, x2), dy = __fsub_rn(ey, y2);
+        if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.f, c.scale())) return -1;
+    }
+    const float num = __fadd_rn(__fadd_rn(__fmul_rn(l.a, x2), __fmul_rn(l.b, y2)), l.c);
+    if (l.den == 0.f) return -1;
+    const float dsqr = __fdiv_rn(__fmul_rn(num, num), l.den);
+    return (double)dsqr < __dmul_rn(3.84, (double)c.sigma2()) ? dist : -1;
 }
 
 // merge (k1, f1, k2, f2) with a partner's over `width` lanes: the two smallest keys and their features

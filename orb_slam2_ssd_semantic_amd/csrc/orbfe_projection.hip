@@ -519,6 +519,19 @@ struct TriArgs {
     int32_t *match12;
 };
 
+// keyframe-2 feature f of the call, as tri_candidate reads it
+struct TriGlobalCand {
+    const TriArgs &a;
+    uint32_t f;
+    __device__ __forceinline__ bool elig() const { return a.elig2[f] != 0; }
+    __device__ __forceinline__ const uint32_t *desc() const { return (const uint32_t *)(a.desc2 + (int64_t)f * 32); }
+    __device__ __forceinline__ float x() const { return a.xy2[2 * f]; }
+    __device__ __forceinline__ float y() const { return a.xy2[2 * f + 1]; }
+    __device__ __forceinline__ bool stereo() const { return a.stereo2[f] != 0; }
+    __device__ __forceinline__ float scale() const { return a.scale2[a.oct2[f]]; }
+    __device__ __forceinline__ float sigma2() const { return a.sigma2_2[a.oct2[f]]; }
+};
+
 __global__ __launch_bounds__(256) void k_triangulation(TriArgs a)
 {
     const int f1 = blockIdx.x * 256 + threadIdx.x;
@@ -528,28 +541,12 @@ __global__ __launch_bounds__(256) void k_triangulation(TriArgs a)
     if (hi > lo && a.elig1[f1]) {
         const Desc8 d1 = proj_load_desc(a.desc1 + (int64_t)f1 * 32);
         const bool st1 = a.stereo1[f1] != 0;
-        const float x1 = a.xy1[2 * f1], y1 = a.xy1[2 * f1 + 1];
-        // :175-182: a = kp1.x * F(0,0) + kp1.y * F(1,0) + F(2,0), every operation rounded separately
-        const float ea = __fadd_rn(__fadd_rn(__fmul_rn(x1, a.F[0]), __fmul_rn(y1, a.F[3])), a.F[6]);
-        const float eb = __fadd_rn(__fadd_rn(__fmul_rn(x1, a.F[1]), __fmul_rn(y1, a.F[4])), a.F[7]);
-        const float ec = __fadd_rn(__fadd_rn(__fmul_rn(x1, a.F[2]), __fmul_rn(y1, a.F[5])), a.F[8]);
-        const float den = __fadd_rn(__fmul_rn(ea, ea), __fmul_rn(eb, eb));
-        int bestDist = a.th_low;
+        const TriLine l = tri_line(a.xy1[2 * f1], a.xy1[2 * f1 + 1], a.F);
+        int bestDist = a.th_low;   // never above th_low: `dist > bestDist` is the whole of :895
         for (int i2 = lo; i2 < hi; ++i2) {
             const uint32_t f2 = a.idx2[i2];
-            if (!a.elig2[f2]) continue;
-            const int dist = hamming8(d1, (const uint32_t *)(a.desc2 + (int64_t)f2 * 32));
-            if (dist > a.th_low || dist > bestDist) continue;   // :895
-            const float x2 = a.xy2[2 * f2], y2 = a.xy2[2 * f2 + 1];
-            const int o2 = a.oct2[f2];
-            if (!st1 && !a.stereo2[f2]) {                         // :900-907
-                const float dx = __fsub_rn(a.ex, x2), dy = __fsub_rn(a.ey, y2);
-                if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.f, a.scale2[o2])) continue;
-            }
-            const float num = __fadd_rn(__fadd_rn(__fmul_rn(ea, x2), __fmul_rn(eb, y2)), ec);
-            if (den == 0.f) continue;
-            const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-            if ((double)dsqr < __dmul_rn(3.84, (double)a.sigma2_2[o2])) {   // :195
+            const int dist = tri_candidate(d1, st1, l, a.ex, a.ey, bestDist, TriGlobalCand{a, f2});
+            if (dist >= 0) {
                 best = (int)f2;
                 bestDist = dist;
             }
