@@ -690,8 +690,9 @@ int64_t orbfe_init_search_scratch_bytes(int32_t npairs, int32_t cap1, int64_t en
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:349-422) -- one keyframe against all its covisible neighbours, or many
  * keyframes of a replayed sequence against theirs -- device-resident (csrc/orbfe_tri_search.hip), so that extractor ->
  * orbfe_frame_geometry_batch_device -> orbfe_bow_transform_batch_device -> orbfe_triangulation_pairs_batch_device -> this call run
- * on one stream without a host read.  It stops at vMatchedPairs: the triangulation of the pairs (:424-610) and
- * KeyFrame::ComputeSceneMedianDepth (the d_median_depth input of the monocular baseline gate) remain the caller's.
+ * on one stream without a host read.  It stops at vMatchedPairs and takes d_has_mp as a constant: the triangulation of the pairs
+ * (:424-610), KeyFrame::ComputeSceneMedianDepth (the d_median_depth input of the monocular baseline gate) and the loop that carries
+ * the filled slots from neighbour to neighbour are "CreateNewMapPoints, device-resident" below.
  *
  * The keyframe block, batch layout of the other *_batch_device calls: keyframe b owns `cap` slots of every array (cap + 1 of
  * d_fv_off, 4 of d_counts); the FeatureVector arrays are exactly what orbfe_bow_transform_batch_device writes.  Pair p matches
@@ -761,6 +762,100 @@ int64_t orbfe_tri_search_scratch_bytes(int32_t npairs, int32_t cap);
 int32_t orbfe_tri_search_info(int32_t what);
 /* 0 = k_tri_search (LDS tiles, a group of lanes per feature; default), 1 = one thread per keyframe-1 feature: same results */
 orbfe_status orbfe_matcher_set_triangulation_kernel(orbfe_matcher *m, int32_t kernel);
+
+/* CreateNewMapPoints, device-resident: the rest of the neighbour loop of LocalMapping::CreateNewMapPoints up to
+ * `new MapPoint(x3D, ...)` (src/LocalMapping.cc:424-615) and KeyFrame::ComputeSceneMedianDepth (src/KeyFrame.cc:724-754), on the
+ * keyframe block of the batched search (csrc/orbfe_newpoints.hip, csrc/orbfe_newpoints.h).  The oracle is
+ * tests/newpoints_oracle.py, a numpy restatement under numbered rules (N1 ..) that NO compiled reference pins: LocalMapping.cc and
+ * KeyFrame.cc are not among the compiled reference sources.
+ *
+ * The verdict of one match = where the loop body left, in the order the reference can leave it: */
+#define ORBFE_NEWPT_LOW_PARALLAX 0   /* the final `else continue`: no stereo keypoint and too little parallax */
+#define ORBFE_NEWPT_W_ZERO 1         /* x3D(3) == 0 after the SVD */
+#define ORBFE_NEWPT_DEPTH1 2         /* z1 <= 0; also UnprojectStereo(idx1) with mvDepth <= 0, where the reference throws */
+#define ORBFE_NEWPT_DEPTH2 3
+#define ORBFE_NEWPT_ERR1 4           /* reprojection error in keyframe 1 above 5.991 (mono) / 7.8 (stereo) * sigma2 */
+#define ORBFE_NEWPT_ERR2 5
+#define ORBFE_NEWPT_DIST_ZERO 6
+#define ORBFE_NEWPT_SCALE 7          /* the scale-consistency gate */
+#define ORBFE_NEWPT_OK 8             /* a MapPoint is created */
+#define ORBFE_NEWPT_IGNORED 9        /* batch forms: an index >= the keyframe's d_n or an octave outside [0, nlevels) */
+typedef struct orbfe_newpt_key {
+    float ux, uy;                    /* mvKeysUn[idx].pt */
+    float rx, ry;                    /* mvKeys[idx].pt: what KeyFrame::UnprojectStereo reads (= ux, uy without distortion) */
+    float depth, uright;             /* mvDepth[idx], mvuRight[idx]: stereo means uright >= 0 */
+    int32_t octave;
+} orbfe_newpt_key;
+/* One match on the HOST, the function the kernel runs (no device, no handle): Tcw row-major 3x4, Ow = GetCameraCenter, both
+ * keyframes share `cam` (fx, fy, cx, cy, bf: u2_r uses keyframe 1's mbf in the reference, sic) and mb; scale_factors /
+ * level_sigma2 have nlevels entries, scale_factor = mfScaleFactor.  cos(2 * atan2(mb / 2, depth)) is evaluated with the
+ * library's canonical trig (DESIGN.md "Canonical trig"), not the host's libm.  Returns ORBFE_NEWPT_*, or -1 for a bad argument
+ * (an octave outside the tables included); x3D [3] is the point for ORBFE_NEWPT_OK. */
+int32_t orbfe_triangulate_match(const float *Tcw1, const float *Ow1, const float *Tcw2, const float *Ow2, const orbfe_track_camera *cam,
+                                float mb, const orbfe_newpt_key *k1, const orbfe_newpt_key *k2, const float *scale_factors,
+                                const float *level_sigma2, int32_t nlevels, float scale_factor, float *x3D);
+/* what the batch forms read beside the orbfe_tri_keyframes block (whose d_kps are mvKeysUn and whose d_uright they read too) */
+typedef struct orbfe_newpt_geom {
+    const orbfe_keypoint *d_kps_raw; /* [nframes][cap] mvKeys; NULL = the block's d_kps */
+    const float *d_depth;            /* [nframes][cap] mvDepth; may be NULL when d_uright is */
+    const float *d_Tcw, *d_Ow;       /* [nframes][12], [nframes][3] */
+    orbfe_track_camera cam;
+    float mb, scale_factor;
+} orbfe_newpt_geom;
+typedef struct orbfe_newpt_out {
+    uint8_t *d_verdict;              /* [npairs][cap]: ORBFE_NEWPT_* of entry j of d_pairs; entries past d_npairs[p] keep what they held */
+    int32_t *d_new_idx;              /* [npairs][cap][2] (idx1, idx2) of the accepted matches, in vMatchedIndices order = the order
+                                      * `new MapPoint` runs in; rows past d_nnew[p] keep what they held */
+    float *d_new_xyz;                /* [npairs][cap][3] their world positions */
+    int32_t *d_nnew;                 /* [npairs] */
+} orbfe_newpt_out;
+/* All matches of npairs pairs: d_pairs / d_npairs as orbfe_search_for_triangulation_batch_device writes them.  Counts are clamped
+ * into [0, cap]; a pair with a frame index outside the block gets 0 points; an entry with an index >= the keyframe's d_n or a
+ * keypoint whose octave is outside [0, nlevels) gets ORBFE_NEWPT_IGNORED (it cannot be rejected without a host read).  Ordered
+ * compaction, no atomic takes a slot.  Enqueued on `stream`: no wait, no host writes; scratch is the matcher's.  scale_factors /
+ * level_sigma2 are HOST arrays.  Limits: those of the batched search. */
+orbfe_status orbfe_triangulate_pairs_batch_device(orbfe_matcher *m, const orbfe_tri_keyframes *kf, const orbfe_newpt_geom *geom,
+                                                  const int32_t *d_kf1, const int32_t *d_kf2, int32_t npairs, const int32_t *d_pairs,
+                                                  const int32_t *d_npairs, const float *scale_factors, const float *level_sigma2,
+                                                  int32_t nlevels, const orbfe_newpt_out *out, void *stream);
+/* KeyFrame::ComputeSceneMedianDepth(q) of every keyframe of the block, one workgroup each: z = (float)(Tcw.row(2).dot(x) + Tcw(2, 3))
+ * over the occupied slots (d_has_mp != 0, slot < d_n clamped into [0, cap]), d_median[f] = the ((count - 1) / q)-th smallest,
+ * selected exactly (radix selection on order-preserving keys).  A keyframe with no MapPoint is undefined behaviour in the
+ * reference; THIS LIBRARY writes -1.0f, which the monocular baseline gate turns into a skipped pair.  d_mp_xyz [nframes][cap][3].
+ * cap <= 8192, q >= 1. */
+orbfe_status orbfe_scene_median_depth_batch_device(orbfe_matcher *m, const float *d_Tcw, const uint8_t *d_has_mp, const float *d_mp_xyz,
+                                                   const int32_t *d_n, int32_t nframes, int32_t cap, int32_t q, float *d_median,
+                                                   void *stream);
+/* the slot state CreateNewMapPoints changes, beside the keyframe block */
+typedef struct orbfe_newpt_state {
+    uint8_t *d_has_mp;               /* [nframes][cap] */
+    float *d_mp_xyz;                 /* [nframes][cap][3] */
+    int32_t *d_mp_id;                /* [nframes][cap]: -1 none, else the id of the slot's MapPoint (the caller's for its own points) */
+} orbfe_newpt_state;
+/* The neighbour loop with carried state.  The pairs arrive in round order; round r is the pairs round_off[r] .. round_off[r + 1]
+ * (a HOST array of nrounds + 1 ascending offsets, round_off[nrounds] = npairs).  Per round, on `stream`, without a host read:
+ * with `mono` the median depth (q = 2) of the round's keyframes 2 from the current state, orbfe_triangulation_pairs_batch_device,
+ * orbfe_search_for_triangulation_batch_device with the current d_has_mp (kf->d_has_mp is ignored), the triangulation above, and
+ * the claim: accepted point k of pair p has the id id_base + p * cap + k (ascending in creation order), each of its two slots takes
+ * the MAXIMUM id that claims it -- the reference's AddMapPoint leaves the last one created in a slot -- then d_has_mp = 1 and the
+ * winner's position.  Every pair of a round sees the state at the start of its round: the result equals the reference's serial
+ * loop whenever no keyframe occurs in two pairs of one round (orbfe_newpoints_plan_rounds), and nrounds == 1 is the static
+ * batch.  d_pair_skip [npairs] may be NULL.  Outputs are indexed by the pair's position in the given (round) order. */
+orbfe_status orbfe_create_new_map_points_batch_device(orbfe_matcher *m, const orbfe_tri_keyframes *kf, const orbfe_newpt_geom *geom,
+                                                      const orbfe_newpt_state *state, int32_t mono, const int32_t *d_kf1,
+                                                      const int32_t *d_kf2, int32_t npairs, const int32_t *round_off, int32_t nrounds,
+                                                      const float *scale_factors, const float *level_sigma2, int32_t nlevels,
+                                                      int32_t th_low, int32_t only_stereo, int32_t check_ori, int32_t id_base,
+                                                      uint8_t *d_pair_skip, const orbfe_tri_out *tri_out, const orbfe_newpt_out *out,
+                                                      void *stream);
+/* bytes of matcher scratch the two calls above take beside the search's; -1 outside the limits.  No device needed. */
+int64_t orbfe_newpoints_scratch_bytes(int32_t npairs, int32_t cap, int32_t nframes);
+/* The GPU-free planner (host): round_of[i] = the earliest round later than the round of every earlier pair that shares a keyframe
+ * with pair i (pairs with disjoint keyframes commute, pairs that share one keep their order); order[j] = the pair that stands at
+ * position j in round order (a stable permutation); round_off[0 .. nrounds].  round_of / order: npairs entries, round_off:
+ * npairs + 1.  Returns nrounds, or -1 for a bad argument. */
+int32_t orbfe_newpoints_plan_rounds(const int32_t *kf1, const int32_t *kf2, int32_t npairs, int32_t *round_of, int32_t *order,
+                                    int32_t *round_off);
 
 /* Frame::ComputeStereoMatches (src/Frame.cc:642-846): row-band descriptor search in the right image,
  * 11 x 11 SAD refinement over 11 shifts on the two extractors' device-resident pyramids (mvImagePyramid of the LAST

@@ -11,13 +11,15 @@ from . import _build, _header
 # The structs of include/orbfe.h that the package instantiates and passes with byref: a parameter that points to one of them is
 # POINTER of its class, every other pointer c_void_p.
 BYREF = ("orbfe_params", "orbfe_camera", "orbfe_track_camera", "orbfe_track_frames", "orbfe_track_last", "orbfe_track_map",
-         "orbfe_track_out", "orbfe_init_search_first", "orbfe_init_search_out", "orbfe_tri_keyframes", "orbfe_tri_out")
+         "orbfe_track_out", "orbfe_init_search_first", "orbfe_init_search_out", "orbfe_tri_keyframes", "orbfe_tri_out", "orbfe_newpt_geom",
+         "orbfe_newpt_out", "orbfe_newpt_state")
 with open(_build.HEADERS[-1]) as _f:
     ABI = _header.Header(_f.read(), BYREF)   # include/orbfe.h, parsed once per process: ABI.ORBFE_<NAME>, ABI.structs, ABI.prototypes
 dtype = ABI.dtype   # dtype("orbfe_sim3_model", T12=(4, 4)): the numpy record of a header struct
-OrbfeParams, OrbfeCamera, TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut, InitSearchFirst, InitSearchOut, TriKeyframes, TriOut = (
-    ABI.structs[name] for name in BYREF)
+(OrbfeParams, OrbfeCamera, TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut, InitSearchFirst, InitSearchOut, TriKeyframes, TriOut,
+ NewptGeom, NewptOut, NewptState) = (ABI.structs[name] for name in BYREF)
 KP_DTYPE, PROJ_QUERY_DTYPE, TRACK_PROJ_DTYPE = dtype("orbfe_keypoint"), dtype("orbfe_proj_query"), dtype("orbfe_track_proj")
+NEWPT_KEY_DTYPE = dtype("orbfe_newpt_key")
 
 ORBFE_OK, ORBFE_ERR_ARG, ORBFE_ERR_SIZE, ORBFE_ERR_CAP = ABI.ORBFE_OK, ABI.ORBFE_ERR_ARG, ABI.ORBFE_ERR_SIZE, ABI.ORBFE_ERR_CAP
 ORBFE_ERR_HIP, ORBFE_ERR_NOMEM, ORBFE_ERR_NODEVICE, ORBFE_ERR_STATE = (ABI.ORBFE_ERR_HIP, ABI.ORBFE_ERR_NOMEM, ABI.ORBFE_ERR_NODEVICE,

@@ -85,9 +85,6 @@ __device__ inline void inv3f(const float *S, float *D)
         for (int k = 0; k < 9; k++) D[k] = 0.0f;
 }
 
-// convertTo with a scale: v * (float)alpha + 0.0f
-__device__ inline float cvt_scale(float v, float a) { return v * a + 0.0f; }
-
 __device__ inline double norm3d(const float *v) { return sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); }
 
 __device__ inline bool parallax_cut(float c) { return c <= __uint_as_float(IN_PARALLAX_CUT_BITS) && c >= -1.0f; }
@@ -221,20 +218,7 @@ constexpr float IN_TH_H = 5.991f, IN_TH_F = 3.841f;
 
 __device__ inline float inv_sigma_square(float sigma) { return (float)(1.0 / (double)(sigma * sigma)); }
 
-// Triangulate: P1, P2 3 x 4 row-major
-template <class PA, class PW, class PV>
-__device__ inline void triangulate(float u1, float v1, float u2, float v2, const float *P1, const float *P2, PA At, PW W, PV Vt, float *x3)
-{
-    for (int c = 0; c < 4; c++) {   // At is A transposed; a * row - row2 is addWeighted: v1 * a + v2 * (-1) + 0
-        At[c * 4 + 0] = u1 * P1[8 + c] + P1[c] * -1.0f + 0.0f;
-        At[c * 4 + 1] = v1 * P1[8 + c] + P1[4 + c] * -1.0f + 0.0f;
-        At[c * 4 + 2] = u2 * P2[8 + c] + P2[c] * -1.0f + 0.0f;
-        At[c * 4 + 3] = v2 * P2[8 + c] + P2[4 + c] * -1.0f + 0.0f;
-    }
-    jacobi_svd_f(At, W, Vt, 4, 4, 4);
-    const float a = (float)(1.0 / (double)(float)Vt[15]);
-    for (int k = 0; k < 3; k++) x3[k] = cvt_scale(Vt[12 + k], a);
-}
+// Triangulate and cvt_scale: csrc/orbfe_svd.h (shared with CreateNewMapPoints, csrc/orbfe_newpoints.h)
 
 struct InHyp {
     float R[9], t[3], P2[12], O2[3];

@@ -285,6 +285,28 @@ ORBFE_HD inline void jacobi_svd_f(PA At, PW W, PV Vt, int m, int n, int n1)
     }
 }
 
+// convertTo with a scale: v * (float)alpha + 0.0f
+ORBFE_HD inline float cvt_scale(float v, float a) { return v * a + 0.0f; }
+
+// Initializer::Triangulate (src/Initializer.cc) and the linear triangulation of LocalMapping::CreateNewMapPoints
+// (src/LocalMapping.cc:498-513): P1, P2 3 x 4 row-major, (u, v) the two observations.  x3 = vt.row(3)(0..2) / vt.row(3)(3); the
+// return value is vt.row(3)(3), which CreateNewMapPoints tests against 0 before it divides (x3 is not to be used then).
+template <class PA, class PW, class PV>
+ORBFE_HD inline float triangulate(float u1, float v1, float u2, float v2, const float *P1, const float *P2, PA At, PW W, PV Vt, float *x3)
+{
+    for (int c = 0; c < 4; c++) {   // At is A transposed; a * row - row2 is addWeighted: v1 * a + v2 * (-1) + 0
+        At[c * 4 + 0] = u1 * P1[8 + c] + P1[c] * -1.0f + 0.0f;
+        At[c * 4 + 1] = v1 * P1[8 + c] + P1[4 + c] * -1.0f + 0.0f;
+        At[c * 4 + 2] = u2 * P2[8 + c] + P2[c] * -1.0f + 0.0f;
+        At[c * 4 + 3] = v2 * P2[8 + c] + P2[4 + c] * -1.0f + 0.0f;
+    }
+    jacobi_svd_f(At, W, Vt, 4, 4, 4);
+    const float w = Vt[15];
+    const float a = (float)(1.0 / (double)w);
+    for (int k = 0; k < 3; k++) x3[k] = cvt_scale(Vt[12 + k], a);
+    return w;
+}
+
 // cv::SVD::compute on A (m x n row-major, m >= n): At takes the transpose
 ORBFE_HD inline void svd_compute(const double *A, int m, int n, double *At, double *W, double *Vt)
 {

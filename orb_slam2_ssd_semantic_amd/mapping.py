@@ -1,17 +1,19 @@
-"""LocalMapping's keyframe-rate matcher, batched and device-resident (csrc/orbfe_tri_search.hip; include/orbfe.h
-"SearchForTriangulation, batched"): the neighbour loop of LocalMapping::CreateNewMapPoints up to vMatchedPairs -- the baseline
-gate, ComputeF12 and the epipole of every (keyframe, neighbour) pair, then ORBmatcher::SearchForTriangulation for all pairs in
-one call.  The triangulation of the pairs and KeyFrame::ComputeSceneMedianDepth stay with the caller.
+"""LocalMapping::CreateNewMapPoints, batched and device-resident (csrc/orbfe_tri_search.hip, csrc/orbfe_newpoints.hip; include/orbfe.h
+"SearchForTriangulation, batched" and "CreateNewMapPoints, device-resident"): the baseline gate, ComputeF12 and the epipole of every
+(keyframe, neighbour) pair, ORBmatcher::SearchForTriangulation for all pairs in one call, the triangulation and the gates of every
+match up to `new MapPoint(x3D, ...)`, KeyFrame::ComputeSceneMedianDepth, and the neighbour loop with the slot state carried from
+one round of pairs to the next.  The triangulation's oracle is tests/newpoints_oracle.py, a numpy restatement that no compiled
+reference pins.
 
 The *_batch_device methods are thin: device pointers (ints) and the structs of _ffi, asynchronous on `stream`.
-search_for_triangulation_device() takes torch tensors and allocates the results.  compute_f12(), tri_search_scratch_bytes() and
-tri_search_info() need no GPU."""
+search_for_triangulation_device() and create_new_map_points_device() take torch tensors and allocate the results.  compute_f12(),
+triangulate_match(), plan_rounds(), the *_scratch_bytes() and tri_search_info() need no GPU."""
 import ctypes as C
 
 import numpy as np
 
 from . import _ffi
-from ._ffi import TriKeyframes, TriOut, check, ptr, stream_arg
+from ._ffi import NEWPT_KEY_DTYPE, NewptGeom, NewptOut, NewptState, TriKeyframes, TriOut, check, ptr, stream_arg
 from .tracking import TH_LOW, camera  # noqa: F401  (camera(): the orbfe_track_camera both keyframes share)
 
 _INFO = {k[len("ORBFE_TRI_INFO_"):].lower(): v for k, v in _ffi.ABI.constants.items() if k.startswith("ORBFE_TRI_INFO_")}
@@ -43,6 +45,56 @@ def tri_search_info():
     return {k: int(_ffi.lib().orbfe_tri_search_info(v)) for k, v in _INFO.items()}
 
 
+NEWPT = {k[len("ORBFE_NEWPT_"):]: v for k, v in _ffi.ABI.constants.items() if k.startswith("ORBFE_NEWPT_")}   # verdict by name
+
+
+def newpt_key(ux, uy, octave, depth=-1.0, uright=-1.0, rx=None, ry=None):
+    """one orbfe_newpt_key record: mvKeysUn (ux, uy, octave), mvKeys (rx, ry; default the same), mvDepth, mvuRight"""
+    k = np.zeros(1, NEWPT_KEY_DTYPE)
+    k["ux"], k["uy"], k["rx"], k["ry"] = ux, uy, ux if rx is None else rx, uy if ry is None else ry
+    k["depth"], k["uright"], k["octave"] = depth, uright, octave
+    return k
+
+
+def triangulate_match(Tcw1, Ow1, Tcw2, Ow2, cam, mb, k1, k2, scale_factors, level_sigma2, scale_factor):
+    """the loop body of CreateNewMapPoints for one match on the host (orbfe_triangulate_match, the function the kernel runs):
+    -> (verdict, x3D float32 [3]); k1 / k2 from newpt_key()"""
+    a = [np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1)[:n]) for v, n in ((Tcw1, 12), (Ow1, 3), (Tcw2, 12), (Ow2, 3))]
+    sf, s2 = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+    x = np.zeros(3, np.float32)
+    v = _ffi.lib().orbfe_triangulate_match(ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), C.byref(cam), float(mb), ptr(k1), ptr(k2), ptr(sf),
+                                           ptr(s2), min(len(sf), len(s2)), float(scale_factor), ptr(x))
+    if v < 0:
+        raise ValueError("orbfe_triangulate_match: " + _ffi.last_error())
+    return int(v), x
+
+
+def plan_rounds(kf1, kf2):
+    """orbfe_newpoints_plan_rounds: -> (round_of [P], order [P], round_off [nrounds + 1]) int32; pair order[j] stands at position j"""
+    k1, k2 = np.ascontiguousarray(kf1, np.int32).reshape(-1), np.ascontiguousarray(kf2, np.int32).reshape(-1)
+    if len(k1) != len(k2):
+        raise ValueError("kf1 and kf2 have one entry per pair each")
+    P = len(k1)
+    round_of, order, off = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P + 1, np.int32)
+    nr = _ffi.lib().orbfe_newpoints_plan_rounds(ptr(k1), ptr(k2), P, ptr(round_of), ptr(order), ptr(off))
+    if nr < 0:
+        raise ValueError("orbfe_newpoints_plan_rounds: " + _ffi.last_error())
+    return round_of, order, off[:nr + 1].copy()
+
+
+def newpoints_scratch_bytes(npairs, cap, nframes):
+    """bytes of matcher scratch the triangulation and the neighbour loop take beside the search's; no GPU needed"""
+    n = _ffi.lib().orbfe_newpoints_scratch_bytes(int(npairs), int(cap), int(nframes))
+    if n < 0:
+        raise ValueError("outside the limits: 1 <= cap <= 8192, npairs * cap < 2^25, nframes >= 0")
+    return int(n)
+
+
+def geometry_struct(d_Tcw, d_Ow, cam, mb, scale_factor, d_depth=None, d_kps_raw=None):
+    """orbfe_newpt_geom from torch tensors (the caller keeps them alive)"""
+    return NewptGeom(_dp(d_kps_raw), _dp(d_depth), _dp(d_Tcw), _dp(d_Ow), cam, float(mb), float(scale_factor))
+
+
 def keyframes_struct(d_kps, d_desc, d_n, cap, nframes, d_fv_node, d_fv_off, d_fv_idx, d_counts, d_uright=None, d_has_mp=None):
     """orbfe_tri_keyframes from torch tensors (the caller keeps them alive)"""
     return TriKeyframes(_dp(d_kps), _dp(d_desc), _dp(d_n), int(cap), int(nframes), _dp(d_uright), _dp(d_has_mp), _dp(d_fv_node),
@@ -53,6 +105,9 @@ class LocalMapper:
     """The device-resident LocalMapping calls on a matcher's scratch: LocalMapper(ORBmatcher(...))"""
 
     compute_f12 = staticmethod(compute_f12)
+    triangulate_match = staticmethod(triangulate_match)
+    plan_rounds = staticmethod(plan_rounds)
+    newpoints_scratch_bytes = staticmethod(newpoints_scratch_bytes)
     tri_search_scratch_bytes = staticmethod(tri_search_scratch_bytes)
     tri_search_info = staticmethod(tri_search_info)
 
@@ -96,3 +151,61 @@ class LocalMapper:
         self.SearchForTriangulation_batch_device(kf, _dp(kf1), _dp(kf2), P, _dp(F12), _dp(epi), _dp(pair_skip), scale_factors, level_sigma2,
                                                  out, th_low, only_stereo, check_ori, stream_arg(dev, stream))
         return match12, nmatches, pairs, npairs
+
+    @staticmethod
+    def _levels(scale_factors, level_sigma2):
+        sf, s2 = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+        if len(sf) != len(s2):
+            raise ValueError("scale_factors and level_sigma2 have one entry per level each")
+        return sf, s2
+
+    def TriangulatePairs_batch_device(self, kf, geom, d_kf1, d_kf2, npairs, d_pairs, d_npairs, scale_factors, level_sigma2, out, stream=None):
+        sf, s2 = self._levels(scale_factors, level_sigma2)
+        check(self._L.orbfe_triangulate_pairs_batch_device(self._mt._m, C.byref(kf), C.byref(geom), d_kf1, d_kf2, int(npairs), d_pairs, d_npairs,
+                                                           ptr(sf), ptr(s2), len(sf), C.byref(out), stream),
+              "orbfe_triangulate_pairs_batch_device")
+
+    def SceneMedianDepth_batch_device(self, d_Tcw, d_has_mp, d_mp_xyz, d_n, nframes, cap, q, d_median, stream=None):
+        check(self._L.orbfe_scene_median_depth_batch_device(self._mt._m, d_Tcw, d_has_mp, d_mp_xyz, d_n, int(nframes), int(cap), int(q),
+                                                            d_median, stream), "orbfe_scene_median_depth_batch_device")
+
+    def CreateNewMapPoints_batch_device(self, kf, geom, state, mono, d_kf1, d_kf2, npairs, round_off, scale_factors, level_sigma2, tri_out,
+                                        out, th_low=TH_LOW, only_stereo=False, check_ori=True, id_base=0, d_pair_skip=None, stream=None):
+        """round_off: the HOST array of nrounds + 1 offsets into the pairs, which stand in round order"""
+        sf, s2 = self._levels(scale_factors, level_sigma2)
+        ro = np.ascontiguousarray(round_off, np.int32).reshape(-1)
+        if len(ro) < 1:
+            raise ValueError("round_off has nrounds + 1 entries")
+        check(self._L.orbfe_create_new_map_points_batch_device(self._mt._m, C.byref(kf), C.byref(geom), C.byref(state), int(mono), d_kf1, d_kf2,
+                                                               int(npairs), ptr(ro), len(ro) - 1, ptr(sf), ptr(s2), len(sf), int(th_low),
+                                                               int(only_stereo), int(check_ori), int(id_base), d_pair_skip, C.byref(tri_out),
+                                                               C.byref(out), stream), "orbfe_create_new_map_points_batch_device")
+
+    def create_new_map_points_device(self, kf, geom, has_mp, mp_xyz, mp_id, kf1, kf2, scale_factors, level_sigma2, mono=False, th_low=TH_LOW,
+                                     only_stereo=False, check_ori=True, id_base=0, round_off=None, stream=None):
+        """The neighbour loop on torch tensors.  kf / geom: keyframes_struct() / geometry_struct(); has_mp uint8 [B][cap], mp_xyz
+        float32 [B][cap][3], mp_id int32 [B][cap] are UPDATED in place; kf1 / kf2: the pairs in the reference's loop order (any
+        int sequence).  Plans the rounds (plan_rounds) unless round_off is given (then the pairs are taken as they stand), allocates
+        the outputs and returns a dict: order (position -> the caller's pair), round_off, and per POSITION new_idx [P][cap][2],
+        new_xyz [P][cap][3], nnew [P], verdict [P][cap], match12 [P][cap], nmatches [P], pairs [P][cap][2], npairs [P], pair_skip
+        [P].  Nothing is read back."""
+        import torch
+        k1, k2 = np.asarray(kf1, np.int32).reshape(-1), np.asarray(kf2, np.int32).reshape(-1)
+        if round_off is None:
+            _, order, round_off = plan_rounds(k1, k2)
+        else:
+            order = np.arange(len(k1), dtype=np.int32)
+        P, cap, dev = len(k1), kf.cap, has_mp.device
+        d1, d2 = (torch.from_numpy(np.ascontiguousarray(k[order])).to(dev) for k in (k1, k2))
+        i32 = dict(dtype=torch.int32, device=dev)
+        r = dict(order=order, round_off=np.asarray(round_off, np.int32), new_idx=torch.full((P, cap, 2), -1, **i32),
+                 new_xyz=torch.zeros((P, cap, 3), dtype=torch.float32, device=dev), nnew=torch.zeros((P,), **i32),
+                 verdict=torch.full((P, cap), 255, dtype=torch.uint8, device=dev), match12=torch.full((P, cap), -1, **i32),
+                 nmatches=torch.zeros((P,), **i32), pairs=torch.full((P, cap, 2), -1, **i32), npairs=torch.zeros((P,), **i32),
+                 pair_skip=torch.zeros((P,), dtype=torch.uint8, device=dev))
+        self.CreateNewMapPoints_batch_device(kf, geom, NewptState(_dp(has_mp), _dp(mp_xyz), _dp(mp_id)), mono, _dp(d1), _dp(d2), P, round_off,
+                                             scale_factors, level_sigma2, TriOut(_dp(r["match12"]), _dp(r["nmatches"]), _dp(r["pairs"]), _dp(r["npairs"])),
+                                             NewptOut(_dp(r["verdict"]), _dp(r["new_idx"]), _dp(r["new_xyz"]), _dp(r["nnew"])), th_low, only_stereo,
+                                             check_ori, id_base, _dp(r["pair_skip"]), stream_arg(dev, stream))
+        r["kf1"], r["kf2"] = d1, d2
+        return r

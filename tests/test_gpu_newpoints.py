@@ -1,0 +1,470 @@
+"""CreateNewMapPoints device-resident (csrc/orbfe_newpoints.hip): the triangulation of all matches of a batch of pairs, the scene
+median depth and the neighbour loop with carried slot state, bit for bit against tests/newpoints_oracle.py -- an UNPINNED numpy
+restatement (LocalMapping.cc is not among the compiled reference sources); the search inside the loop is the oracle's matching
+core + replay, as in test_gpu_tri_search.py.  No tolerances.  Outputs start as sentinels, so what must not be written shows."""
+import numpy as np
+import pytest
+
+import newpoints_cases as NC
+import newpoints_oracle as NO
+import tri_batch_cases as TC
+from test_gpu_tri_search import Block, _dev
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+SENT = -7
+
+
+@pytest.fixture(scope="module")
+def mt():
+    from orb_slam2_ssd_semantic_amd import ORBmatcher
+    m = ORBmatcher(0.9, True)
+    yield m
+    m.close()
+
+
+@pytest.fixture(scope="module", params=[0, 1], ids=["lds-tiles", "thread-per-feature"])
+def lm(request, mt):
+    """both search kernels, as test_gpu_tri_search.py runs them"""
+    from orb_slam2_ssd_semantic_amd import LocalMapper
+    m = LocalMapper(mt)
+    m.set_triangulation_kernel(request.param)
+    yield m
+    m.set_triangulation_kernel(0)
+
+
+@pytest.fixture(scope="module")
+def lm0(mt):
+    from orb_slam2_ssd_semantic_amd import LocalMapper
+    return LocalMapper(mt)
+
+
+def _camera(c):
+    from orb_slam2_ssd_semantic_amd import mapping
+    return mapping.camera(c["fx"], c["fy"], c["cx"], c["cy"], c["bf"], 0.0, 640.0, 0.0, 480.0)
+
+
+class NBlock(Block):
+    """test_gpu_tri_search's block plus what the triangulation reads (depth, poses) and the slot state"""
+
+    def __init__(self, frames, cam=NC.CAM, mb=NC.MB, scale_factor=NC.SCALE_FACTOR, cap=None, n=None):
+        import torch
+        from orb_slam2_ssd_semantic_amd import mapping
+        super().__init__(frames, cap=cap, n=n)
+        B, cap = max(self.B, 1), self.cap
+        depth, xyz = np.full((B, cap), -1, f32), np.zeros((B, cap, 3), f32)
+        T, O = np.zeros((B, 12), f32), np.zeros((B, 3), f32)
+        for b, f in enumerate(frames):
+            k = len(f["desc"])
+            if k:
+                depth[b] = f["depth"][np.arange(cap) % k]   # rows past the count: the keyframe's own features again
+                xyz[b, :k] = f["mp_xyz"]
+            T[b], O[b] = f["Tcw"], f["Ow"]
+        self.frames = frames
+        self.t.update(depth=_dev(depth), Tcw=_dev(T), Ow=_dev(O), xyz=_dev(xyz), id=torch.full((B, cap), -1, dtype=torch.int32, device="cuda"))
+        self.mp0, self.xyz0 = self.t["mp"].clone(), self.t["xyz"].clone()
+        self.geom = mapping.geometry_struct(self.t["Tcw"], self.t["Ow"], _camera(cam), mb, scale_factor, self.t["depth"])
+
+    def reset(self):
+        self.t["mp"].copy_(self.mp0)
+        self.t["xyz"].copy_(self.xyz0)
+        self.t["id"].fill_(-1)
+
+    def state(self):
+        return tuple(self.t[k].cpu().numpy() for k in ("mp", "xyz", "id"))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ B: all matches of P pairs
+def _triangulate(lm, blk, kf1, kf2, rows, counts, sf=NC.SF, s2=NC.S2):
+    """rows: per pair the (idx1, idx2) list that fills d_pairs; counts: what d_npairs says -> (verdict, new_idx, new_xyz, nnew)"""
+    import torch
+    from orb_slam2_ssd_semantic_amd._ffi import NewptOut
+    P, cap = len(kf1), blk.cap
+    pairs = np.full((P, cap, 2), 0, np.int32)
+    for p, r in enumerate(rows):
+        pairs[p, :len(r)] = r
+    d_pairs, d_np = _dev(pairs), _dev(np.asarray(counts, np.int32))
+    ver = torch.full((P, cap), 200, dtype=torch.uint8, device="cuda")
+    idx = torch.full((P, cap, 2), SENT, dtype=torch.int32, device="cuda")
+    xyz = torch.full((P, cap, 3), float(SENT), dtype=torch.float32, device="cuda")
+    nnew = torch.full((P + 16,), SENT, dtype=torch.int32, device="cuda")
+    d1, d2 = _dev(np.asarray(kf1, np.int32)), _dev(np.asarray(kf2, np.int32))
+    lm.TriangulatePairs_batch_device(blk.kf, blk.geom, d1.data_ptr(), d2.data_ptr(), P, d_pairs.data_ptr(), d_np.data_ptr(), sf, s2,
+                                     NewptOut(ver.data_ptr(), idx.data_ptr(), xyz.data_ptr(), nnew.data_ptr()))
+    torch.cuda.synchronize()
+    nn = nnew.cpu().numpy()
+    assert (nn[P:] == SENT).all()
+    return ver.cpu().numpy(), idx.cpu().numpy(), xyz.cpu().numpy(), nn[:P]
+
+
+def _check_pair(got, p, want, cnt, what):
+    """want: [(verdict, x3D)] of the first cnt entries of the pair's row"""
+    ver, idx, xyz, nnew = got
+    assert ver[p, :cnt].tolist() == [w[0] for w in want[:cnt]], what
+    assert (ver[p, cnt:] == 200).all(), (what, "verdicts past the count written")
+    ok = [j for j in range(cnt) if want[j][0] == NO.OK]
+    assert nnew[p] == len(ok), (what, nnew[p], len(ok))
+    assert (idx[p, len(ok):] == SENT).all() and (xyz[p, len(ok):] == SENT).all(), (what, "rows past nnew written")
+    return ok
+
+
+@pytest.fixture(scope="module")
+def many_matches():
+    """2 keyframes, 512 candidate matches and the oracle's verdict on each, computed once"""
+    frames = NC.scene(11, 2, 300)
+    pairs = NC.true_and_false_matches(frames, 0, 1, 512, 12)
+    want = [NO.triangulate_match(*NC.match_args(frames, 0, 1, a, b)) for a, b in pairs]
+    assert {w[0] for w in want} >= {NO.OK, NO.LOW_PARALLAX, NO.DEPTH1, NO.ERR1, NO.SCALE}
+    return frames, pairs, want
+
+
+@pytest.mark.parametrize("cap, counts", [(303, (0, 1, 63, 64, 65)), (512, (255, 256, 257))], ids=["cap303", "cap512"])
+def test_triangulate_pairs_counts(lm0, many_matches, cap, counts):
+    """0, 1, 63, 64, 65 and 255, 256, 257 matches per pair: the wave and workgroup edges of the ordered compaction and of the
+    chunking; every pair its own slice of the 512 candidate matches"""
+    frames, pairs, want = many_matches
+    blk = NBlock(frames, cap=cap)
+    P = len(counts)
+    starts = [37 * p for p in range(P)]
+    rows = [pairs[s:s + c] for s, c in zip(starts, counts)]
+    got = _triangulate(lm0, blk, [0] * P, [1] * P, rows, counts)
+    for p, (s, c) in enumerate(zip(starts, counts)):
+        ok = _check_pair(got, p, want[s:s + c], c, (cap, c))
+        assert np.array_equal(got[1][p, :len(ok)], pairs[s:s + c][ok])
+        assert np.array_equal(_bits(got[2][p, :len(ok)]), _bits(np.array([want[s + j][1] for j in ok], f32).reshape(-1, 3)))
+
+
+def test_triangulate_pairs_planted(lm0):
+    """every planted edge in one call (one pair each: they need their own poses) on the planted camera and level tables"""
+    frames, pairs = NC.planted_frames()
+    blk = NBlock(frames, cam=NC.P_CAM, mb=NC.P_MB, scale_factor=NC.P_SCALE_FACTOR)
+    P = len(pairs)
+    got = _triangulate(lm0, blk, [p[0] for p in pairs], [p[1] for p in pairs], [[(0, 0)]] * P, [1] * P, NC.P_SF, NC.P_S2)
+    for p, c in enumerate(NC.planted()):
+        want = NO.triangulate_match(*c["args"])
+        assert c["want"] is None or want[0] == c["want"]
+        ok = _check_pair(got, p, [want], 1, c["name"])
+        if ok:
+            assert np.array_equal(_bits(got[2][p, 0]), _bits(want[1])), c["name"]
+
+
+def test_triangulate_pairs_what_cannot_be_rejected(lm0, many_matches):
+    """an empty (skipped) pair, frame indices outside the block, d_npairs above cap and below zero, an index >= d_n, an octave
+    outside the table: clamped, ignored or left alone, never read out of bounds"""
+    frames, pairs, want = many_matches
+    frames = [dict(f) for f in frames]
+    oc = frames[1]["octave"].copy()
+    bad_oct = [int(pairs[3, 1]), int(pairs[9, 1])]
+    oc[bad_oct[0]], oc[bad_oct[1]] = TC.NLEVELS, -1
+    frames[1]["octave"] = oc
+    cap = 320
+    blk = NBlock(frames, cap=cap, n=[300, 300])
+    row = pairs[:cap].copy()
+    row[5, 0], row[6, 1], row[7, 0] = 300, 310, -1          # >= d_n (the rows behind hold real features), negative
+    dead = {j for j in range(cap) if row[j, 1] in bad_oct} | {5, 6, 7}
+    kf1, kf2 = [0, 0, 2, 0, -1, 0], [1, 1, 1, 2, 1, 1]
+    counts = [0, cap + 50, 20, 20, 20, -3]
+    got = _triangulate(lm0, blk, kf1, kf2, [row[:0], row, row[:20], row[:20], row[:20], row[:20]], counts)
+    w = [(NO.IGNORED, None) if j in dead else want[j] for j in range(cap)]
+    _check_pair(got, 0, w, 0, "empty")
+    ok = _check_pair(got, 1, w, cap, "npairs above cap")
+    assert len(dead) >= 5 and np.array_equal(got[1][1, :len(ok)], row[ok])
+    assert np.array_equal(_bits(got[2][1, :len(ok)]), _bits(np.array([w[j][1] for j in ok], f32)))
+    for p in (2, 3, 4, 5):
+        _check_pair(got, p, [], 0, "pair %d" % p)
+
+
+# ------------------------------------------------------------------------------------------------ C: the scene median depth
+def _median(lm, T, has, xyz, n, cap, q):
+    import torch
+    B = len(n)
+    out = torch.full((B + 16,), float(SENT), dtype=torch.float32, device="cuda")
+    dT, dh, dx, dn = _dev(T), _dev(has), _dev(xyz), _dev(np.asarray(n, np.int32))
+    lm.SceneMedianDepth_batch_device(dT.data_ptr(), dh.data_ptr(), dx.data_ptr(), dn.data_ptr(), B, cap, q, out.data_ptr())
+    torch.cuda.synchronize()
+    o = out.cpu().numpy()
+    assert (o[B:] == SENT).all()
+    return o[:B]
+
+
+@pytest.mark.parametrize("q", [2, 3])
+def test_scene_median_depth(lm0, q):
+    """0, 1, 2, 3, 64, 65 and cap occupied slots, slots past d_n occupied too (not counted), negative depths, runs of equal depths,
+    d_n above cap; the value is the ((count - 1) / q)-th smallest, exactly"""
+    rng = np.random.default_rng(7 + q)
+    cap = 200
+    occ = [0, 1, 2, 3, 64, 65, cap, 90, 120]
+    B = len(occ)
+    T = np.concatenate([np.stack([NC._frame_pose(rng, rng.normal(0, 1, 3), 20.0)[0] for _ in range(B)])], 0)
+    xyz = rng.normal(0, 6, (B, cap, 3)).astype(f32)       # around the cameras: about half the depths are negative
+    xyz[7] = np.repeat(xyz[7, :10], 20, axis=0)           # frame 7: every depth twenty times
+    has, n = np.zeros((B, cap), np.uint8), np.full(B, cap - 20, np.int32)
+    for b, k in enumerate(occ):
+        lim = cap if k == cap else cap - 20
+        has[b, rng.permutation(lim)[:k]] = 1
+        has[b, lim:] = 1                                  # occupied slots past d_n
+    n[6] = cap + 9                                        # clamped
+    got = _median(lm0, T, has, xyz, n, cap, q)
+    want = [NO.scene_median_depth(T[b], has[b], xyz[b], min(n[b], cap), q) for b in range(B)]
+    assert want[0] == -1 and min(want[1:]) < 0 < max(want[1:]) and all(float(w) != 0 for w in want)
+    assert _bits(got).tolist() == _bits(want).tolist()
+
+
+def test_scene_median_depth_largest_block(lm0):
+    rng = np.random.default_rng(3)
+    cap, B = 8192, 2
+    T = np.stack([NC._frame_pose(rng, (0, 0, 0), 10.0)[0] for _ in range(B)])
+    xyz = (rng.normal(0, 1, (B, cap, 3)) + (0, 0, 4)).astype(f32)
+    has = np.ones((B, cap), np.uint8)
+    has[1, ::3] = 0
+    got = _median(lm0, T, has, xyz, [cap, cap], cap, 2)
+    want = [NO.scene_median_depth(T[b], has[b], xyz[b], cap, 2) for b in range(B)]
+    assert _bits(got).tolist() == _bits(want).tolist()
+
+
+# ------------------------------------------------------------------------------------------------ D: the neighbour loop
+def _loop(lm, blk, pairs, round_off=None, mono=False):
+    """-> (per pair in the CALLER's order: dict like the oracle's one_pair, state arrays, raw bytes)"""
+    import torch
+    has, xyz, ids = blk.t["mp"], blk.t["xyz"], blk.t["id"]
+    r = lm.create_new_map_points_device(blk.kf, blk.geom, has, xyz, ids, [p[0] for p in pairs], [p[1] for p in pairs], NC.SF, NC.S2,
+                                        mono=mono, round_off=round_off)
+    torch.cuda.synchronize()
+    h = {k: v.cpu().numpy() for k, v in r.items() if hasattr(v, "cpu")}
+    outs = [None] * len(pairs)
+    for pos, i in enumerate(r["order"]):
+        npr, nn = int(h["npairs"][pos]), int(h["nnew"][pos])
+        assert h["nmatches"][pos] == npr and (h["verdict"][pos, npr:] == 255).all() and (h["new_idx"][pos, nn:] == -1).all()
+        outs[i] = dict(skip=bool(h["pair_skip"][pos]), pairs=h["pairs"][pos, :npr], verdict=h["verdict"][pos, :npr],
+                       new_idx=h["new_idx"][pos, :nn], new_xyz=h["new_xyz"][pos, :nn], pos=pos)
+    raw = b"".join(h[k].tobytes() for k in sorted(h)) + b"".join(a.tobytes() for a in blk.state())
+    return outs, r, raw
+
+
+def _same_outputs(got, want, what=""):
+    for p, (g, w) in enumerate(zip(got, want)):
+        assert g["skip"] == bool(w["skip"]), (what, p, "skip")
+        assert np.array_equal(g["pairs"], w["pairs"]), (what, p, "pairs")
+        assert g["verdict"].tolist() == w["verdict"].tolist(), (what, p, "verdict")
+        assert np.array_equal(g["new_idx"], w["new_idx"]) and np.array_equal(_bits(g["new_xyz"]), _bits(w["new_xyz"])), (what, p, "points")
+
+
+def _same_state(blk, want, what=""):
+    has, xyz, ids = blk.state()
+    B = len(want[0])
+    assert np.array_equal(has[:B], want[0]), what
+    assert np.array_equal(ids[:B], want[2]), what
+    assert np.array_equal(_bits(xyz[:B])[want[0] != 0], _bits(want[1])[want[0] != 0]), what
+
+
+def _differs(a, b):
+    return any(not np.array_equal(x["pairs"], y["pairs"]) for x, y in zip(a, b))
+
+
+@pytest.fixture(scope="module")
+def neighbours():
+    """keyframe 0 against three neighbours that see the same landmarks, and the oracle's serial and static results"""
+    frames, cap = NC.scene(300, 4, 60, nnodes=3, p_stereo=0.6), 64
+    pairs = [(0, 1), (0, 2), (0, 3)]
+    s_serial, s_static = NO.new_state(frames, cap), NO.new_state(frames, cap)
+    serial = NO.serial_loop(frames, pairs, s_serial, cap, **NC.loop_kw())
+    static = NO.round_loop(frames, pairs, [0, 3], s_static, cap, **NC.loop_kw())
+    assert _differs(serial, static) and sum(len(o["new_idx"]) for o in serial) > 20
+    return frames, cap, pairs, (serial, s_serial), (static, s_static)
+
+
+def test_neighbour_loop_carries_the_state(lm, neighbours):
+    """the planned rounds (3 rounds of one pair) equal the oracle's serial loop; one round of three pairs equals the static batch;
+    and the two DIFFER, so a loop that forgets the state cannot pass.  Twice on reset state: identical bytes."""
+    frames, cap, pairs, (serial, s_serial), (static, s_static) = neighbours
+    blk = NBlock(frames, cap=cap)
+    got, r, raw = _loop(lm, blk, pairs)
+    assert list(r["round_off"]) == [0, 1, 2, 3]
+    _same_outputs(got, serial, "rounds")
+    _same_state(blk, s_serial, "rounds")
+    blk.reset()
+    got1, _, raw1 = _loop(lm, blk, pairs)
+    assert raw1 == raw
+    blk.reset()
+    got_static, _, _ = _loop(lm, blk, pairs, round_off=[0, 3])
+    _same_outputs(got_static, static, "static")
+    _same_state(blk, s_static, "static")
+    assert _differs(got, got_static)
+
+
+def test_two_features_take_the_same_neighbour_feature(lm):
+    """keyframe 0 holds some features twice: both copies match the same keyframe-2 feature (the search never marks it), both points
+    are created and emitted, and the neighbour's slot holds the later one"""
+    frames, cap = NC.scene(310, 2, 50, nnodes=2, p_stereo=0.5), 80
+    f0 = frames[0]
+    n, dup = len(f0["desc"]), np.arange(0, 20)
+    sel = np.concatenate([np.arange(n), dup])
+    g = TC.keyframe(f0["desc"][sel], f0["xy"][sel], f0["octave"][sel], f0["angle"][sel], f0["uRight"][sel], f0["has_mp"][sel],
+                    TC.with_nodes(dict(fv=None), TC.nodes_of(f0)[sel])["fv"])
+    g.update(Tcw=f0["Tcw"], Ow=f0["Ow"], depth=f0["depth"][sel], mp_xyz=f0["mp_xyz"][sel])
+    frames = [g, frames[1]]
+    state = NO.new_state(frames, cap)
+    want = NO.serial_loop(frames, [(0, 1)], state, cap, **NC.loop_kw())
+    idx2 = want[0]["new_idx"][:, 1]
+    twice = [v for v in set(idx2.tolist()) if (idx2 == v).sum() == 2]
+    assert len(twice) >= 3, "the case must hold keyframe-2 features that two points claim"
+    blk = NBlock(frames, cap=cap)
+    got, r, _ = _loop(lm, blk, [(0, 1)])
+    _same_outputs(got, want)
+    _same_state(blk, state)
+    ids = blk.state()[2]
+    for v in twice:
+        k = np.nonzero(got[0]["new_idx"][:, 1] == v)[0]
+        assert ids[1, v] == k.max()      # id = position * cap + k with position 0: the later of the two
+
+
+def test_disjoint_neighbourhoods_share_rounds(lm):
+    frames, cap = NC.scene(320, 6, 50, nnodes=3, p_stereo=0.5, centres=[(0.3 * b, 0.02 * b, 0) for b in range(6)]), 56
+    pairs = [(0, 1), (0, 2), (3, 4), (3, 5), (0, 4)]
+    _, order, off = NO.plan_rounds([p[0] for p in pairs], [p[1] for p in pairs])
+    assert list(off) == [0, 2, 4, 5]
+    state = NO.new_state(frames, cap)
+    want = NO.serial_loop(frames, pairs, state, cap, pos=np.argsort(order), **NC.loop_kw())
+    blk = NBlock(frames, cap=cap)
+    got, r, _ = _loop(lm, blk, pairs)
+    assert list(r["order"]) == list(order) and list(r["round_off"]) == list(off)
+    _same_outputs(got, want)
+    _same_state(blk, state)
+
+
+def test_monocular_median_depth_moves_between_rounds(lm):
+    """monocular: keyframe 1 starts with three near MapPoints, so keyframe 2, two centimetres beside it, is far enough
+    (baseline / median >= 0.01); round 1 gives keyframe 1 new, deeper points, its median depth grows, and in round 2 the pair
+    (2, 1) is skipped -- only because of round 1.  In one static round it is not."""
+    frames = NC.scene(330, 3, 60, nnodes=3, p_stereo=0.0, centres=[(0.4, 0, 0), (0, 0, 0), (0.02, 0, 0)], rot_deg=0.3)
+    cap = 64
+    f1 = frames[1]
+    z = np.array([NO.np_cam_coord(f1["Tcw"], 2, x) for x in f1["mp_xyz"]])
+    near = np.argsort(z)[:3]
+    f1["has_mp"] = np.zeros(len(z), np.uint8)
+    f1["has_mp"][near] = 1
+    assert z[near].max() < 1.9
+    for b in (0, 2):
+        frames[b]["has_mp"] = (np.arange(60) % 4 == 0).astype(np.uint8)
+    pairs = [(0, 1), (2, 1)]
+    kw = NC.loop_kw(mono=True)
+    state, state1 = NO.new_state(frames, cap), NO.new_state(frames, cap)
+    want = NO.serial_loop(frames, pairs, state, cap, **kw)
+    static = NO.round_loop(frames, pairs, [0, 2], state1, cap, **kw)
+    assert [w["skip"] for w in want] == [False, True] and [w["skip"] for w in static] == [False, False]
+    assert want[1]["median"] > want[0]["median"] == static[1]["median"]
+    blk = NBlock(frames, cap=cap)
+    got, r, _ = _loop(lm, blk, pairs, mono=True)
+    assert list(r["round_off"]) == [0, 1, 2]
+    _same_outputs(got, want)
+    _same_state(blk, state)
+    blk.reset()
+    got, _, _ = _loop(lm, blk, pairs, round_off=[0, 2], mono=True)
+    _same_outputs(got, static)
+    _same_state(blk, state1)
+
+
+def test_no_rounds_and_empty_rounds(lm, neighbours):
+    frames, cap, pairs, (serial, s_serial), _ = neighbours
+    blk = NBlock(frames, cap=cap)
+    before = blk.state()
+    got, _, _ = _loop(lm, blk, [], round_off=[0])
+    assert got == [] and all(np.array_equal(a, b) for a, b in zip(before, blk.state()))
+    got, _, _ = _loop(lm, blk, [], round_off=[0, 0, 0])
+    assert got == [] and all(np.array_equal(a, b) for a, b in zip(before, blk.state()))
+    got, _, _ = _loop(lm, blk, pairs, round_off=[0, 0, 1, 1, 2, 3, 3])
+    _same_outputs(got, serial)
+    _same_state(blk, s_serial)
+    from orb_slam2_ssd_semantic_amd import OrbfeError
+    for bad in ([0, 2], [1, 3], [0, 2, 1, 3]):
+        with pytest.raises(OrbfeError):
+            _loop(lm, blk, pairs, round_off=bad)
+
+
+# ------------------------------------------------------------------------------------------------ the device-resident chain
+def test_chain_from_images_to_new_map_points(mt):
+    """ORBextractor batch -> orbfe_frame_geometry_batch_device (RGB-D) -> orbfe_bow_transform_batch_device -> create_new_map_points_device
+    on 4 synthetic frames with known poses, device pointers and one stream only.  Checked afterwards: every emitted point passes
+    the oracle's gates when re-evaluated from the downloaded keypoints (same bits), and the ids and slots are consistent."""
+    import torch
+    from orb_slam2_ssd_semantic_amd import KP_DTYPE, Camera, LocalMapper, ORBextractor, ORBVocabulary, mapping
+    from orb_slam2_ssd_semantic_amd.synth import synth_frame
+    from test_bow import make_voc
+    B, w, h, z = 4, 640, 480, 2.0
+    fx, fy, cx, cy, bf = 535.4, 539.2, 320.1, 247.6, 40.0
+    rng = np.random.default_rng(405)
+    base = synth_frame(77)
+    imgs = np.stack([np.clip(np.rint(np.roll(base, 4 * j, axis=1).astype(np.float64) + rng.normal(0, 2.0, base.shape)), 0, 255).astype(np.uint8)
+                     for j in range(B)])
+    Tcw = np.zeros((B, 3, 4), f32)
+    Tcw[:, :, :3] = np.eye(3)
+    Tcw[:, 0, 3] = [4 * j * z / fx for j in range(B)]
+    Ow = (-Tcw[:, :, 3]).astype(f32)
+    depth = np.full((B, h, w), z, f32)
+    depth[:, :, :w // 2] = 0          # the left half has no depth: monocular keypoints there
+    lm = LocalMapper(mt)
+    ext = ORBextractor(1000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=B)
+    cap = ext.capacity()
+    cam_geo = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), (), bf=bf)
+    cam = mapping.camera(fx, fy, cx, cy, bf, 0.0, float(w), 0.0, float(h))
+    mb = 0.01
+    V = ORBVocabulary(mt, **make_voc(15, 10, 3))
+    pairs = [(0, 1), (0, 2), (0, 3), (1, 2)]
+    st = torch.cuda.current_stream().cuda_stream
+    i32 = dict(dtype=torch.int32, device="cuda")
+    d_gray, d_depth = torch.from_numpy(imgs).cuda(), torch.from_numpy(depth).cuda()
+    d_kps, d_desc, d_n = torch.zeros((B, cap, 7), **i32), torch.zeros((B, cap, 32), dtype=torch.uint8, device="cuda"), torch.zeros(B, **i32)
+    bl = dict(f_word=torch.zeros((B, cap), **i32), f_node=torch.zeros((B, cap), **i32), f_weight=torch.zeros((B, cap), dtype=torch.float64, device="cuda"),
+              bow_id=torch.zeros((B, cap), **i32), bow_val=torch.zeros((B, cap), dtype=torch.float64, device="cuda"),
+              fv_node=torch.zeros((B, cap), **i32), fv_off=torch.zeros((B, cap + 1), **i32), fv_idx=torch.zeros((B, cap), **i32),
+              counts=torch.zeros((B, 4), **i32))
+    d_T, d_O = _dev(Tcw.reshape(B, 12)), _dev(Ow)
+    has = torch.zeros((B, cap), dtype=torch.uint8, device="cuda")
+    xyz = torch.zeros((B, cap, 3), dtype=torch.float32, device="cuda")
+    ids = torch.full((B, cap), -1, **i32)
+    ext.extract_batch_device(d_gray.data_ptr(), B, w, h, w, w * h, d_kps.data_ptr(), d_desc.data_ptr(), cap, d_n.data_ptr(), st)
+    d_un, d_dep, d_ur = cam_geo.frame_geometry(d_kps, d_n, cap, depth=d_depth, scale=1.0, stream=st)
+    V.transform_batch_device(d_desc.data_ptr(), d_n.data_ptr(), B, cap, 2, bl["f_word"].data_ptr(), bl["f_node"].data_ptr(),
+                             bl["f_weight"].data_ptr(), bl["bow_id"].data_ptr(), bl["bow_val"].data_ptr(), bl["fv_node"].data_ptr(),
+                             bl["fv_off"].data_ptr(), bl["fv_idx"].data_ptr(), bl["counts"].data_ptr(), st)
+    kf = mapping.keyframes_struct(d_un, d_desc, d_n, cap, B, bl["fv_node"], bl["fv_off"], bl["fv_idx"], bl["counts"], d_ur, None)
+    geom = mapping.geometry_struct(d_T, d_O, cam, mb, 1.2, d_dep, d_kps)
+    r = lm.create_new_map_points_device(kf, geom, has, xyz, ids, [p[0] for p in pairs], [p[1] for p in pairs], TC.SF, TC.S2, stream=st)
+    torch.cuda.synchronize()
+    n = d_n.cpu().numpy()
+    un, raw = (t.cpu().numpy().view(KP_DTYPE).reshape(B, cap) for t in (d_un, d_kps))
+    dep, ur = d_dep.cpu().numpy(), d_ur.cpu().numpy()
+    H = {k: v.cpu().numpy() for k, v in r.items() if hasattr(v, "cpu")}
+    has, xyz, ids = has.cpu().numpy(), xyz.cpu().numpy(), ids.cpu().numpy()
+    ocam = NO.camera(fx, fy, cx, cy, bf)
+
+    def key(b, i):
+        return NO.key(un["x"][b, i], un["y"][b, i], un["octave"][b, i], dep[b, i], ur[b, i], raw["x"][b, i], raw["y"][b, i])
+    assert list(r["round_off"]) == [0, 1, 2, 4] and list(r["order"]) == [0, 1, 2, 3]
+    total, last = 0, {}
+    for pos, i in enumerate(r["order"]):
+        i1, i2 = pairs[i]
+        nn = int(H["nnew"][pos])
+        assert not H["pair_skip"][pos] and nn <= H["npairs"][pos] <= min(n[i1], n[i2])
+        assert (H["verdict"][pos, :H["npairs"][pos]] == NO.OK).sum() == nn
+        for k in range(nn):
+            a, b = H["new_idx"][pos, k]
+            v, x = NO.triangulate_match(Tcw[i1].reshape(12), Ow[i1], Tcw[i2].reshape(12), Ow[i2], ocam, mb, key(i1, a), key(i2, b), TC.SF, TC.S2, 1.2)
+            assert v == NO.OK and np.array_equal(_bits(x), _bits(H["new_xyz"][pos, k])), (pos, k)
+            last[(i1, int(a))] = last[(i2, int(b))] = (pos * cap + k, x)
+        total += nn
+    assert total > 20
+    assert int(has.sum()) == len(last) == int((ids >= 0).sum())
+    for (b, i), (pid, x) in last.items():
+        assert has[b, i] == 1 and ids[b, i] == pid and np.array_equal(_bits(xyz[b, i]), _bits(x))
+    # a slot that a round filled is not matched again in a later round
+    for pos in range(1, 4):
+        i1, i2 = pairs[r["order"][pos]]
+        start = max(int(o) for o in r["round_off"] if o <= pos)   # the first position of this pair's round
+        earlier = {k for k, (pid, _) in last.items() if pid < start * cap}
+        assert not any((i1, int(a)) in earlier or (i2, int(b)) in earlier for a, b in H["pairs"][pos, :H["npairs"][pos]])
