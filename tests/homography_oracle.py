@@ -93,9 +93,9 @@ def have_collinear_points(pts, count):
     return False
 
 
-def get_subset(src, dst, rng, max_attempts=10000):
+def get_subset(src, dst, rng, max_attempts=10000, trace=None):
     """getSubset with modelPoints 4 and checkPartialSubsets false (H2): the four indices, or None.  src / dst: lists of
-    (x, y) Python floats holding float32 values."""
+    (x, y) Python floats holding float32 values.  trace["collinear"] counts the subsets checkSubset rejected."""
     count = len(src)
     idx = [0, 0, 0, 0]
     it = 0
@@ -110,6 +110,8 @@ def get_subset(src, dst, rng, max_attempts=10000):
             i += 1
         if i == 4 and (have_collinear_points([src[t] for t in idx], 4) or have_collinear_points([dst[t] for t in idx], 4)):
             it += 1
+            if trace is not None:
+                trace["collinear"] = trace.get("collinear", 0) + 1
             continue
         break
     return list(idx) if (i == 4 and it < max_attempts) else None
@@ -309,10 +311,13 @@ def _pairs(src, dst):
     return src, dst
 
 
-def ransac(src, dst, threshold=3.0, max_iters=2000, confidence=0.995):
+def ransac(src, dst, threshold=3.0, max_iters=2000, confidence=0.995, trace=None):
     """RANSACPointSetRegistrator::run for n >= 5: dict(ok, H [9] (zeros when not ok), mask bool [n], iters (the loop counter at
-    exit), niters (the final bound))."""
+    exit), niters (the final bound)).  A `trace` dict receives accepts (the loop counter and the new niters at each
+    acceptance), collinear (subsets checkSubset rejected) and fit_failed (4-point fits runKernel refused)."""
     src, dst = _pairs(src, dst)
+    if trace is not None:
+        trace.update(accepts=[], collinear=0, fit_failed=0)
     count = len(src)
     if threshold <= 0:
         threshold = 3.0
@@ -325,7 +330,7 @@ def ransac(src, dst, threshold=3.0, max_iters=2000, confidence=0.995):
     it = 0
     failed = False
     while it < niters:
-        idx = get_subset(sl, dl, rng)
+        idx = get_subset(sl, dl, rng, trace=trace)
         if idx is None:
             if it == 0:
                 failed = True
@@ -337,6 +342,10 @@ def ransac(src, dst, threshold=3.0, max_iters=2000, confidence=0.995):
                 best = H
                 max_good = good
                 niters = update_num_iters(confidence, float(count - good) / count, 4, niters)
+                if trace is not None:
+                    trace["accepts"].append((it, niters))
+        elif trace is not None:
+            trace["fit_failed"] += 1
         it += 1
     if failed or max_good <= 0:
         return dict(ok=False, H=np.zeros(9), mask=np.zeros(count, bool), iters=it, niters=niters)
@@ -450,8 +459,28 @@ def invert_eig_diag(A):
     return np.diag(X).copy()
 
 
-def refine(src, dst, mask, H, max_iters=10):
-    """createLMSolver(HomographyRefineCallback(inliers), 10)->run(H[0:8]): the refined 9 doubles (H22 kept)."""
+# The LM rules a test may break one at a time, to show that a case table can tell them apart (tests/test_homography_edge_cases.py).
+# Empty = OpenCV's behaviour; nothing but a test sets it.
+#   lc_stale            lc keeps its old value when the lambda == 0 inversion re-inflates lambda
+#   nu_unclamped_10     nu is not clamped at 10
+#   nu_not_halved       the inversion leaves out nu *= 0.5
+#   lambda_always_zero  R > 0.75 zeroes lambda even when lambda / 2 >= lc
+#   iters_9             9 iterations at most instead of 10
+#   mid_as_low          0.25 <= R <= 0.75 takes the R < 0.25 branch
+#   no_r_exit           the loop does not leave on ||r||inf < FLT_EPSILON
+LM_RULES = ("lc_stale", "nu_unclamped_10", "nu_not_halved", "lambda_always_zero", "iters_9", "mid_as_low", "no_r_exit")
+LM_BREAK = frozenset()
+
+
+def refine(src, dst, mask, H, max_iters=10, trace=None):
+    """createLMSolver(HomographyRefineCallback(inliers), 10)->run(H[0:8]): the refined 9 doubles (H22 kept).  A `trace` dict
+    receives lm: one dict per iteration with band ("high": R > 0.75, "low": R < 0.25, "mid"), lam ("zeroed" / "kept" on the
+    high band, else None), inverted (the lambda == 0 re-inflation ran), nu ("clamp2" / "clamp10" / "between" on the low band,
+    else None) and accepted (Sd < S); lm_exit ("iters", "d" or "r": the first test of the loop condition that failed) and
+    lm_iters."""
+    assert LM_BREAK <= set(LM_RULES)
+    if "iters_9" in LM_BREAK:
+        max_iters -= 1
     src, dst = _pairs(src, dst)
     mask = np.asarray(mask, bool)
     s, d_ = src[mask], dst[mask]
@@ -464,6 +493,7 @@ def refine(src, dst, mask, H, max_iters=10):
     Rlo, Rhi = 0.25, 0.75
     lam, lc = 1.0, 0.75
     it = 0
+    steps = []
     while True:
         Ap = A.copy()
         for i in range(8):
@@ -475,24 +505,34 @@ def refine(src, dst, mask, H, max_iters=10):
         temp_d = np.array([_serial_sum(A[i] * d) * -1 + v[i] * 2 for i in range(8)])
         dS = dot(d, temp_d)
         R = (S - Sd) / (dS if abs(dS) > DBL_EPSILON else 1)
+        step = dict(band="high" if R > Rhi else "low" if R < Rlo else "mid", lam=None, inverted=False, nu=None)
         if R > Rhi:
             lam *= 0.5
-            if lam < lc:
+            if lam < lc or "lambda_always_zero" in LM_BREAK:
                 lam = 0.0
-        elif R < Rlo:
+            step["lam"] = "zeroed" if lam == 0 else "kept"
+        elif R < Rlo or "mid_as_low" in LM_BREAK:
             t = dot(d, v)
             nu = (Sd - S) / (t if abs(t) > DBL_EPSILON else 1) + 2
+            step["nu"] = "clamp2" if nu <= 2. else "clamp10" if nu >= 10. else "between"
             nu = 2. if nu < 2. else nu
-            nu = 10. if 10. < nu else nu
+            if "nu_unclamped_10" not in LM_BREAK:
+                nu = 10. if 10. < nu else nu
             if lam == 0:
                 dg = invert_eig_diag(A)
                 maxval = DBL_EPSILON
                 for i in range(8):
                     a = abs(dg[i])
                     maxval = a if maxval < a else maxval
-                lam = lc = 1. / maxval
-                nu *= 0.5
+                lam = 1. / maxval
+                if "lc_stale" not in LM_BREAK:
+                    lc = lam
+                if "nu_not_halved" not in LM_BREAK:
+                    nu *= 0.5
+                step["inverted"] = True
             lam *= nu
+        step["accepted"] = bool(Sd < S)
+        steps.append(step)
         if Sd < S:
             S = Sd
             x = xd
@@ -500,22 +540,33 @@ def refine(src, dst, mask, H, max_iters=10):
             A = _jtj(J)
             v = _jtr(J, r)
         it += 1
-        if not (it < max_iters and norm_inf(d) >= FLT_EPSILON and norm_inf(r) >= FLT_EPSILON):
-            break
+        if not it < max_iters:
+            why = "iters"
+        elif not norm_inf(d) >= FLT_EPSILON:
+            why = "d"
+        elif not (norm_inf(r) >= FLT_EPSILON or "no_r_exit" in LM_BREAK):
+            why = "r"
+        else:
+            continue
+        break
+    if trace is not None:
+        trace.update(lm=steps, lm_exit=why, lm_iters=it)
     out = np.asarray(H, np.float64).copy()
     out[:8] = x
     return out
 
 
 def find_homography(src, dst, method=RANSAC, threshold=3.0, max_iters=2000, confidence=0.995, taps=False):
-    """(H [3, 3] float64 or None, mask uint8 [n]); with taps=True also a dict of the stage results."""
+    """(H [3, 3] float64 or None, mask uint8 [n]); with taps=True also a dict of the stage results, whose "trace" holds what
+    ransac() and refine() record (empty for a stage that did not run)."""
     src, dst = _pairs(src, dst)
     n = len(src)
     if method not in (0, RANSAC):
         raise ValueError("method must be 0 or RANSAC")
     if threshold <= 0:
         threshold = 3.0
-    t = dict(ransac_ok=False, ransac_H=np.zeros(9), iters=0, niters=0, refit_H=np.zeros(9), refit_ok=False)
+    tr = {}
+    t = dict(ransac_ok=False, ransac_H=np.zeros(9), iters=0, niters=0, refit_H=np.zeros(9), refit_ok=False, trace=tr)
     if n < 4:   # H6
         return (None, np.zeros(n, np.uint8), t) if taps else (None, np.zeros(n, np.uint8))
     if method == 0 or n == 4:
@@ -523,14 +574,14 @@ def find_homography(src, dst, method=RANSAC, threshold=3.0, max_iters=2000, conf
         H = run_kernel(src, dst)
         ok = H is not None
     else:
-        rr = ransac(src, dst, threshold, max_iters, confidence)
+        rr = ransac(src, dst, threshold, max_iters, confidence, trace=tr)
         t.update(ransac_ok=rr["ok"], ransac_H=rr["H"], iters=rr["iters"], niters=rr["niters"])
         mask, ok, H = rr["mask"], rr["ok"], rr["H"]
         if ok and n > 4:
             H, t["refit_ok"] = refit(src, dst, mask, H)
             t["refit_H"] = H.copy()
     if ok and n > 4:
-        H = refine(src, dst, mask, H)
+        H = refine(src, dst, mask, H, trace=tr)
     if not ok:
         mask = np.zeros(n, bool)
     out = (H.reshape(3, 3) if ok else None, mask.astype(np.uint8))
