@@ -857,6 +857,109 @@ int64_t orbfe_newpoints_scratch_bytes(int32_t npairs, int32_t cap, int32_t nfram
 int32_t orbfe_newpoints_plan_rounds(const int32_t *kf1, const int32_t *kf2, int32_t npairs, int32_t *round_of, int32_t *order,
                                     int32_t *round_off);
 
+/* Fuse, batched: ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1031-1182; LocalMapping::SearchInNeighbors, once per
+ * target keyframe and once more with every target's points against the current keyframe) and Fuse(pKF, Scw, vpPoints, th,
+ * vpReplacePoint) (:1198-1318; LoopClosing::SearchAndFuse) for a batch of (keyframe, list of MapPoints) pairs, device-resident
+ * (csrc/orbfe_fuse.hip; the gate is csrc/orbfe_track_geom.h's trk_gate_fuse, host and device alike).
+ *
+ * Pair p fuses the list d_list_idx[d_list_off[p] .. d_list_off[p + 1]) (indices into `map`, CSR over all pairs) into keyframe row
+ * d_pair_kf[p] of an orbfe_track_frames block (keypoint records read in place, the grid of orbfe_assign_grid_batch_device; d_uright
+ * drives the stereo branch of the reprojection gate, NULL = every keypoint is monocular; d_slot is not read).  The same keyframe
+ * may stand in many pairs.  The pose is per PAIR: d_Tcw[p][12] row-major 3x4 (Rcw | tcw) and d_Ow[p][3]; pose-level expressions
+ * stay the caller's -- Ow = GetCameraCenter(), and for the Sim3 overload Rcw = sRcw / scw, tcw = Scw.col(3) / scw, Ow = -Rcw.t() *
+ * tcw.  cam->minx .. maxy are KeyFrame::mnMinX .. mnMaxY.
+ *
+ * Per entry, in the reference's order (rules F1 .. of DESIGN.md 8p): a negative index is a NULL pointer, map->d_bad is isBad() at
+ * entry and a non-zero d_list_skip byte (may be NULL) is the dynamic reason the reference `continue`s on -- IsInKeyFrame(pKF) /
+ * spAlreadyFound.count(pMP); then p3Dc = Rcw * p3Dw + tcw, z < 0 out, invz = 1 / z, u = fx * (X * invz) + cx, KeyFrame::IsInImage
+ * (min <= u < max; a NaN from z == 0 is out), dist3D = |p3Dw - Ow| outside [0.8f * mfMinDistance, 1.2f * mfMaxDistance] out (the
+ * getters' values), PO . Pn < 0.5 * dist3D (in double) out, level = PredictScale from the UNSCALED mfMaxDistance (src/MapPoint.cc:
+ * 448-463) -- so for these calls map->d_min_dist / d_max_dist hold mfMinDistance / mfMaxDistance themselves and the gate applies
+ * the getters' factors --, GetFeaturesInArea(u, v, th * scale_factors[level]), candidates of octave level - 1 or level, in the PLAIN
+ * overload the chi2 gate of ORBFE_PROJ_CHI2_GATE, the FIRST candidate in GetFeaturesInArea order with the smallest Hamming distance
+ * (`dist < bestDist`), accepted iff bestDist <= th_low.  That result depends on the point, the pose and the keyframe's features
+ * only -- never on what another entry or an earlier Fuse call did to the map.
+ * Three things cannot be rejected without a host read and make "no match": a list index >= map->npoints, a pair whose keyframe row
+ * is outside [0, nkf), and a keypoint whose octave is outside [0, nlevels) (it is never a candidate).  Offsets beyond nentries are
+ * cut there.  Limits: cap <= 15360, nlevels <= 16, 0 <= th_low <= 255, nentries <= 2^25; anything else is ORBFE_ERR_ARG before any
+ * launch. */
+#define ORBFE_FUSE_PLAIN 0
+#define ORBFE_FUSE_SIM3 1
+/* what the reference does with an entry (d_action) */
+#define ORBFE_FUSE_NONE 0               /* no match */
+#define ORBFE_FUSE_ADD 1                /* the slot is empty and this entry is its first match: AddObservation + AddMapPoint */
+#define ORBFE_FUSE_REPLACE_SLOT 2       /* plain: the slot's point is good and does not have more observations (equal counts land
+                                         * here): pMPinKF->Replace(pMP); d_other = the slot's point */
+#define ORBFE_FUSE_REPLACE_POINT 3      /* plain: the slot's point is good and has more observations: pMP->Replace(pMPinKF) */
+#define ORBFE_FUSE_COUNTED 4            /* the slot's point is bad: only nFused++ (such a slot never changes) */
+#define ORBFE_FUSE_DEFERRED 5           /* plain: an earlier entry of this pair matched the same slot with action 1, 2 or 3; what the
+                                         * reference does now depends on what Replace / AddObservation did to the map (observation
+                                         * transfers across keyframes, +2 for a stereo keypoint), which flat arrays cannot express:
+                                         * the caller decides it in list order; d_other = the in-pair position of that first matcher */
+#define ORBFE_FUSE_REPLACE_CANDIDATE 6  /* Sim3: vpReplacePoint[i] = d_other: the slot's point at entry if it is good, else the
+                                         * point an earlier entry of this call ADDed to the slot (Replace is the caller's there, so the
+                                         * replay is complete: no DEFERRED in this overload) */
+typedef struct orbfe_fuse_lists {
+    const int32_t *d_pair_kf;        /* [npairs] row of the keyframe block */
+    const float *d_Tcw;              /* [npairs][12] */
+    const float *d_Ow;               /* [npairs][3] */
+    const uint32_t *d_list_off;      /* [npairs + 1] ascending */
+    const int32_t *d_list_idx;       /* [nentries] map index, negative = NULL */
+    const uint8_t *d_list_skip;      /* [nentries] or NULL */
+    int64_t nentries;
+    int32_t npairs;
+} orbfe_fuse_lists;
+/* flat, aligned with the CSR list; d_first may be NULL */
+typedef struct orbfe_fuse_out {
+    int32_t *d_match;                /* [nentries] bestIdx of an accepted entry, else -1 */
+    int32_t *d_dist;                 /* [nentries] bestDist, 256 = no candidate */
+    uint8_t *d_action;               /* [nentries] ORBFE_FUSE_* */
+    int32_t *d_other;                /* [nentries] map index of the other point (2, 3, 6), position of the first matcher (5), else -1 */
+    int32_t *d_nfused;               /* [npairs] the reference's return value: every accepted entry counts */
+    int32_t *d_first;                /* [npairs][cap] per slot the smallest in-pair position that matched it, -1 none */
+} orbfe_fuse_out;
+/* the gate and the search alone: d_match / d_dist [nentries].  map->d_obs_gt0 is not read.  scale_factors / inv_level_sigma2 are
+ * HOST arrays of nlevels floats (mvScaleFactors / mvInvLevelSigma2), log_scale_factor = mfLogScaleFactor.  Takes no scratch. */
+orbfe_status orbfe_fuse_search_batch_device(orbfe_matcher *m, const orbfe_track_frames *kf, int32_t nkf, const orbfe_fuse_lists *lists,
+                                            const orbfe_track_camera *cam, const orbfe_track_map *map, float th,
+                                            const float *scale_factors, const float *inv_level_sigma2, int32_t nlevels,
+                                            float log_scale_factor, int32_t th_low, int32_t mode, int32_t *d_match, int32_t *d_dist,
+                                            void *stream);
+/* search + replay.  The slot state is flat and READ ONLY: d_slot_mp [nkf][cap] = -1 (no MapPoint) or the map index of
+ * GetMapPoint(slot) (NULL: every slot is empty; an index >= map->npoints counts as empty), d_nobs [npoints] = Observations()
+ * (plain overload).  Every pair is replayed against the state AT ENTRY.  The caller owns two cases: the same point twice in one
+ * list (the second occurrence is replayed as if it were another point), and the later Fuse calls of a loop after an earlier one
+ * changed the map.  Since d_match never depends on either, a caller that replays all pairs in order on its own graph using d_match
+ * gets the reference's result; d_action saves it the work wherever the entry state decides.  Enqueued on `stream`, waits for nothing,
+ * writes no host memory. */
+orbfe_status orbfe_fuse_batch_device(orbfe_matcher *m, const orbfe_track_frames *kf, int32_t nkf, const orbfe_fuse_lists *lists,
+                                     const orbfe_track_camera *cam, const orbfe_track_map *map, const int32_t *d_nobs,
+                                     const int32_t *d_slot_mp, float th, const float *scale_factors, const float *inv_level_sigma2,
+                                     int32_t nlevels, float log_scale_factor, int32_t th_low, int32_t mode, const orbfe_fuse_out *out,
+                                     void *stream);
+/* trk_gate_fuse on the HOST for n points of one pair (no device, no handle): q[n] the query (r = th * scale_factors[level], levels
+ * [level - 1, level], ur = u - bf * invz, flags ORBFE_PROJ_CHI2_GATE for ORBFE_FUSE_PLAIN and 0 for ORBFE_FUSE_SIM3), level[n], ok[n];
+ * zeros and level -1 where ok is 0.  min_dist / max_dist are mfMinDistance / mfMaxDistance.  Bit for bit what orbfe_project_points
+ * (ORBFE_PJ_SKIP_NEG_DEPTH, open upper bounds) gives when it is handed the getters' 0.8f * min_dist / 1.2f * max_dist. */
+orbfe_status orbfe_fuse_gate_points(const float *Tcw, const float *Ow, const orbfe_track_camera *cam, float th, const float *scale_factors,
+                                    float log_scale_factor, int32_t nlevels, int32_t mode, int32_t n, const float *world_pos,
+                                    const float *normal, const float *min_dist, const float *max_dist, orbfe_proj_query *q,
+                                    int32_t *level, uint8_t *ok);
+/* vpFuseCandidates of SearchInNeighbors (src/LocalMapping.cc:705-725) from the slot state: the map indices of the occupied slots
+ * (slot < d_n[kf] clamped into [0, cap]) of the target keyframe rows d_targets[ntargets], in (target, slot) order; bad points are
+ * dropped first, then every occurrence after the first (the mnFuseCandidateForKF stamp).  Ordered: no atomic takes an output place.
+ * d_cand [cand_cap]; d_ncand[0] = entries written, d_ncand[1] = the full count.  With cur_kf >= 0 and d_cand_skip [cand_cap] != NULL,
+ * d_cand_skip[j] = candidate j already sits in a slot of keyframe row cur_kf (IsInKeyFrame): the d_list_skip of the last Fuse of
+ * SearchInNeighbors, without reading the list back.  A target row outside [0, nkf) has no points.  Limits: cap <= 15360, ntargets *
+ * cap < 2^25. */
+orbfe_status orbfe_fuse_candidates_device(orbfe_matcher *m, const int32_t *d_slot_mp, const int32_t *d_n, int32_t nkf, int32_t cap,
+                                          const int32_t *d_targets, int32_t ntargets, int32_t cur_kf, const uint8_t *d_bad,
+                                          int32_t npoints, int32_t *d_cand, uint8_t *d_cand_skip, int32_t cand_cap, int32_t *d_ncand,
+                                          void *stream);
+/* bytes of matcher scratch orbfe_fuse_candidates_device takes (the search and the replay take none); -1 outside the limits.  No
+ * device needed. */
+int64_t orbfe_fuse_scratch_bytes(int32_t npoints, int32_t ntargets, int32_t cap);
+
 /* Frame::ComputeStereoMatches (src/Frame.cc:642-846): row-band descriptor search in the right image,
  * 11 x 11 SAD refinement over 11 shifts on the two extractors' device-resident pyramids (mvImagePyramid of the LAST
  * call of `left` / `right`, frame 0), parabola fit, disparity -> depth, and the median-based outlier rejection.

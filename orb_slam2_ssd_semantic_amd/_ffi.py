@@ -12,12 +12,12 @@ from . import _build, _header
 # POINTER of its class, every other pointer c_void_p.
 BYREF = ("orbfe_params", "orbfe_camera", "orbfe_track_camera", "orbfe_track_frames", "orbfe_track_last", "orbfe_track_map",
          "orbfe_track_out", "orbfe_init_search_first", "orbfe_init_search_out", "orbfe_tri_keyframes", "orbfe_tri_out", "orbfe_newpt_geom",
-         "orbfe_newpt_out", "orbfe_newpt_state")
+         "orbfe_newpt_out", "orbfe_newpt_state", "orbfe_fuse_lists", "orbfe_fuse_out")
 with open(_build.HEADERS[-1]) as _f:
     ABI = _header.Header(_f.read(), BYREF)   # include/orbfe.h, parsed once per process: ABI.ORBFE_<NAME>, ABI.structs, ABI.prototypes
 dtype = ABI.dtype   # dtype("orbfe_sim3_model", T12=(4, 4)): the numpy record of a header struct
 (OrbfeParams, OrbfeCamera, TrackCamera, TrackFrames, TrackLast, TrackMap, TrackOut, InitSearchFirst, InitSearchOut, TriKeyframes, TriOut,
- NewptGeom, NewptOut, NewptState) = (ABI.structs[name] for name in BYREF)
+ NewptGeom, NewptOut, NewptState, FuseLists, FuseOut) = (ABI.structs[name] for name in BYREF)
 KP_DTYPE, PROJ_QUERY_DTYPE, TRACK_PROJ_DTYPE = dtype("orbfe_keypoint"), dtype("orbfe_proj_query"), dtype("orbfe_track_proj")
 NEWPT_KEY_DTYPE = dtype("orbfe_newpt_key")
 

@@ -4,6 +4,7 @@
 //   SearchByProjection(Current, Last) gating    src/ORBmatcher.cc:1590-1644   (operation order: orc_proj_queries_last_frame)
 //   Frame::isInFrustum + MapPoint::PredictScale src/Frame.cc:387-451, src/MapPoint.cc:465-480
 //   SearchByProjection(F, vpMapPoints) gating   src/ORBmatcher.cc:63-93
+//   Fuse x2 gating (orbfe_fuse.hip)             src/ORBmatcher.cc:1060-1097, :1235-1270
 // Float arithmetic in the order the reference's cv::Mat expressions evaluate to -- 3x3 * 3x1 products accumulate left to right
 // in float, norms and dot products in double -- nothing fused (the library is built with -ffp-contract=off), IEEE division.
 // Poses are row-major 3x4 (Rcw | tcw).  Restated in tests/track_oracle.py.
@@ -157,4 +158,45 @@ __host__ __device__ inline void trk_query_local_map(const TrkProj &p, float th, 
     q->ur = p.ur;
     q->flags = ORBFE_PROJ_RIGHT_GATE | (obs_gt0 ? ORBFE_PROJ_CLAIMS : 0);
     q->pad = 0;
+}
+
+// ORBmatcher::Fuse, both overloads (src/ORBmatcher.cc:1060-1097 and, identically, :1235-1270): the gating of one MapPoint that is
+// neither NULL, bad nor already in the keyframe; false = the reference `continue`s.  Ow is the caller's (GetCameraCenter, or
+// -Rcw.t() * tcw of the decomposed Scw), c.minx .. c.maxy are KeyFrame::mnMinX .. mnMaxY (ints, as floats).  The Sim3 body
+// writes `1.0 / z` in double and stores it to float: the same value as the float division here, because a double quotient
+// rounded to float equals the float quotient when the double has at least 2 * 24 + 2 significand bits (53 >= 50).  z == 0
+// gives an infinite invz and a NaN or infinite u: not in the image, so out.  The viewing-angle gate compares the double dot
+// product with 0.5 * (double)dist3D -- not trk_frustum's float view_cos < 0.5f.  chi2 != 0: the plain overload, whose
+// candidates pass the reprojection-error gate (:1112-1139); 0: the Sim3 overload, which has none.  The distance gate is the
+// getters': out iff dist3D < 0.8f * mfMinDistance || dist3D > 1.2f * mfMaxDistance, the values orbfe_project_points is handed.
+__host__ __device__ inline bool trk_gate_fuse(const float *Tcw, const float *Ow, const TrkCam &c, const float *P, const float *Pn,
+                                              float min_distance, float max_distance, float th, const float *scale_factors,
+                                              float log_scale_factor, int nlevels, int chi2, orbfe_proj_query *q, int32_t *level)
+{
+    float pc[3];
+    trk_to_camera(Tcw, P, pc);
+    if (pc[2] < 0.0f) return false;
+    const float invz = trk_div(1.0f, pc[2]);
+    const float x = pc[0] * invz, y = pc[1] * invz;
+    const float u = c.fx * x + c.cx;
+    const float v = c.fy * y + c.cy;
+    if (!(u >= c.minx && u < c.maxx && v >= c.miny && v < c.maxy)) return false;   // KeyFrame::IsInImage; NaN is out
+    const float po[3] = {P[0] - Ow[0], P[1] - Ow[1], P[2] - Ow[2]};
+    const float dist = (float)sqrt((double)po[0] * (double)po[0] + ((double)po[1] * (double)po[1]) + ((double)po[2] * (double)po[2]));
+    // min_distance / max_distance are mfMinDistance / mfMaxDistance: the getters scale them (src/MapPoint.cc:427-437),
+    // PredictScale reads the unscaled mfMaxDistance (:448-463)
+    if (dist < 0.8f * min_distance || dist > 1.2f * max_distance) return false;
+    const double dot = (double)po[0] * (double)Pn[0] + ((double)po[1] * (double)Pn[1]) + ((double)po[2] * (double)Pn[2]);
+    if (dot < 0.5 * (double)dist) return false;
+    const int lv = trk_predict_scale(max_distance, dist, log_scale_factor, nlevels);
+    q->u = u;
+    q->v = v;
+    q->r = th * scale_factors[lv];
+    q->min_level = lv - 1;
+    q->max_level = lv;
+    q->ur = u - c.bf * invz;
+    q->flags = chi2 ? ORBFE_PROJ_CHI2_GATE : 0;
+    q->pad = 0;
+    *level = lv;
+    return true;
 }
