@@ -46,6 +46,31 @@ DBL_EPSILON = 2.220446049250313e-16
 DBL_MIN = 2.2250738585072014e-308
 _ERR = dict(divide="ignore", invalid="ignore", over="ignore", under="ignore")
 
+# ---- the break switch (tests/test_pnp_edge_cases.py) --------------------------------------------------------------------------
+# One rule at a time is broken to show that a case table would notice.  Empty: the oracle proper, bit for bit.
+EPNP_RULES = {   # the EPnP arithmetic: these take a scope
+    "betas1_sign": "_betas_1 with b4[0] < 0 leaves betas 1..3 un-negated",
+    "betas23_b0": "_betas_23 with b[0] < 0 tests b[2] as the other arm does (> 0)",
+    "betas23_b2": "_betas_23 takes sqrt(|b[2]|) whatever the sign of b[2]",
+    "betas23_b1": "_betas_23 never negates beta 0 on b[1] < 0",
+    "solve_for_sign": "the camera points are never negated",
+    "det_neg": "the third row of R is never negated",
+    "choose_2": "N = 2 is never chosen",
+    "choose_3": "N = 3 is never chosen",
+}
+SCAN_RULES = {   # the acceptance scan of iterate
+    "best_tie_replaces": "a count equal to the best replaces it",
+    "refine_current_mask": "Refine runs over the current iteration's mask",
+    "refine_return_ge": "Refine returns on rcnt >= min_inliers",
+    "loop_and": "the loop runs while iterations < max_its AND cur < n_iterations",
+}
+EPNP_BREAK = frozenset()
+EPNP_BREAK_SCOPE = "all"   # "all": every compute_pose; "refine": only calls over more than four points (the cooperative path)
+
+
+def _broken(rule, n):
+    return rule in EPNP_BREAK and (EPNP_BREAK_SCOPE == "all" or n > 4)
+
 
 # ---- draws (P5) ---------------------------------------------------------------------------------------------------------------
 def index_from_draw(r, size):
@@ -266,8 +291,9 @@ def mul_transposed(A):
         return seqsum(A[:, :, :, None] * A[:, :, None, :], axis=1)   # symmetric by commutativity of the products
 
 
-def qr_solve(A, b, x):
-    """qr_solve (P6, P7) on A [B, nr, nc], b [B, nr]; x [B, nc] is overwritten where the matrix is not found singular"""
+def qr_solve(A, b, x, kept=None):
+    """qr_solve (P6, P7) on A [B, nr, nc], b [B, nr]; x [B, nc] is overwritten where the matrix is not found singular.  `kept`
+    (bool [B], in / out) is set where x was left as it was"""
     A = np.array(A, np.float64, copy=True)
     b = np.array(b, np.float64, copy=True)
     x = np.array(x, np.float64, copy=True)
@@ -300,6 +326,8 @@ def qr_solve(A, b, x):
         X[:, nc - 1] = b[:, nc - 1] / A2[:, nc - 1]
         for i in range(nc - 2, -1, -1):
             X[:, i] = (b[:, i] - seqsum(A[:, i, i + 1:] * X[:, i + 1:])) / A2[:, i]
+    if kept is not None:
+        kept |= ~alive
     return np.where(alive[:, None], X, x)
 
 
@@ -313,8 +341,11 @@ def _dist2(a, b):
     return d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
 
 
-def compute_pose(pws, us, K, detail=False):
-    """compute_pose on pws [B, n, 3], us [B, n, 2] (double), K = (fu, fv, uc, vc) -> (R [B, 3, 3], t [B, 3], err [B], N [B])"""
+def compute_pose(pws, us, K, detail=False, trace=None):
+    """compute_pose on pws [B, n, 3], us [B, n, 2] (double), K = (fu, fv, uc, vc) -> (R [B, 3, 3], t [B, 3], err [B], N [B]); with
+    detail also the three reprojection errors [B, 3].  A `trace` dict receives, per item: betas1_neg bool [B]; betas23_arm {2, 3:
+    int [B]} = 4 * (b[0] < 0) + 2 * (b[2] < 0) + (b[1] < 0); flip and det_neg {1, 2, 3: bool [B]}; qr_kept {1, 2, 3: bool [B]} (a
+    Gauss-Newton step left x as it was); N [B]; n."""
     pws = np.asarray(pws, np.float64)
     us = np.asarray(us, np.float64)
     fu, fv, uc, vc = (np.float64(v) for v in K)
@@ -362,18 +393,25 @@ def compute_pose(pws, us, K, detail=False):
             L[:, i, 8] = 2.0 * _dot3(dv[2][i], dv[3][i])
             L[:, i, 9] = _dot3(dv[3][i], dv[3][i])
         rho = np.stack([_dist2(cws[:, a], cws[:, b]) for (a, b) in pairs], 1)
-        betas = [None, _betas_1(L, rho), _betas_2(L, rho), _betas_3(L, rho)]
+        tr = dict(n=n, betas23_arm={}, flip={}, det_neg={}, qr_kept={})
+        betas = [None, _betas_1(L, rho, n, tr), _betas_2(L, rho, n, tr), _betas_3(L, rho, n, tr)]
         Rs, ts, errs = [None], [None], [None]
         for k in (1, 2, 3):
-            betas[k] = gauss_newton(L, rho, betas[k])
-            R, t = _compute_R_and_t(ut, betas[k], alphas, pws)
+            tr["qr_kept"][k] = np.zeros(B, bool)
+            betas[k] = gauss_newton(L, rho, betas[k], tr["qr_kept"][k])
+            R, t = _compute_R_and_t(ut, betas[k], alphas, pws, tr, k)
             Rs.append(R)
             ts.append(t)
             errs.append(reprojection_error(R, t, pws, us, K))
         N = np.ones(B, np.int64)
-        N = np.where(errs[2] < errs[1], 2, N)
+        if not _broken("choose_2", n):
+            N = np.where(errs[2] < errs[1], 2, N)
         eN = np.where(N == 2, errs[2], errs[1])
-        N = np.where(errs[3] < eN, 3, N)
+        if not _broken("choose_3", n):
+            N = np.where(errs[3] < eN, 3, N)
+        tr["N"] = N
+        if trace is not None:
+            trace.update(tr)
         R = np.where((N == 1)[:, None, None], Rs[1], np.where((N == 2)[:, None, None], Rs[2], Rs[3]))
         t = np.where((N == 1)[:, None], ts[1], np.where((N == 2)[:, None], ts[2], ts[3]))
         err = np.where(N == 1, errs[1], np.where(N == 2, errs[2], errs[3]))
@@ -382,22 +420,32 @@ def compute_pose(pws, us, K, detail=False):
     return R, t, err, N
 
 
-def _betas_1(L, rho):
+def _betas_1(L, rho, n=4, tr=None):
     b4 = sv_solve(L[:, :, [0, 1, 3, 6]], rho)
     neg = b4[:, 0] < 0
+    if tr is not None:
+        tr["betas1_neg"] = neg
     b0 = np.sqrt(np.where(neg, -b4[:, 0], b4[:, 0]))
     out = np.zeros_like(b4)
     out[:, 0] = b0
+    neg_rest = neg & (not _broken("betas1_sign", n))
     for k in (1, 2, 3):
-        out[:, k] = np.where(neg, -b4[:, k], b4[:, k]) / b0
+        out[:, k] = np.where(neg_rest, -b4[:, k], b4[:, k]) / b0
     return out
 
 
-def _betas_23(b, third):
+def _betas_23(b, third, n=4, tr=None):
     neg = b[:, 0] < 0
+    if tr is not None:
+        tr["betas23_arm"][3 if third else 2] = 4 * neg.astype(np.int64) + 2 * (b[:, 2] < 0) + (b[:, 1] < 0)
     b0 = np.sqrt(np.where(neg, -b[:, 0], b[:, 0]))
-    b1 = np.where(neg, np.where(b[:, 2] < 0, np.sqrt(-b[:, 2]), 0.0), np.where(b[:, 2] > 0, np.sqrt(b[:, 2]), 0.0))
-    b0 = np.where(b[:, 1] < 0, -b0, b0)
+    pos_rule = np.where(b[:, 2] > 0, np.sqrt(b[:, 2]), 0.0)
+    neg_rule = pos_rule if _broken("betas23_b0", n) else np.where(b[:, 2] < 0, np.sqrt(-b[:, 2]), 0.0)
+    b1 = np.where(neg, neg_rule, pos_rule)
+    if _broken("betas23_b2", n):
+        b1 = np.sqrt(np.abs(b[:, 2]))
+    if not _broken("betas23_b1", n):
+        b0 = np.where(b[:, 1] < 0, -b0, b0)
     out = np.zeros((len(b), 4))
     out[:, 0] = b0
     out[:, 1] = b1
@@ -406,15 +454,15 @@ def _betas_23(b, third):
     return out
 
 
-def _betas_2(L, rho):
-    return _betas_23(sv_solve(L[:, :, [0, 1, 2]], rho), False)
+def _betas_2(L, rho, n=4, tr=None):
+    return _betas_23(sv_solve(L[:, :, [0, 1, 2]], rho), False, n, tr)
 
 
-def _betas_3(L, rho):
-    return _betas_23(sv_solve(L[:, :, [0, 1, 2, 3, 4]], rho), True)
+def _betas_3(L, rho, n=4, tr=None):
+    return _betas_23(sv_solve(L[:, :, [0, 1, 2, 3, 4]], rho), True, n, tr)
 
 
-def gauss_newton(L, rho, betas):
+def gauss_newton(L, rho, betas, kept=None):
     betas = np.array(betas, np.float64, copy=True)
     B = len(betas)
     x = np.zeros((B, 4))   # P6
@@ -427,12 +475,12 @@ def gauss_newton(L, rho, betas):
         A[:, :, 3] = (L[:, :, 6] * b0 + L[:, :, 7] * b1 + L[:, :, 8] * b2 + 2 * L[:, :, 9] * b3)
         b = rho - (L[:, :, 0] * b0 * b0 + L[:, :, 1] * b0 * b1 + L[:, :, 2] * b1 * b1 + L[:, :, 3] * b0 * b2 + L[:, :, 4] * b1 * b2 +
                    L[:, :, 5] * b2 * b2 + L[:, :, 6] * b0 * b3 + L[:, :, 7] * b1 * b3 + L[:, :, 8] * b2 * b3 + L[:, :, 9] * b3 * b3)
-        x = qr_solve(A, b, x)
+        x = qr_solve(A, b, x, kept)
         betas = betas + x
     return betas
 
 
-def _compute_R_and_t(ut, betas, alphas, pws):
+def _compute_R_and_t(ut, betas, alphas, pws, tr=None, k=0):
     B, n, _ = pws.shape
     nd = np.float64(n)
     ccs = np.zeros((B, 4, 3))
@@ -441,7 +489,10 @@ def _compute_R_and_t(ut, betas, alphas, pws):
     pcs = (alphas[:, :, 0, None] * ccs[:, None, 0] + alphas[:, :, 1, None] * ccs[:, None, 1] + alphas[:, :, 2, None] * ccs[:, None, 2] +
            alphas[:, :, 3, None] * ccs[:, None, 3])
     flip = pcs[:, 0, 2] < 0.0   # solve_for_sign
-    pcs = np.where(flip[:, None, None], -pcs, pcs)
+    if tr is not None:
+        tr["flip"][k] = flip
+    if not _broken("solve_for_sign", n):
+        pcs = np.where(flip[:, None, None], -pcs, pcs)
     # estimate_R_and_t
     pc0 = seqsum(pcs, axis=1) / nd
     pw0 = seqsum(pws, axis=1) / nd
@@ -457,7 +508,10 @@ def _compute_R_and_t(ut, betas, alphas, pws):
             R[:, i, j] = _dot3(U[:, i], V[:, j])
     det = (R[:, 0, 0] * R[:, 1, 1] * R[:, 2, 2] + R[:, 0, 1] * R[:, 1, 2] * R[:, 2, 0] + R[:, 0, 2] * R[:, 1, 0] * R[:, 2, 1] -
            R[:, 0, 2] * R[:, 1, 1] * R[:, 2, 0] - R[:, 0, 1] * R[:, 1, 0] * R[:, 2, 2] - R[:, 0, 0] * R[:, 1, 2] * R[:, 2, 1])
-    R[:, 2] = np.where((det < 0)[:, None], -R[:, 2], R[:, 2])
+    if tr is not None:
+        tr["det_neg"][k] = det < 0
+    if not _broken("det_neg", n):
+        R[:, 2] = np.where((det < 0)[:, None], -R[:, 2], R[:, 2])
     t = np.stack([pc0[:, k] - _dot3(R[:, k], pw0) for k in range(3)], 1)
     return R, t
 
@@ -515,23 +569,27 @@ class PnPSolver:
         self.best_inliers = 0
         self.best_mask = np.zeros(self.N, bool)
         self.best_Tcw = np.zeros((4, 4), np.float32)
+        self.refine_log = []   # one trace of compute_pose per refine(), with m, the inliers it ran over
         self.set_ransac_parameters()
 
     def set_ransac_parameters(self, probability=0.99, min_inliers=8, max_its=300, min_set=4, epsilon=0.4, th2=5.991):
         self.min_inliers, self.epsilon, self.max_its = ransac_params(probability, min_inliers, max_its, min_set, epsilon, self.N)
         self.max_error = self.sigma2 * np.float32(th2)
 
-    def _pose(self, idx):
+    def _pose(self, idx, trace=None):
         pws = self.P3Dw[idx].astype(np.float64)[None]
         us = self.P2D[idx].astype(np.float64)[None]
-        return compute_pose(pws, us, self.K, detail=True)
+        return compute_pose(pws, us, self.K, detail=True, trace=trace)
 
-    def refine(self):
-        idx = np.nonzero(self.best_mask)[0]
-        R, t, _, _, _ = self._pose(idx)
+    def refine(self, over=None):
+        idx = np.nonzero(self.best_mask if over is None else over)[0]
+        tr = dict(m=len(idx))
+        R, t, _, _, _ = self._pose(idx, tr)
+        self.refine_log.append(tr)
         mask, _ = check_inliers(R[0], t[0], self.P3Dw, self.P2D, self.max_error, self.K)
         cnt = int(mask.sum())
-        return cnt > self.min_inliers, mask, cnt, tcw_from(R[0], t[0])
+        ok = cnt >= self.min_inliers if "refine_return_ge" in EPNP_BREAK else cnt > self.min_inliers
+        return ok, mask, cnt, tcw_from(R[0], t[0])
 
     def iterate(self, n_iterations, draws, taps=None):
         """-> dict(Tcw float32 [4, 4] or None, no_more, mask bool [N], n_inliers, iterations_run).  `draws`: four raw values per
@@ -546,8 +604,10 @@ class PnPSolver:
         quads = np.array([quad_from_draws(draws[4 * k:4 * k + 4], self.N) for k in range(total)], np.int64).reshape(total, 4)
         if total:
             R, t, _, Nc, _ = compute_pose(self.P3Dw[quads].astype(np.float64), self.P2D[quads].astype(np.float64), self.K, detail=True)
+        assert EPNP_BREAK <= set(EPNP_RULES) | set(SCAN_RULES) and EPNP_BREAK_SCOPE in ("all", "refine")
         cur = 0
-        while self.iterations < self.max_its or cur < n_iterations:
+        while ((self.iterations < self.max_its and cur < n_iterations) if "loop_and" in EPNP_BREAK else
+               (self.iterations < self.max_its or cur < n_iterations)):
             k = cur
             cur += 1
             self.iterations += 1
@@ -559,12 +619,13 @@ class PnPSolver:
             if taps is not None:
                 taps.append(rec)
             if cnt >= self.min_inliers:
-                if cnt > self.best_inliers:
+                if cnt > self.best_inliers or ("best_tie_replaces" in EPNP_BREAK and cnt == self.best_inliers):
                     self.best_mask = mask.copy()
                     self.best_inliers = cnt
                     self.best_Tcw = tcw_from(R[k], t[k])
-                ok, rmask, rcnt, rT = self.refine()
+                ok, rmask, rcnt, rT = self.refine(mask if "refine_current_mask" in EPNP_BREAK else None)
                 rec["refined"] = True
+                rec["refine"] = self.refine_log[-1]
                 rec["refine_inliers"] = rcnt
                 if ok:
                     out.update(Tcw=rT, mask=rmask, n_inliers=rcnt)

@@ -46,6 +46,18 @@ DBL_EPSILON = 2.220446049250313e-16
 FLT_EPSILON = F(np.finfo(np.float32).eps)
 ZERO = F(0)
 
+# ---- the break switch (tests/test_sim3_edge_cases.py) -------------------------------------------------------------------------
+# One rule at a time is broken to show that a case table would notice.  Empty: the oracle proper, bit for bit.
+SIM3_RULES = {
+    "tie_gt": "a count equal to the best does not replace it (> for >=)",
+    "return_ge": "a count equal to min_inliers returns (>= for >)",
+    "clamp_le": "the loop runs while iterations <= max_its",
+    "fix_scale_ignored": "the scale is 1 whatever fix_scale says",
+    "max_errors_no_trunc": "the thresholds are 9.210 * sigma2 without the integer truncation",
+    "no_identity_arm": "Rodrigues without its theta < DBL_EPSILON arm",
+}
+SIM3_BREAK = frozenset()
+
 
 # ---- canonical fp64 atan2 / sin / cos ------------------------------------------------------------------------------------------
 def _hi(x):
@@ -256,6 +268,8 @@ def camera_points(Xw, Rcw, tcw):
 def max_errors(sigma2):
     """mvnMaxError: (size_t)(9.210 * (double)sigma2), as the float it becomes in `err < maxError` (:71-72, :359)"""
     s = np.asarray(sigma2, F).reshape(-1).astype(np.float64)
+    if "max_errors_no_trunc" in SIM3_BREAK:
+        return (9.210 * s).astype(F)
     return np.floor(9.210 * s).astype(np.uint64).astype(F)
 
 
@@ -443,8 +457,8 @@ def jacobi_f32(A_in):
     return np.array(W, F), np.array(V, F).reshape(n, n)
 
 
-def rotation_from_n(N, mode="canonical"):
-    """eigen -> quaternion -> angle-axis -> cv::Rodrigues (S4-S7): R float32 3x3"""
+def rotation_from_n(N, mode="canonical", trace=None):
+    """eigen -> quaternion -> angle-axis -> cv::Rodrigues (S4-S7): R float32 3x3.  trace["identity"]: the theta < DBL_EPSILON arm"""
     atan2, sin, cos = trig(mode)
     _, V = jacobi_f32(N)
     vec = V[0, 1:4].copy()
@@ -456,7 +470,9 @@ def rotation_from_n(N, mode="canonical"):
         vec = vec * F(alpha) + ZERO
     rx, ry, rz = (float(q) for q in vec)
     theta = math.sqrt(rx * rx + ry * ry + rz * rz)
-    if theta < DBL_EPSILON:
+    if trace is not None:
+        trace["identity"] = bool(theta < DBL_EPSILON)
+    if theta < DBL_EPSILON and "no_identity_arm" not in SIM3_BREAK:
         return np.eye(3, dtype=F)
     c = cos(theta)
     s = sin(theta)
@@ -480,9 +496,13 @@ def mat3(A, B):
 
 
 def compute_sim3(P1, P2, fix_scale, mode="canonical"):
-    """ComputeSim3 (:221-340): dict of R [3, 3], s, t [3], T12 [4, 4], T21 [4, 4] (float32) and N"""
+    """ComputeSim3 (:221-340): dict of R [3, 3], s, t [3], T12 [4, 4], T21 [4, 4] (float32) and N; the trace: identity (Rodrigues
+    took its theta < DBL_EPSILON arm) and finite (every entry of T12 and T21 is)"""
     N, Pr1, Pr2, O1, O2, _ = n_matrix(P1, P2)
-    R = rotation_from_n(N, mode)
+    tr = {}
+    R = rotation_from_n(N, mode, tr)
+    if "fix_scale_ignored" in SIM3_BREAK:
+        fix_scale = True
     P3 = mat3(R, Pr2)
     if not fix_scale:
         a = [float(q) for q in Pr1.ravel()]
@@ -511,7 +531,7 @@ def compute_sim3(P1, P2, fix_scale, mode="canonical"):
         T21 = np.eye(4, dtype=F)
         T21[:3, :3] = sRinv
         T21[:3, 3] = tinv
-    return dict(R=R, s=s, t=t, T12=T12, T21=T21, N=N)
+    return dict(R=R, s=s, t=t, T12=T12, T21=T21, N=N, identity=tr["identity"], finite=bool(np.isfinite(T12).all() and np.isfinite(T21).all()))
 
 
 # ---- CheckInliers --------------------------------------------------------------------------------------------------------------
@@ -562,8 +582,9 @@ class Solver:
         if self.n < self.min_inliers or self.n < 3:
             out["no_more"] = True
             return out
+        assert SIM3_BREAK <= set(SIM3_RULES)
         cur = 0
-        while self.iterations < self.max_its and cur < n_iterations:
+        while (self.iterations <= self.max_its if "clamp_le" in SIM3_BREAK else self.iterations < self.max_its) and cur < n_iterations:
             tri = triple_from_draws(draws[3 * cur:3 * cur + 3], self.n)
             cur += 1
             self.iterations += 1
@@ -572,13 +593,13 @@ class Solver:
             with np.errstate(all="ignore"):
                 inl = (e1 < self.thr1) & (e2 < self.thr2)
             cnt = int(inl.sum())
-            out["log"].append(dict(triple=tri, count=cnt, err1=e1, err2=e2, **{k: m[k] for k in ("T12", "T21", "R", "s", "t")}))
+            out["log"].append(dict(triple=tri, count=cnt, err1=e1, err2=e2, **{k: m[k] for k in ("T12", "T21", "R", "s", "t", "identity", "finite")}))
             out["iterations_run"] = cur
-            if cnt >= self.best_inliers:
+            if cnt > self.best_inliers if "tie_gt" in SIM3_BREAK else cnt >= self.best_inliers:
                 self.best_mask = inl.astype(np.uint8)
                 self.best_inliers = cnt
                 self.best = m
-                if cnt > self.min_inliers:
+                if cnt >= self.min_inliers if "return_ge" in SIM3_BREAK else cnt > self.min_inliers:
                     out.update(found=True, n_inliers=cnt, T12=m["T12"], mask=self.best_mask.copy())
                     return out
         if self.iterations >= self.max_its:

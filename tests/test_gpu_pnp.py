@@ -13,17 +13,9 @@ import pnp_cases as PC
 import pnp_oracle as PO
 from orb_slam2_ssd_semantic_amd import PnP, PnPSolver, _ffi
 from orb_slam2_ssd_semantic_amd import pnp as PN
+from pnp_checks import run_against_replay, same_bits
 
 MAX_POINTS = 2048
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(u)[~na], b.view(u)[~nb]))
 
 
 @pytest.fixture(scope="module")
@@ -88,36 +80,6 @@ def test_kat_compute_pose(n):
 
 
 # ---- iterate -------------------------------------------------------------------------------------------------------------------
-def run_against_replay(pn, sc, prm, runs):
-    """replays the oracle's calls on the device and compares everything a call leaves behind"""
-    params = np.zeros(1, PN.PARAMS_DTYPE)
-    params["min_inliers"], params["epsilon"], params["max_its"], params["th2"] = prm[0], prm[1], prm[2], np.float32(5.991)
-    state = np.zeros(1, PN.STATE_DTYPE)
-    best_mask = np.zeros(len(sc["P3Dw"]), np.uint8)
-    results = []
-    for ci, r in enumerate(runs):
-        res, mask = pn.iterate(sc["P3Dw"], sc["P2D"], sc["sigma2"], PC.K, params, r["n_iterations"], r["draws"], state, best_mask)
-        o = r["out"]
-        assert int(res["iterations_run"]) == o["iterations_run"], ci
-        assert bool(res["found"]) == (o["Tcw"] is not None) and bool(res["no_more"]) == o["no_more"], ci
-        assert int(res["n_inliers"]) == o["n_inliers"], ci
-        assert np.array_equal(mask.astype(bool), o["mask"]), ci
-        assert same_bits(res["Tcw"], o["Tcw"] if o["Tcw"] is not None else np.zeros((4, 4), np.float32)), ci
-        assert int(state["iterations"][0]) == r["iterations"] and int(state["best_inliers"][0]) == r["best_inliers"], ci
-        assert np.array_equal(best_mask.astype(bool), r["best_mask"]), ci
-        assert same_bits(state["best_Tcw"][0], r["best_Tcw"]), ci
-        taps = pn.tap(0, PN.TAP_ITERATIONS) if o["iterations_run"] else np.zeros(0, PN.ITER_DTYPE)
-        assert len(taps) == min(len(r["taps"]), PN.TAP_ITERS), ci
-        for k, (g, t) in enumerate(zip(taps, r["taps"])):
-            assert list(g["quad"]) == list(t["quad"]) and int(g["N"]) == t["N"], (ci, k)
-            assert same_bits(g["R"], t["R"]) and same_bits(g["t"], t["t"]), (ci, k)
-            assert int(g["n_inliers"]) == t["n_inliers"] and int(g["refine_inliers"]) == t["refine_inliers"], (ci, k)
-        if o["iterations_run"]:
-            assert same_bits(pn.tap(0, PN.TAP_ERRORS), r["taps"][0]["error2"]), ci
-        results.append((res, taps))
-    return results
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(PC.ITERATE_CASES))
 def test_iterate_case(pn, name):

@@ -13,18 +13,10 @@ import sim3_cases as SC
 import sim3_oracle as SO
 from orb_slam2_ssd_semantic_amd import Sim3, Sim3Solver, _ffi
 from orb_slam2_ssd_semantic_amd import sim3 as S3
+from sim3_checks import check_case, model_equal, same_bits
 
 MAX_PAIRS = 512
 F = np.float32
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(u)[~na], b.view(u)[~nb]))
 
 
 @pytest.fixture(scope="module")
@@ -113,54 +105,6 @@ def test_kat_rotation():
 
 
 # ---- the host call ---------------------------------------------------------------------------------------------------------------
-def model_equal(m, o):
-    """a device orbfe_sim3_model record against the oracle's model dict"""
-    return (same_bits(m["T12"], o["T12"]) and same_bits(m["R"], o["R"]) and same_bits(m["t"], o["t"])
-            and same_bits(np.array([m["s"]], F), np.array([o["s"]], F)))
-
-
-def check_case(h, c, outs, errors_at=None):
-    """every iterate call of case c on handle h against the oracle's results `outs`; errors_at: the iterations (within each
-    call) whose err1 / err2 are compared, each by a replay of the call from the same state (default: first, middle, last run)"""
-    n = len(c["X1"])
-    state = np.zeros(1, S3.STATE_DTYPE)
-    best_mask = np.zeros(n, np.uint8)
-    args = (c["X1"], c["X2"], c["sigma2_1"], c["sigma2_2"], c["K1"], c["K2"], c["fix_scale"], c["min_inliers"], c["max_its"])
-    for (nit, draws), o in zip(c["calls"], outs):
-        run = o["iterations_run"]
-        its = sorted({0, run // 2, run - 1}) if errors_at is None else errors_at
-        for it in [i for i in its if 0 <= i < run][1:]:
-            st, bm = state.copy(), best_mask.copy()
-            h.set_tap_iteration(it)
-            h.iterate(*args, nit, draws, st, bm)
-            e = h.tap(0, S3.TAP_ERRORS)
-            assert same_bits(e[:, 0], o["log"][it]["err1"]) and same_bits(e[:, 1], o["log"][it]["err2"]), (c["name"], it)
-        h.set_tap_iteration(0)
-        res, mask = h.iterate(*args, nit, draws, state, best_mask)
-        assert (bool(res["found"]), bool(res["no_more"]), int(res["n_inliers"]), int(res["iterations_run"])) == \
-            (o["found"], o["no_more"], o["n_inliers"], run), c["name"]
-        assert np.array_equal(mask, o["mask"]) and np.array_equal(best_mask, o["state"]["best_mask"])
-        assert int(state["iterations"][0]) == o["state"]["iterations"] and int(state["best_inliers"][0]) == o["state"]["best_inliers"]
-        best = o["state"]["best"]
-        if best is not None:
-            assert model_equal(state["best"][0], best), c["name"]
-            assert same_bits(res["model"]["R"], best["R"]) and same_bits(res["model"]["t"], best["t"])
-        if o["found"]:
-            assert same_bits(res["model"]["T12"], o["T12"])
-        else:
-            assert not res["model"]["T12"].any()
-        if n >= max(c["min_inliers"], 3):
-            rec = h.tap(0, S3.TAP_ITERATIONS)
-            assert len(rec) == min(run, S3.TAP_ITERS)
-            for r, lg in zip(rec, o["log"]):
-                assert r["triple"].tolist() == lg["triple"] and int(r["n_inliers"]) == lg["count"]
-                assert same_bits(r["T12"], lg["T12"])
-            if run:
-                e = h.tap(0, S3.TAP_ERRORS)
-                assert same_bits(e[:, 0], o["log"][0]["err1"]) and same_bits(e[:, 1], o["log"][0]["err2"])
-    return state, best_mask
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(SC.full_table()))
 def test_host_call_case(sm, name):
