@@ -960,6 +960,108 @@ orbfe_status orbfe_fuse_candidates_device(orbfe_matcher *m, const int32_t *d_slo
  * device needed. */
 int64_t orbfe_fuse_scratch_bytes(int32_t npoints, int32_t ntargets, int32_t cap);
 
+/* SearchBySim3 and the loop's SearchByProjection, batched: the two ORBmatcher members LoopClosing::ComputeSim3 calls between
+ * Sim3Solver::iterate and SearchAndFuse -- SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1334-1558)
+ * and SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (:378-498) -- for a batch of loop candidates, device-resident
+ * (csrc/orbfe_sim3_search.hip; the per-point arithmetic is csrc/orbfe_track_geom.h's trk_sim3_pair_pose / trk_gate_sim3 /
+ * trk_gate_fuse, host and device alike).  Conventions of the Fuse calls: everything is enqueued on `stream`, no call
+ * waits for the device or writes host memory, scratch is the matcher's, keyframes are rows of an orbfe_track_frames block with the
+ * grid of orbfe_assign_grid_batch_device (d_uright and d_slot are not read), map->d_min_dist / d_max_dist hold mfMinDistance /
+ * mfMaxDistance and the gates apply the getters' 0.8f / 1.2f, scale_factors is a HOST array of nlevels floats.  Limits: cap <=
+ * 15360, nlevels <= 16, thresholds 0..255; anything else is ORBFE_ERR_ARG before any launch.
+ *
+ * The poses (:1355-1357) as row-major 3x4 blocks T12 = (sR12 | t12), T21 = (sR21 | t21): sR12 = (float)(R12[i] * (double)s12),
+ * sR21 = (float)(R12^T[i] * (1.0 / (double)s12)), t21 = (-sR21) * t12 as a float matrix product accumulated from 0 left to right.
+ * orbfe_sim3_pair_pose: one candidate on the HOST (no device, no handle).  orbfe_sim3_pair_poses_device: one thread per candidate;
+ * candidate p's record starts at d_src + p * stride (bytes) and holds the scale (one float at off_s), the rotation (9 floats at
+ * off_R, row-major) and the translation (3 floats at off_t) -- the model.s / model.R / model.t of an orbfe_sim3_result read in
+ * place, or a plain [s, R, t] array with stride 52 and offsets 0, 4, 40; off_found >= 0 names an int32 of the record (the
+ * result's `found`): where it is 0 the candidate gets zeros in both poses and d_pair_skip[p] = 1 (else 0; may be NULL), the byte
+ * the searches below take as "this pair does nothing".  stride and offsets are multiples of 4. */
+orbfe_status orbfe_sim3_pair_pose(float s12, const float *R12, const float *t12, float *T12, float *T21);
+orbfe_status orbfe_sim3_pair_poses_device(orbfe_matcher *m, const void *d_src, int64_t stride, int32_t off_s, int32_t off_R,
+                                          int32_t off_t, int32_t off_found, int32_t npairs, float *d_T12, float *d_T21,
+                                          uint8_t *d_pair_skip, void *stream);
+/* trk_gate_sim3 on the HOST for n points of one direction (no device, no handle; :1400-1431 / :1476-1503): pc = T_own * Pw with
+ * the pose (Rcw | tcw) of the keyframe that holds the points, pc' = T_to_other * pc with (sR21 | t21) or (sR12 | t12); pc'.z < 0
+ * out; invz = 1 / z, u = fx * (x * invz) + cx; KeyFrame::IsInImage (min <= u < max; NaN is out); dist3D = |pc'| (the camera-frame
+ * point, a double sum of squares) outside [0.8f * min_dist, 1.2f * max_dist] out; no viewing-angle gate; level = PredictScale from
+ * the unscaled max_dist.  q[n]: r = th * scale_factors[level], levels [level - 1, level], ur = u - bf * invz, flags 0; level[n],
+ * ok[n]; zeros and level -1 where ok is 0. */
+orbfe_status orbfe_sim3_gate_points(const float *T_own, const float *T_to_other, const orbfe_track_camera *cam, float th,
+                                    const float *scale_factors, float log_scale_factor, int32_t nlevels, int32_t n,
+                                    const float *world_pos, const float *min_dist, const float *max_dist, orbfe_proj_query *q,
+                                    int32_t *level, uint8_t *ok);
+/* SearchBySim3 for npairs candidates: pair p = (keyframe rows d_kf1[p], d_kf2[p]) of `kf` (the same keyframe may stand in many
+ * pairs, on either side), poses d_Tcw [nkf][12], slot table d_slot_mp [nkf][cap] as in orbfe_fuse_batch_device (map index or -1; an
+ * index >= map->npoints counts as empty), similarity d_T12 / d_T21 [npairs][12], d_pair_skip [npairs] or NULL.  map->d_normal and
+ * d_obs_gt0 are not read.  d_match12 [npairs][cap] is vpMatches12 in / out in INDEX form (what orbfe_search_by_bow_batch_device
+ * yields after inversion): -1 NULL, j >= 0 the point in slot j of keyframe 2, -2 a point keyframe 2 does not observe; so
+ * vbAlreadyMatched1[i] = d_match12[p][i] != -1 and vbAlreadyMatched2[j] for every 0 <= j < N2 in the row.  Both directions gate
+ * with one thread per slot, compact the live queries and search with one wave per live query: the FIRST candidate in
+ * GetFeaturesInArea order with the smallest distance among the octaves level - 1 and level, accepted iff <= th_high; an already
+ * matched feature of the other keyframe stays a candidate.  Then the agreement pass (:1542-1555): d_match12[p][i1] = idx2 where
+ * vnMatch1[i1] == idx2 and vnMatch2[idx2] == i1; d_nfound[p] = the return value.  d_match1 / d_match2 [npairs][cap] (may be NULL):
+ * vnMatch1 / vnMatch2, -1 elsewhere up to cap.  A pair with a keyframe row outside [0, nkf) or with a skip byte gets d_nfound[p] =
+ * 0 and its d_match12 row stays as it was.  Further limit: npairs * 2 * cap < 2^25. */
+orbfe_status orbfe_search_by_sim3_batch_device(orbfe_matcher *m, const orbfe_track_frames *kf, int32_t nkf, const float *d_Tcw,
+                                               const int32_t *d_slot_mp, const orbfe_track_map *map, const orbfe_track_camera *cam,
+                                               const int32_t *d_kf1, const int32_t *d_kf2, const float *d_T12, const float *d_T21,
+                                               const uint8_t *d_pair_skip, int32_t npairs, float th, int32_t th_high,
+                                               const float *scale_factors, int32_t nlevels, float log_scale_factor, int32_t *d_match12,
+                                               int32_t *d_nfound, int32_t *d_match1, int32_t *d_match2, void *stream);
+/* d_list_skip[e] = 1 where the point of list entry e (d_list_idx, CSR over the pairs by d_list_off, as orbfe_fuse_lists) stands
+ * anywhere in row d_pair_row[p] (NULL: row p) of d_rows [nrows][cap], else 0: spAlreadyFound.count(pMP) with the rows = vpMatched,
+ * IsInKeyFrame(pKF) -- Fuse's d_list_skip -- with the rows = the slot table.  Negative row values and negative list indices are
+ * members of nothing; a row outside [0, nrows) has no members.  Exact and deterministic; takes no scratch.  nentries <= 2^25. */
+orbfe_status orbfe_mark_list_members_device(orbfe_matcher *m, const int32_t *d_rows, int32_t nrows, int32_t cap,
+                                            const int32_t *d_pair_row, const uint32_t *d_list_off, const int32_t *d_list_idx,
+                                            int64_t nentries, int32_t npairs, uint8_t *d_list_skip, void *stream);
+/* SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) for npairs (keyframe, list) pairs: pair p searches keyframe row p of `kf`
+ * (one keyframe under two poses: pass its row twice) under the pose d_Tcw[p][12], d_Ow[p][3] -- the caller's pose-level
+ * expressions, as for Fuse's Sim3 overload -- with the list d_list_idx[d_list_off[p] .. d_list_off[p + 1]) of map indices (an index
+ * outside [0, map->npoints) makes no query).  d_matched [npairs][cap] is vpMatched in / out: the map index of the point, -1 NULL
+ * (any other value is a point that is in no list).  (a) a list entry whose point stands in d_matched[p] AT ENTRY is skipped
+ * (orbfe_mark_list_members_device, or the caller's d_list_skip [nentries] when not NULL); (b) the gate is Fuse's Sim3 gate
+ * (trk_gate_fuse without chi2), the queries leave compacted in list order, at most qcap per pair (qcap >= the longest list always
+ * suffices; queries past it are dropped); (c) the search is the batch core of orbfe_search_by_projection_batch_device: slots
+ * occupied at entry are never candidates, an accepted query's slot is skipped by every later one, no ratio rule, accepted iff
+ * bestDist <= th_low; ent_cap / d_status [2] as there -- when ent_cap is too small d_status[0] holds the exact need, d_matched
+ * stays as it was and d_nmatches is 0: call again; (d) d_matched[p][bestIdx] = the point, d_nmatches[p] = the return value.
+ * Further limits: npairs * qcap < 2^25, nentries <= 2^25. */
+orbfe_status orbfe_search_by_projection_sim3_batch_device(orbfe_matcher *m, const orbfe_track_frames *kf, int32_t npairs,
+                                                          const float *d_Tcw, const float *d_Ow, const orbfe_track_camera *cam,
+                                                          const orbfe_track_map *map, const uint32_t *d_list_off,
+                                                          const int32_t *d_list_idx, const uint8_t *d_list_skip, int64_t nentries,
+                                                          float th, const float *scale_factors, int32_t nlevels, float log_scale_factor,
+                                                          int32_t th_low, int32_t qcap, int64_t ent_cap, int32_t *d_matched,
+                                                          int32_t *d_nmatches, int32_t *d_status, void *stream);
+/* bytes of matcher scratch: qcap == 0 -- orbfe_search_by_sim3_batch_device for (npairs, cap); qcap >= 1 --
+ * orbfe_search_by_projection_sim3_batch_device for (npairs, cap, qcap, nentries, ent_cap), the batch core's blocks included.  -1
+ * outside the limits.  No device needed. */
+int64_t orbfe_sim3_search_scratch_bytes(int32_t npairs, int32_t cap, int32_t qcap, int64_t nentries, int64_t ent_cap);
+/* The glue of one ComputeSim3 round on one stream, between orbfe_search_by_bow_batch_device(kf_kf = 1), orbfe_sim3_iterate_device and
+ * orbfe_search_by_sim3_batch_device; pair p = (keyframe rows d_kf1[p], d_kf2[p]), every row [npairs][cap].
+ * orbfe_sim3_invert_matches_device: d_bow_match[p][i] = the keyframe-1 feature SearchByBoW assigned to keyframe-2 feature i (-1 none)
+ *   -> d_match12[p][i1] = that i (vpMatches12 in index form), -1 elsewhere up to cap; i < d_n[d_kf2[p]].
+ * orbfe_sim3_correspondences_device: Sim3Solver's constructor (src/Sim3Solver.cc:43-115) for every pair, as the CSR
+ *   orbfe_sim3_iterate_device takes: in i1 order every d_match12[p][i1] = j in [0, N2) whose two slots hold good points (d_slot_mp,
+ *   map->d_bad; keypoint octaves inside [0, nlevels)) gives X1 = Rcw1 * Xw1 + tcw1, X2 likewise (orbfe_sim3_prepare_device's
+ *   arithmetic, the poses read from d_Tcw [nkf][12]), sigma2_1 / sigma2_2 = level_sigma2[octave] (HOST array, mvLevelSigma2) and
+ *   d_idx1 = i1 (mvnIndices1); d_offsets [npairs + 1].  corr_cap entries of every output, corr_cap >= npairs * cap.  Ordered: no atomic
+ *   takes a place.  Takes 4 * npairs bytes of matcher scratch.
+ * orbfe_sim3_keep_inliers_device: d_match12[p][i1] = -1 where d_key_mask[p * cap + i1] == 0 -- iterate's vbInliers with every set's
+ *   key_offset = p * cap and n_keys = cap (src/LoopClosing.cc:410-416). */
+orbfe_status orbfe_sim3_invert_matches_device(orbfe_matcher *m, const int32_t *d_bow_match, const int32_t *d_kf2, const int32_t *d_n,
+                                              int32_t nkf, int32_t cap, int32_t npairs, int32_t *d_match12, void *stream);
+orbfe_status orbfe_sim3_correspondences_device(orbfe_matcher *m, const orbfe_track_frames *kf, int32_t nkf, const float *d_Tcw,
+                                               const int32_t *d_slot_mp, const orbfe_track_map *map, const int32_t *d_kf1,
+                                               const int32_t *d_kf2, int32_t npairs, const int32_t *d_match12, const float *level_sigma2,
+                                               int32_t nlevels, int32_t corr_cap, int32_t *d_offsets, float *d_X1, float *d_X2,
+                                               float *d_sigma2_1, float *d_sigma2_2, int32_t *d_idx1, void *stream);
+orbfe_status orbfe_sim3_keep_inliers_device(orbfe_matcher *m, const uint8_t *d_key_mask, int32_t cap, int32_t npairs, int32_t *d_match12,
+                                            void *stream);
+
 /* Frame::ComputeStereoMatches (src/Frame.cc:642-846): row-band descriptor search in the right image,
  * 11 x 11 SAD refinement over 11 shifts on the two extractors' device-resident pyramids (mvImagePyramid of the LAST
  * call of `left` / `right`, frame 0), parabola fit, disparity -> depth, and the median-based outlier rejection.

@@ -21,7 +21,9 @@ from . import tracking  # noqa: F401
 from .tracking import Tracker  # noqa: F401
 from . import mapping  # noqa: F401
 from .mapping import LocalMapper, compute_f12, plan_rounds, tri_search_scratch_bytes, triangulate_match  # noqa: F401
+from . import loopclosing  # noqa: F401
+from .loopclosing import LoopCloser  # noqa: F401
 from .cloud import ObjectDatabase, PointCloudMap, generate_point_cloud, paint_boxes, pose_matrix, statistical_outlier_removal, voxel_grid  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "FramePipeline", "Flow", "Geometry", "geometry", "Homography", "find_homography", "Camera", "Sim3", "Sim3Solver", "sim3_iterate_device", "PnP", "PnPSolver", "pnp_iterate_device", "pnp_prepare_device", "InitializerHandle", "Initializer", "initialize_device", "PointCloudMap", "ObjectDatabase", "statistical_outlier_removal", "generate_point_cloud", "voxel_grid", "paint_boxes", "pose_matrix", "FrameGrid", "ORBVocabulary", "VocabularyFile", "mapio", "feature_vector_to_csr",
-           "KP_DTYPE", "OrbfeError", "Tracker", "tracking", "LocalMapper", "mapping", "compute_f12", "tri_search_scratch_bytes", "plan_rounds", "triangulate_match"]
+           "KP_DTYPE", "OrbfeError", "Tracker", "tracking", "LocalMapper", "mapping", "compute_f12", "tri_search_scratch_bytes", "plan_rounds", "triangulate_match", "LoopCloser", "loopclosing"]

@@ -5,6 +5,7 @@
 //   Frame::isInFrustum + MapPoint::PredictScale src/Frame.cc:387-451, src/MapPoint.cc:465-480
 //   SearchByProjection(F, vpMapPoints) gating   src/ORBmatcher.cc:63-93
 //   Fuse x2 gating (orbfe_fuse.hip)             src/ORBmatcher.cc:1060-1097, :1235-1270
+//   SearchBySim3 poses + gating (orbfe_sim3_search.hip)   src/ORBmatcher.cc:1355-1357, :1400-1431, :1476-1503
 // Float arithmetic in the order the reference's cv::Mat expressions evaluate to -- 3x3 * 3x1 products accumulate left to right
 // in float, norms and dot products in double -- nothing fused (the library is built with -ffp-contract=off), IEEE division.
 // Poses are row-major 3x4 (Rcw | tcw).  Restated in tests/track_oracle.py.
@@ -196,6 +197,78 @@ __host__ __device__ inline bool trk_gate_fuse(const float *Tcw, const float *Ow,
     q->max_level = lv;
     q->ur = u - c.bf * invz;
     q->flags = chi2 ? ORBFE_PROJ_CHI2_GATE : 0;
+    q->pad = 0;
+    *level = lv;
+    return true;
+}
+
+// r = A * x + b for a row-major 3x4 (A | b) the way the reference's cv::Mat expression `A * x + b` evaluates: the product's
+// accumulator starts at 0.0f (so a product of -0 becomes +0, which trk_to_camera's first term keeps), then one float add of b
+__host__ __device__ inline void trk_affine(const float *T, const float *x, float *r)
+{
+    for (int k = 0; k < 3; ++k) {
+        float acc = 0.0f;
+        acc += T[4 * k] * x[0];
+        acc += T[4 * k + 1] * x[1];
+        acc += T[4 * k + 2] * x[2];
+        r[k] = acc + T[4 * k + 3];
+    }
+}
+
+// The two similarity poses of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1355-1357) as row-major 3x4 blocks T12 = (sR12 | t12),
+// T21 = (sR21 | t21): sR12 = s12 * R12 and sR21 = (1.0 / s12) * R12.t() are double products rounded to float element by element
+// (the scalar is a double in both: `s12 *` promotes the float, `1.0 / s12` is a double quotient), t21 = -sR21 * t12 negates sR21
+// first (exact) and accumulates the float product from 0.0f left to right.
+__host__ __device__ inline void trk_sim3_pair_pose(float s12, const float *R12, const float *t12, float *T12, float *T21)
+{
+    const double s = (double)s12, inv = 1.0 / (double)s12;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            T12[4 * r + c] = (float)((double)R12[3 * r + c] * s);
+            T21[4 * r + c] = (float)((double)R12[3 * c + r] * inv);
+        }
+        T12[4 * r + 3] = t12[r];
+    }
+    for (int r = 0; r < 3; ++r) {
+        float acc = 0.0f;
+        acc += -T21[4 * r] * t12[0];
+        acc += -T21[4 * r + 1] * t12[1];
+        acc += -T21[4 * r + 2] * t12[2];
+        T21[4 * r + 3] = acc;
+    }
+}
+
+// ORBmatcher::SearchBySim3, either direction (src/ORBmatcher.cc:1400-1431 and, identically, :1476-1503): the gating of one
+// MapPoint of a keyframe that is neither NULL, already matched nor bad; false = the reference `continue`s.  T_own is the pose of
+// the keyframe that holds the point (Rcw | tcw), T_to_other the similarity (sR21 | t21) or (sR12 | t12) into the other camera,
+// c.minx .. c.maxy are the other keyframe's mnMinX .. mnMaxY.  invz is written `1.0 / z` in double and stored to float: the
+// float quotient (see trk_gate_fuse).  z == 0 gives a NaN or infinite u: out.  dist3D is the norm of the point IN THE OTHER CAMERA
+// (cv::norm(p3Dc2): a double sum of squares, sqrt, to float) -- not |Pw - Ow| --, there is no viewing-angle gate, and the distance
+// gate is the getters': out iff dist3D < 0.8f * mfMinDistance || dist3D > 1.2f * mfMaxDistance, PredictScale from the unscaled
+// mfMaxDistance.
+__host__ __device__ inline bool trk_gate_sim3(const float *T_own, const float *T_to_other, const TrkCam &c, const float *P,
+                                              float min_distance, float max_distance, float th, const float *scale_factors,
+                                              float log_scale_factor, int nlevels, orbfe_proj_query *q, int32_t *level)
+{
+    float pc[3], po[3];
+    trk_affine(T_own, P, pc);
+    trk_affine(T_to_other, pc, po);
+    if (po[2] < 0.0f) return false;
+    const float invz = trk_div(1.0f, po[2]);
+    const float x = po[0] * invz, y = po[1] * invz;
+    const float u = c.fx * x + c.cx;
+    const float v = c.fy * y + c.cy;
+    if (!(u >= c.minx && u < c.maxx && v >= c.miny && v < c.maxy)) return false;   // KeyFrame::IsInImage; NaN is out
+    const float dist = (float)sqrt((double)po[0] * (double)po[0] + ((double)po[1] * (double)po[1]) + ((double)po[2] * (double)po[2]));
+    if (dist < 0.8f * min_distance || dist > 1.2f * max_distance) return false;
+    const int lv = trk_predict_scale(max_distance, dist, log_scale_factor, nlevels);
+    q->u = u;
+    q->v = v;
+    q->r = th * scale_factors[lv];
+    q->min_level = lv - 1;
+    q->max_level = lv;
+    q->ur = u - c.bf * invz;
+    q->flags = 0;
     q->pad = 0;
     *level = lv;
     return true;
