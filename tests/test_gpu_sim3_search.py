@@ -8,13 +8,13 @@ import pytest
 
 import proj_cases as PC
 import sim3_search_cases as SC
+import sim3_search_checks as CK
 import sim3_search_oracle as SO
-from oracle import ref_ffi as R
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-HAVE_REF = R.available()
+HAVE_REF = CK.HAVE_REF
 
 
 @pytest.fixture(scope="module")
@@ -31,32 +31,8 @@ def lc(mt):
     return LoopCloser(mt)
 
 
-def _poses(s12, R12, t12):
-    from orb_slam2_ssd_semantic_amd import loopclosing
-    T12, T21 = loopclosing.sim3_pair_pose(s12, R12, t12)
-    return T12.reshape(3, 4), T21.reshape(3, 4)
-
-
-def _oracle_sim3(k1, k2, sim, th, m_in, th_high=100):
-    T12, T21 = _poses(*sim)
-    return SO.search_by_sim3(k1, k2, T12, T21, th, m_in, th_high)
-
-
-def _pad(v, cap):
-    out = np.full(cap, -1, np.int32)
-    out[:len(v)] = v
-    return out
-
-
-def _check_sim3_single(lc, k1, k2, sim, m_in, cap=None, th=7.5, th_high=100, ref=True):
-    mo, nf, v1, v2 = lc.search_by_sim3_pairs_device([k1, k2], [(0, 1)], [sim], th, [m_in], th_high=th_high, cap=cap)[0]
-    wo, wn, w1, w2 = _oracle_sim3(k1, k2, sim, th, m_in, th_high)
-    assert np.array_equal(v1, _pad(w1, len(v1))) and np.array_equal(v2, _pad(w2, len(v2)))
-    assert np.array_equal(mo, wo) and nf == wn
-    if ref and HAVE_REF and th_high == 100:
-        ro, rv = R.search_by_sim3(k1, k2, *sim, th, m_in)
-        assert np.array_equal(mo, ro[:len(mo)]) and nf == rv
-    return mo, nf, v1, v2
+# the single-pair comparisons live in tests/sim3_search_checks.py, shared with tests/test_gpu_sim3_search_edges.py
+_poses, _oracle_sim3, _pad, _check_sim3_single, _check_proj = CK.poses, CK.oracle_sim3, CK.pad, CK.check_sim3_single, CK.check_proj
 
 
 # ------------------------------------------------------------------------------------------------ parity
@@ -73,16 +49,6 @@ def test_search_by_sim3_empty_keyframes(lc, shape):
     k1, k2, s12, R12, t12, m_in = PC.sim3_pair_case(np.random.default_rng(9150), *shape)
     _, nf, _, _ = _check_sim3_single(lc, k1, k2, (s12, R12, t12), m_in, cap=45)
     assert nf == 0 or shape == (1, 1)
-
-
-def _check_proj(lc, kf, Scw, pts, m_in, cap=None, th=10, th_low=50, list_skip="device"):
-    got, nm = lc.search_by_projection_sim3_device(kf, Scw, pts, m_in, th, th_low, cap, list_skip)
-    want, wn = SO.search_by_projection_kf_sim3(kf, Scw, pts, m_in, th, th_low)
-    assert np.array_equal(got, want) and nm == wn
-    if HAVE_REF and th_low == 50:
-        ro, rv = R.search_by_projection_kf_sim3(kf, Scw, pts, m_in, th)
-        assert np.array_equal(got, ro) and nm == rv
-    return got, nm
 
 
 @pytest.mark.parametrize("seed", range(6))

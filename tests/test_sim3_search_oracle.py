@@ -161,3 +161,11 @@ def test_limits_and_scratch():
     for bad in ((1, 15361), (1, 0), (1 << 13, 4096)):
         with pytest.raises(ValueError):
             lc.sim3_search_scratch_bytes(*bad)
+    # the qcap >= 1 form: npairs * qcap < 2^25, nentries <= 2^25, ent_cap < 2^32, each on its last good and first bad value
+    assert lc.sim3_search_scratch_bytes(1 << 12, 64, (1 << 13) - 1, 0, 0) > 0 and lc.sim3_search_scratch_bytes(1, 64, (1 << 25) - 1, 0, 0) > 0
+    assert lc.sim3_search_scratch_bytes(1, 64, 1, 1 << 25, 0) > 1 << 25
+    assert lc.sim3_search_scratch_bytes(1, 64, 1, 0, (1 << 32) - 1) > lc.sim3_search_scratch_bytes(1, 64, 1, 0, 0)
+    for bad in ((1 << 12, 64, 1 << 13, 0, 0), (1, 64, 1 << 25, 0, 0), (1, 64, 1, (1 << 25) + 1, 0), (1, 64, 1, 0, 1 << 32), (1, 64, -1, 0, 0),
+                (1, 64, 1, -1, 0), (1, 64, 1, 0, -1)):
+        with pytest.raises(ValueError):
+            lc.sim3_search_scratch_bytes(*bad)
