@@ -135,3 +135,64 @@ def planted_gate():
         ("level nlevels - 1 unclamped", z1, head, 0.0, float(F(1.2) ** 7 * F(0.99)), 1, 7),
     ]
     return [(n, np.array(P, F), np.array(Pn, F), F(mn), F(mx), ok, lv) for n, P, Pn, mn, mx, ok, lv in out]
+
+
+# ------------------------------------------------------------------------------------------------ pair lookup, scan carry
+PAIR_LOOKUP_LENGTHS = (0, 1, 0, 0, 3, 1025, 0, 5, 0)   # empty pairs between full ones; boundaries 1, 1029, 1034: no multiples of 4
+PAIR_LOOKUP_STRIDE = 1024                               # the replay's workgroup: positions 0 and 1024 are one thread's
+
+
+def pair_lookup(mode, th=3.0):
+    """Nine (keyframe, list) pairs over the two keyframes of seed_case(10) / seed_case(11) (300 and 1000 features, 400 points each),
+    rows alternating, for the bisection that finds an entry's pair in list_off: dict(rows [9], sels [9] = selections of the row's
+    400-point list, S [2] = the rows' Sim3s).  The short lists hold entries the oracle says match (plus some that do not and, in
+    the 5-entry list, one entry twice).  The 1025-entry list walks the 400 points round and round, rotated so that position 1024
+    -- the second entry of the replay's thread 0 -- holds a point that matches and therefore stood at 224 and 624 already."""
+    cases = [seed_case(10)[:2], seed_case(11)[:2]]
+    S = [scw_of(c[0], 0.9) for c in cases]
+    hit, miss = [], []
+    for (kf, mps), s in zip(cases, S):
+        tmap, idx, skip, _, _ = tables(kf, mps, mode)
+        T, Ow = pose_of(kf, mode, s)
+        m = FO.fuse_search(kf, T, Ow, tmap, idx, skip, th, mode)[0]
+        hit.append(np.flatnonzero(m >= 0))
+        miss.append(np.flatnonzero(m < 0))
+    rows = [i % 2 for i in range(len(PAIR_LOOKUP_LENGTHS))]
+    n = len(cases[1][1]["bad"])
+    sels = []
+    for row, length in zip(rows, PAIR_LOOKUP_LENGTHS):
+        h, x = hit[row], miss[row]
+        if length > PAIR_LOOKUP_STRIDE:
+            r = (int(h[len(h) // 2]) - PAIR_LOOKUP_STRIDE) % n
+            sel = (np.arange(length) + r) % n
+        else:
+            sel = {0: [], 1: [h[0]], 3: [h[1], x[0], h[2]], 5: [h[3], x[1], h[4], x[2], h[3]]}[length]
+        sels.append(np.asarray(sel, np.int64))
+    return dict(rows=rows, sels=sels, S=S, cases=cases)
+
+
+CAND_NPOINTS = 300_000
+CAND_BLOCK = 256                                         # positions per workgroup of the candidates kernels
+CAND_SCAN = 1024                                         # block counts the scan takes per chunk
+
+
+def candidates_case(ntargets, cap, seed=0):
+    """vpFuseCandidates over ntargets * cap positions, for the scan of the per-block counts where it carries from one chunk of 1024
+    blocks into the next: dict(slot [ntargets + 1][cap] (the last row is the current keyframe), n, targets, bad, cur).  ~300 000
+    points, 5 % bad; row 3 holds fewer than cap points.  Behind position 1024 * 256 every other slot repeats a point that
+    occurred before it, the others hold points that occur nowhere before."""
+    rng = np.random.default_rng(7700 + seed + ntargets * 10_000 + cap)
+    total, edge = ntargets * cap, CAND_SCAN * CAND_BLOCK
+    low = min(total, edge)
+    fresh = rng.permutation(CAND_NPOINTS)
+    flat = np.full(total, -1, np.int64)
+    flat[:low] = fresh[rng.integers(0, 200_000, low)]                 # with repeats among themselves
+    if total > low:
+        k = total - low
+        flat[low:] = np.where(np.arange(k) % 2 == 0, flat[rng.integers(0, low, k)], fresh[200_000 + rng.permutation(100_000)[:k]])
+    flat[rng.random(total) < 0.03] = -1                               # empty slots
+    slot = np.concatenate([flat.reshape(ntargets, cap), fresh[rng.integers(0, CAND_NPOINTS, cap)].reshape(1, cap)]).astype(np.int32)
+    n = np.full(ntargets + 1, cap, np.int32)
+    n[3] = cap - 37
+    bad = (rng.random(CAND_NPOINTS) < 0.05).astype(np.uint8)
+    return dict(slot=slot, n=n, targets=np.arange(ntargets, dtype=np.int32), bad=bad, cur=ntargets)

@@ -109,6 +109,38 @@ def loop_kw(mono=False, trig="canonical"):
     return dict(cam=CAM, mb=MB, mono=mono, search=search, sf=SF, s2=S2, scale_factor=SCALE_FACTOR, trig=trig)
 
 
+# ------------------------------------------------------------------------------------------------ more new points than a claim block
+WIDE_SEED, WIDE_CAP, WIDE_PAIRS = 341, 904, ((0, 1), (0, 2))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_loop():
+    """keyframe 0 against two neighbours, 900 features each in ~280 nodes, cap = 904 (no multiple of the claim kernels' 256): the
+    first pair creates more than 256 points, so k_np_claim runs several blocks per pair, with feature indices up to 899; both
+    pairs in ONE round claim some keyframe-0 slots twice, from different blocks.  The oracle's serial loop (= the planned rounds,
+    one pair each) and its one-round loop, computed once: dict(frames, cap, pairs, serial, s_serial, static, s_static)."""
+    frames, cap, pairs = scene(WIDE_SEED, 3, 900, nnodes=300), WIDE_CAP, list(WIDE_PAIRS)
+    s_serial, s_static = NO.new_state(frames, cap), NO.new_state(frames, cap)
+    serial = NO.serial_loop(frames, pairs, s_serial, cap, **loop_kw())
+    static = NO.round_loop(frames, pairs, [0, len(pairs)], s_static, cap, **loop_kw())
+    return dict(frames=frames, cap=cap, pairs=pairs, serial=serial, s_serial=s_serial, static=static, s_static=s_static)
+
+
+def median_edge_frames(cap=300):
+    """frames for the scene median depth at the workgroup's 256 slots and at the ends of the rank: (Tcw [B][12], has_mp [B][cap],
+    mp_xyz [B][cap][3], n [B], names): 255, 256 and 257 occupied slots, and a frame whose 100 depths are all equal"""
+    rng = np.random.default_rng(97)
+    occ, names = [255, 256, 257, 100], ["255", "256", "257", "all_equal"]
+    B = len(occ)
+    T = np.stack([_frame_pose(rng, rng.normal(0, 1, 3), 20.0)[0] for _ in range(B)])
+    xyz = rng.normal(0, 6, (B, cap, 3)).astype(f32)
+    xyz[3] = xyz[3, 0]
+    has = np.zeros((B, cap), np.uint8)
+    for b, k in enumerate(occ):
+        has[b, rng.permutation(cap)[:k]] = 1
+    return T, has, xyz, np.full(B, cap, np.int32), names
+
+
 # ------------------------------------------------------------------------------------------------ planted
 P_CAM = NO.camera(1.0, 1.0, 0.0, 0.0, 0.08)
 P_MB = f32(0.08)

@@ -286,27 +286,27 @@ def _apply(out, pos, i1, i2, state, cap, id_base=0):
                 ids[f, i], has[f, i], xyz[f, i] = pid, 1, x
 
 
-def serial_loop(frames, pairs, state, cap, pos=None, **kw):
+def serial_loop(frames, pairs, state, cap, pos=None, id_base=0, **kw):
     """the reference's loop: search -> triangulate -> fill slots, neighbour by neighbour in the given order.  pos[i] = the position
-    that numbers pair i's points (default i).  -> [one_pair dict]; `state` is updated in place."""
+    that numbers pair i's points (default i); id_base is added to every id.  -> [one_pair dict]; `state` is updated in place."""
     outs = []
     for i, (i1, i2) in enumerate(pairs):
         o = one_pair(frames, i1, i2, state[0], state[1], **kw)
         # AddMapPoint overwrites: the later point stays.  Later = larger position here, which is the creation order whenever
         # pos ascends along the loop for the pairs that share a keyframe (plan_rounds keeps their order)
-        _apply(o, i if pos is None else int(pos[i]), i1, i2, state, cap)
+        _apply(o, i if pos is None else int(pos[i]), i1, i2, state, cap, id_base)
         outs.append(o)
     return outs
 
 
-def round_loop(frames, pairs, round_off, state, cap, **kw):
+def round_loop(frames, pairs, round_off, state, cap, id_base=0, **kw):
     """the device's loop: every pair of a round reads the state at the start of the round; then the round's claims, the maximum id
-    per slot.  `pairs` in round order."""
+    per slot.  `pairs` in round order; id_base is added to every id."""
     outs = []
     for r in range(len(round_off) - 1):
         frozen = (state[0].copy(), state[1].copy())
         rs = [(p, one_pair(frames, pairs[p][0], pairs[p][1], frozen[0], frozen[1], **kw)) for p in range(round_off[r], round_off[r + 1])]
         for p, o in rs:
-            _apply(o, p, pairs[p][0], pairs[p][1], state, cap)
+            _apply(o, p, pairs[p][0], pairs[p][1], state, cap, id_base)
             outs.append(o)
     return outs

@@ -160,3 +160,60 @@ def test_candidates_oracle_on_planted_lists():
     cand, skip = FO.candidates(slot, n, [1, 0], bad)
     assert cand.tolist() == [5, 2, 3, 9] and not skip.any()
     assert len(FO.candidates(slot, n, [], bad)[0]) == 0
+
+
+@pytest.mark.parametrize("mode", [FO.PLAIN, FO.SIM3])
+def test_pair_lookup_lists_reach_their_edges(mode):
+    """empty pairs between full ones, no boundary on a multiple of 4 (the waves of a search workgroup), and a match at position
+    1024 of the long list whose slot an entry below 1024 matched first: the collision across the replay's stride"""
+    L = FC.pair_lookup(mode)
+    lengths = [len(s) for s in L["sels"]]
+    assert tuple(lengths) == FC.PAIR_LOOKUP_LENGTHS and L["rows"] == [0, 1] * 4 + [0]
+    off = np.concatenate([[0], np.cumsum(lengths)])
+    assert 0 in lengths[1:-1] and lengths[0] == lengths[-1] == 0          # empty pairs first, last and between full ones
+    assert sum(1 for o in set(off.tolist()) if o % 4) >= 3              # boundaries inside a search workgroup's four entries
+    fused = 0
+    for row, sel in zip(L["rows"], L["sels"]):
+        kf, mps = L["cases"][row]
+        tmap, idx, skip, slot, nobs = FC.tables(kf, mps, mode)
+        T, Ow = FC.pose_of(kf, mode, L["S"][row])
+        r = FO.fuse_pair(kf, T, Ow, tmap, idx[sel], skip[sel], slot, nobs, 3.0, mode)
+        fused += r["nfused"] > 0
+        if len(sel) == 0:
+            assert r["nfused"] == 0 and (r["first"] == -1).all()
+        if len(sel) > FC.PAIR_LOOKUP_STRIDE:
+            s, m = FC.PAIR_LOOKUP_STRIDE, r["match"]
+            assert len(sel) == s + 1 and m[s] >= 0 and 0 <= r["first"][m[s]] < s and sel[r["first"][m[s]]] == sel[s]
+            assert r["action"][s] == (FO.DEFERRED if mode == FO.PLAIN else FO.REPLACE_CANDIDATE)
+            if mode == FO.PLAIN:
+                assert r["other"][s] == r["first"][m[s]]
+            assert (m[:s] >= 0).sum() > 100
+    assert fused >= 3
+
+
+@pytest.mark.parametrize("ntargets, cap", [(64, 4096), (64, 4100), (65, 4096)])
+def test_candidates_cases_cross_the_scan_chunk(ntargets, cap):
+    """1024, 1025 and 1040 blocks of 256 positions: candidates on both sides of block 1024, repeats of earlier points behind it
+    (dropped) and points that first occur behind it (kept), a short row, bad points, points of the current keyframe"""
+    c = FC.candidates_case(ntargets, cap)
+    slot, n, bad = c["slot"], c["n"], c["bad"]
+    total, edge = ntargets * cap, FC.CAND_SCAN * FC.CAND_BLOCK
+    assert (total + FC.CAND_BLOCK - 1) // FC.CAND_BLOCK == {(64, 4096): 1024, (64, 4100): 1025, (65, 4096): 1040}[(ntargets, cap)]
+    assert slot.shape == (ntargets + 1, cap) and len(bad) == FC.CAND_NPOINTS and (n[:ntargets] < cap).sum() == 1
+    assert 0.04 < bad.mean() < 0.06
+    wc, ws = FO.candidates(slot, n, list(c["targets"]), bad, c["cur"])
+    assert len(wc) > 100_000 and len(set(wc.tolist())) == len(wc) and 0 < ws.sum() < len(wc)
+    flat = slot[:ntargets].reshape(-1)
+    first = {}
+    for j in np.flatnonzero(flat >= 0)[::-1]:
+        if j % cap < n[j // cap]:
+            first[int(flat[j])] = int(j)
+    pos = np.array([first[int(p)] for p in wc])
+    assert (np.diff(pos) > 0).all()                       # the candidates stand in position order
+    if total > edge:
+        late = flat[edge:]
+        late = late[late >= 0]
+        assert (pos >= edge).sum() > 50 and (pos < edge).sum() > 100_000
+        assert sum(first[int(p)] < edge for p in late if not bad[p]) > 50   # repeats behind the edge of points in front of it
+    else:
+        assert pos.max() < edge

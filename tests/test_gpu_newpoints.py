@@ -228,12 +228,12 @@ def test_scene_median_depth_largest_block(lm0):
 
 
 # ------------------------------------------------------------------------------------------------ D: the neighbour loop
-def _loop(lm, blk, pairs, round_off=None, mono=False):
+def _loop(lm, blk, pairs, round_off=None, mono=False, id_base=0):
     """-> (per pair in the CALLER's order: dict like the oracle's one_pair, state arrays, raw bytes)"""
     import torch
     has, xyz, ids = blk.t["mp"], blk.t["xyz"], blk.t["id"]
     r = lm.create_new_map_points_device(blk.kf, blk.geom, has, xyz, ids, [p[0] for p in pairs], [p[1] for p in pairs], NC.SF, NC.S2,
-                                        mono=mono, round_off=round_off)
+                                        mono=mono, round_off=round_off, id_base=id_base)
     torch.cuda.synchronize()
     h = {k: v.cpu().numpy() for k, v in r.items() if hasattr(v, "cpu")}
     outs = [None] * len(pairs)

@@ -209,3 +209,54 @@ def test_state_matters():
     static = NO.round_loop(frames, pairs, [0, 3], NO.new_state(frames, cap), cap, **kw)
     assert not _loop_outputs_equal(serial, static)
     assert len(serial[1]["pairs"]) < len(static[1]["pairs"])
+
+
+def test_wide_loop_fills_more_than_one_claim_block():
+    """the wide case: more than 256 new points in a pair, feature indices in the last quarter of the block, more FeatureVector
+    nodes than two laps of the search's workgroups in every frame, a cap that is no multiple of 256, and -- in the one-round form --
+    keyframe-0 slots that both pairs claim, from different 256-blocks of their new points"""
+    from orb_slam2_ssd_semantic_amd import mapping
+    W = mapping.tri_search_info()["node_workgroups"]
+    w = NC.wide_loop()
+    serial, static, cap = w["serial"], w["static"], w["cap"]
+    assert cap % 256 != 0 and cap > 768 and w["pairs"] == [(0, 1), (0, 2)]
+    assert list(NO.plan_rounds([0, 0], [1, 2])[2]) == [0, 1, 2]        # the planned rounds are the serial loop
+    assert len(serial[0]["new_idx"]) > 256 and len(static[0]["new_idx"]) > 256 and len(static[1]["new_idx"]) > 256
+    assert max(int(o["new_idx"].max()) for o in serial) >= 768
+    assert all(len(f["fv"][0]) > 2 * W for f in w["frames"])
+    assert not _loop_outputs_equal(serial, static)
+    k0, k1 = ({int(i): k for k, i in enumerate(o["new_idx"][:, 0])} for o in static)
+    shared = set(k0) & set(k1)
+    assert shared and {(k0[s] // 256, k1[s] // 256) for s in shared} >= {(1, 0), (0, 0)}
+    ids = w["s_static"][2]
+    assert all(ids[0, s] == cap + k1[s] for s in shared)               # the later pair's point stays
+    assert not shared & {int(i) for i in serial[1]["new_idx"][:, 0]}   # carried state: the second pair never sees a filled slot
+
+
+def test_id_base_shifts_every_id():
+    frames, cap = _small_scene(300, 4), 48
+    pairs = [(0, 1), (0, 2), (0, 3)]
+    s0, s1, s2 = (NO.new_state(frames, cap) for _ in range(3))
+    a = NO.serial_loop(frames, pairs, s0, cap, **NC.loop_kw())
+    b = NO.serial_loop(frames, pairs, s1, cap, id_base=1000, **NC.loop_kw())
+    c = NO.round_loop(frames, pairs, [0, 3], s2, cap, id_base=1000, **NC.loop_kw())
+    assert _loop_outputs_equal(a, b) and np.array_equal(s0[0], s1[0]) and np.array_equal(s0[1], s1[1])
+    assert np.array_equal(np.where(s0[2] >= 0, s0[2] + 1000, -1), s1[2]) and (s0[2] >= 0).sum() > 10
+    assert (s2[2][s2[2] >= 0] >= 1000).all()
+    # two calls on carried state = one call: the second call's ids go on where the first one's end
+    t = NO.new_state(frames, cap)
+    NO.serial_loop(frames, pairs[:1], t, cap, **NC.loop_kw())
+    NO.serial_loop(frames, pairs[1:], t, cap, id_base=cap, **NC.loop_kw())
+    assert all(np.array_equal(x, y) for x, y in zip(t, s0))
+
+
+def test_median_edge_frames():
+    T, has, xyz, n, names = NC.median_edge_frames()
+    assert has.sum(1).tolist() == [255, 256, 257, 100] and names[3] == "all_equal"
+    for b in range(4):
+        z = sorted(float(NO.np_cam_coord(T[b], 2, xyz[b, i])) for i in range(n[b]) if has[b, i])
+        assert (len(set(z)) == 1) == (b == 3)
+        assert NO.scene_median_depth(T[b], has[b], xyz[b], n[b], 1) == np.float32(z[-1])
+        assert NO.scene_median_depth(T[b], has[b], xyz[b], n[b], 1000) == np.float32(z[0])
+        assert NO.scene_median_depth(T[b], has[b], xyz[b], n[b], 2) == np.float32(z[(len(z) - 1) // 2])
+        assert b == 3 or z[0] < z[(len(z) - 1) // 2] < z[-1]

@@ -102,6 +102,64 @@ def test_list_lengths_table(oracle):
     _ref_agrees(cases["n2_65"], only_stereo=True)
 
 
+def _tri_info():
+    from orb_slam2_ssd_semantic_amd import mapping
+    return mapping.tri_search_info()   # host only: the kernel's own constants
+
+
+def test_many_nodes_gives_every_workgroup_a_second_node(oracle):
+    """more keyframe-1 nodes than two laps of the search's workgroups; heavy nodes (several tiles, several passes) in the first lap
+    and behind it; workgroups that go from a multi-tile node to a single-tile one and back; a node absent from keyframe 2 and a
+    node without queries between two nodes that match; standing matches in every lap"""
+    info = _tri_info()
+    W, T, Q = info["node_workgroups"], info["tile"], info["queries_per_pass"]
+    c, plant = TC.many_nodes(info)
+    assert len(c["k1"]["desc"]) == len(c["k2"]["desc"]) == 1500
+    w = TC.node_walk(c)
+    nfv1 = len(w["n1"])
+    assert nfv1 > 2 * W and nfv1 == len(c["k1"]["fv"][0])
+    live = (w["n2"] > 0) & (w["n1"] > 0)
+    heavy = np.nonzero((w["n2"] > 2 * T) & (w["n1"] > Q) & (w["elig"] > Q))[0]
+    assert (heavy < W).any() and (heavy >= W).any(), heavy
+    assert (w["matches"][heavy] > 0).all()
+    one_tile_two_passes = np.nonzero(live & (w["n2"] <= T) & (w["elig"] > Q))[0]
+    assert len(one_tile_two_passes) >= 1 and (one_tile_two_passes + W < nfv1).any()   # ... and the same workgroup goes on
+    seqs = TC.workgroup_sequences(nfv1, W)
+    assert len(seqs) == W and min(len(s) for s in seqs) >= 2 and sorted(a for s in seqs for a in s) == list(range(nfv1))
+    multi = live & (w["n2"] > T)
+    single = live & (w["n2"] <= T)
+    steps = [(a, b) for s in seqs for a, b in zip(s, s[1:])]
+    assert any(multi[a] and single[b] and w["matches"][b] > 0 for a, b in steps)
+    assert any(single[a] and multi[b] and w["matches"][a] > 0 and w["matches"][b] > 0 for a, b in steps)
+    for name, gap in (("absent", lambda a: w["n2"][a] == 0 and w["n1"][a] > 0), ("taken", lambda a: live[a] and w["elig"][a] == 0)):
+        s = seqs[plant[name]]
+        assert len(s) == 3 and w["matches"][s[0]] > 0 and gap(s[1]) and w["matches"][s[2]] > 0, (name, s)
+    for lap in range(3):
+        assert w["matches"][lap * W:(lap + 1) * W].sum() >= 30, lap
+    # every mode the GPU test runs still reaches every lap
+    for only, ori in ((False, False), (True, True), (True, False)):
+        ww = TC.node_walk(c, only, ori)
+        assert all(ww["matches"][lap * W:(lap + 1) * W].sum() > 0 for lap in range(3)), (only, ori)
+        _ref_agrees(c, only, ori)
+    _ref_agrees(c)
+
+
+def test_nodes_at_the_workgroup_count(oracle):
+    """W, W + 1, 2 W and 2 W + 1 nodes of one feature: the way round where keyframe 1 has them has exactly that many nodes, its
+    LAST node keeps a match (at W + 1 and 2 W + 1 the only node of its lap), and so does every lap before it"""
+    W = _tri_info()["node_workgroups"]
+    for n in (W, W + 1, 2 * W, 2 * W + 1):
+        fwd, back = TC.nodes_at(n)
+        assert len(back["k1"]["fv"][0]) == n == back["k1"]["fv"][1][-1] == len(fwd["k2"]["fv"][0])
+        assert (np.diff(back["k1"]["fv"][1].astype(np.int64)) == 1).all()
+        w = TC.node_walk(back)
+        assert w["matches"][n - 1] > 0, n
+        assert all(w["matches"][lap * W:(lap + 1) * W].sum() > 0 for lap in range((n + W - 1) // W)), n
+        assert TC.expected(fwd)[1] > 5 and TC.expected(back, only_stereo=True, check_ori=False)[1] > 0, n
+        _ref_agrees(fwd)
+        _ref_agrees(back)
+
+
 def test_histogram_cases_have_their_shape(oracle):
     for name, (plan, keep) in TC.HISTOGRAMS.items():
         c = TC.histogram_case(name)

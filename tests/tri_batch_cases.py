@@ -1,7 +1,8 @@
 """Cases for the batched, device-resident SearchForTriangulation (csrc/orbfe_tri_search.hip): planted edges of the per-candidate
 test, FeatureVector shapes at the ends of the node lookup, node-list lengths at the kernel's lane-group and tile sizes,
-rotation-histogram shapes, and batches.  numpy + the CPU oracle only; tests/test_tri_batch_cases.py checks that every case reaches
-its edge, tests/test_gpu_tri_search.py feeds them to the HIP kernels.  Test support only.
+rotation-histogram shapes, batches, and keyframes with more nodes than the search has workgroups.  numpy + the CPU oracle only;
+tests/test_tri_batch_cases.py checks that every case reaches its edge, tests/test_gpu_tri_search.py and
+tests/test_gpu_tri_search_edges.py feed them to the HIP kernels.  Test support only.
 
 A keyframe is dict(desc [n][32], xy [n][2], octave, angle, uRight (stereo: >= 0), has_mp, fv=(node, off, idx)), optionally `dead`
 [n]: features the device must ignore without an error (octave outside the levels, index >= the keyframe's count).  A pair case is
@@ -210,6 +211,83 @@ def list_lengths(info):
         out["n1_%d_short" % n1] = one_node(800 + n1, n1, T - 3)   # ... and over a list that is staged once
     out["both_600"] = one_node(600, 600, 600)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ more nodes than workgroups
+def node_walk(c, only_stereo=False, check_ori=True):
+    """what k_tri_search meets at every keyframe-1 node, by position in keyframe 1's node list: dict(n1 = the node's keyframe-1
+    entries, n2 = the entries of the same node in keyframe 2 (0 = the node is absent there), elig = the keyframe-1 entries that are
+    queries, matches = the standing matches (after the rotation check) whose keyframe-1 feature sits in the node)"""
+    k1, k2 = c["k1"], c["k2"]
+    node1, off1, idx1 = k1["fv"]
+    len2 = {int(v): int(k2["fv"][1][a + 1]) - int(k2["fv"][1][a]) for a, v in enumerate(k2["fv"][0])}
+    el = core_side(k1, only_stereo)["elig"]
+    stands = expected(c, 50, only_stereo, check_ori)[0] >= 0
+    n = len(node1)
+    out = dict(n1=np.zeros(n, np.int64), n2=np.zeros(n, np.int64), elig=np.zeros(n, np.int64), matches=np.zeros(n, np.int64))
+    for a in range(n):
+        f = idx1[off1[a]:off1[a + 1]]
+        out["n1"][a], out["n2"][a] = len(f), len2.get(int(node1[a]), 0)
+        out["elig"][a], out["matches"][a] = el[f].sum(), stands[f].sum()
+    return out
+
+
+def workgroup_sequences(nfv1, W):
+    """the keyframe-1 node positions each of k_tri_search's min(cap, W) workgroups of a pair takes, in its order (cap >= W)"""
+    return [list(range(y, nfv1, W)) for y in range(min(W, nfv1))]
+
+
+MANY_NODES_MERGES = ((0, 44), (44, 60), (324, 368))   # node ids [lo, hi) that become node lo
+
+
+def many_nodes(info):
+    """One pair of 1500 x 1500 features in ~290 nodes, for a kernel whose workgroups take the keyframe-1 nodes round robin, W =
+    info["node_workgroups"] (128) at a time, so that every workgroup walks two or three nodes: scene 901 has ~390 nodes of ~4
+    features; the ids below 44 become one heavy node at position 0 (150 x 140: three tiles, four passes), 44 .. 59 a node of one
+    tile and two passes at position 1, 324 .. 367 a second heavy node at position 2 W, so that workgroup 0 goes heavy, ordinary,
+    heavy.  Two gaps are planted in the first workgroups that have three nodes whose first and third match: the middle node of
+    one loses its keyframe-2 side (its keyframe-2 features leave the FeatureVector), every keyframe-1 feature of the other's
+    middle node gets a MapPoint.  Chosen on the CPU;
+    tests/test_tri_batch_cases.py asserts every property from `info`, so a kernel with other sizes fails there, not silently.
+    -> (pair case, dict(absent = the workgroup with the absent middle node, taken = the one with the ineligible middle node))"""
+    W = info["node_workgroups"]
+    c, _ = scene(901, 1500, 1500, 400)
+
+    def merged(v):
+        v = v.copy()
+        for lo, hi in MANY_NODES_MERGES:
+            v[(v >= lo) & (v < hi)] = lo
+        return v
+    n1, n2 = merged(nodes_of(c["k1"])), merged(nodes_of(c["k2"]))
+    c = dict(c, k1=with_nodes(c["k1"], n1), k2=with_nodes(c["k2"], n2))
+    walk = node_walk(c)
+    node1 = c["k1"]["fv"][0]
+    # the workgroups whose three nodes are ordinary (one tile, one pass) and match at both ends and in the middle
+    full = [y for y in range(max(len(node1) - 2 * W, 0))
+            if all(walk["matches"][y + k * W] > 0 and walk["n2"][y + k * W] < info["tile"] for k in range(3))]
+    assert len(full) >= 2, "scene 901 no longer has two workgroups with three matching nodes"
+    absent, taken = full[0], full[1]
+    n2 = np.where(n2 == int(node1[absent + W]), -1, n2)
+    mp = c["k1"]["has_mp"].copy()
+    mp[n1 == int(node1[taken + W])] = 1
+    return dict(c, k1=dict(c["k1"], has_mp=mp), k2=with_nodes(c["k2"], n2)), dict(absent=absent, taken=taken)
+
+
+NODES_AT_SEED = {128: 690, 129: 695, 256: 817, 257: 818}   # the first seeds from 560 + n whose LAST node of `back` keeps a match
+
+
+def nodes_at(n, seed=None):
+    """n nodes of ONE feature each on one keyframe, every feature of the other keyframe in its partner's node (or in none), as
+    test_counts_above_cap_are_clamped builds them -> (fwd, back): fwd has the n-node keyframe as keyframe 2; back is the pair the
+    other way round (F21 = F12', its epipole far away), where keyframe 1 has exactly n nodes: with W workgroups, n = W + 1 is the
+    case where exactly one of them takes a second node, and that node is the last: its match is the one a workgroup that stops
+    after its first node loses."""
+    one = one_node(NODES_AT_SEED.get(n, 560 + n) if seed is None else seed, n, n)
+    m = core_match(one)
+    full = with_nodes(one["k2"], np.arange(n))                                    # n nodes of one feature each
+    part = with_nodes(one["k1"], [m[i] if m[i] >= 0 else -1 for i in range(n)])   # every feature in its partner's node
+    Ft = np.ascontiguousarray(one["F12"].reshape(3, 3).T).reshape(9)
+    return dict(one, k1=part, k2=full), dict(one, k1=full, k2=part, F12=Ft, ex=F(-1e6), ey=F(-1e6), pose=None)
 
 
 # ------------------------------------------------------------------------------------------------ rotation histogram
