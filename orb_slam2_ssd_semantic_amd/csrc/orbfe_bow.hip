@@ -40,10 +40,7 @@ __global__ __launch_bounds__(64) void k_search_by_bow(const uint8_t *__restrict_
     for (uint32_t ik = offKF[a]; ik < offKF[a + 1]; ++ik) {
         const uint32_t rk = idxKF[ik];
         if (validKF && !validKF[rk]) continue;
-        Desc8 dk;
-        const uint32_t *pk = (const uint32_t *)(descKF + (int64_t)rk * 32);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dk.w[i] = pk[i];
+        const Desc8 dk = load_desc8(descKF + (int64_t)rk * 32);
         int b1 = 256, b2 = 256, bi = -1;
         for (uint32_t jf = offF[b]; jf < offF[b + 1]; ++jf) {
             const uint32_t rf = idxF[jf];
@@ -63,55 +60,7 @@ __global__ __launch_bounds__(256) void k_rot_prune_bow(int32_t *__restrict__ mat
                                                        const float *__restrict__ angF, int nF, int check_ori,
                                                        int32_t *__restrict__ nmatches)
 {
-    __shared__ int s_hist[ORBFE_HISTO_LENGTH];
-    __shared__ int s_keep[3];
-    __shared__ int s_count;
-    const int tid = threadIdx.x;
-    if (tid < ORBFE_HISTO_LENGTH) s_hist[tid] = 0;
-    if (tid == 0) s_count = 0;
-    __syncthreads();
-    if (check_ori) {
-        for (int i = tid; i < nF; i += 256) {
-            const int j = match[i];
-            if (j >= 0) atomicAdd(&s_hist[rot_bin(angKF[j], angF[i])], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; ++i) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s; i3 = i;
-                }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
-            s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
-        }
-        __syncthreads();
-    }
-    int local = 0;
-    for (int i = tid; i < nF; i += 256) {
-        const int j = match[i];
-        if (j < 0) continue;
-        if (check_ori) {
-            const int bin = rot_bin(angKF[j], angF[i]);
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
-                match[i] = -1;
-                continue;
-            }
-        }
-        ++local;
-    }
-    atomicAdd(&s_count, local);
-    __syncthreads();
-    if (tid == 0) nmatches[0] = s_count;
+    rot_prune(match, nF, check_ori, nmatches, [&](int, int j) { return angKF[j]; }, [&](int i, int) { return angF[i]; });
 }
 
 static bool csr_ok(const uint32_t *node, const uint32_t *off, const uint32_t *idx, int nn, int nfeat,
@@ -227,12 +176,7 @@ __global__ __launch_bounds__(256) void k_bow_descend(const uint32_t *__restrict_
         f_weight[i] = 0.0;
     }
     if (i >= n) return;
-    Desc8 q;
-    {
-        const uint32_t *p = (const uint32_t *)(desc + (int64_t)i * 32);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) q.w[k] = p[k];
-    }
+    const Desc8 q = load_desc8(desc + (int64_t)i * 32);
     uint32_t fin = 0, nid = 0;
     int level = 0;
     uint32_t c0 = child_off[0], c1 = child_off[1];
@@ -587,11 +531,7 @@ __global__ __launch_bounds__(256) void k_search_by_bow_rows(BowBatch a)
             rf0 = idxF[f0 + lane16];
             if (validF && !validF[rf0]) ok0 = false;
         }
-        {
-            const uint32_t *pf = (const uint32_t *)(descF + (int64_t)(ok0 ? rf0 : 0) * 32);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) d0.w[i] = pf[i];
-        }
+        d0 = load_desc8(descF + (int64_t)(ok0 ? rf0 : 0) * 32);
         for (uint32_t t = 0; t < nKa; ++t) {
             // the KF features of the node are staged 16 at a time in LDS (index, MapPoint flag, descriptor): the serial
             // loop below then depends on LDS latency only, not on two dependent global loads per feature
@@ -654,49 +594,10 @@ __global__ __launch_bounds__(256) void k_search_by_bow_rows(BowBatch a)
 // rotation prune for the batched form: angles come from the keypoint records
 __global__ __launch_bounds__(256) void k_rot_prune_bow_batch(BowBatch a)
 {
-    __shared__ int s_hist[ORBFE_HISTO_LENGTH];
-    __shared__ int s_keep[3];
-    __shared__ int s_count;
-    const int tid = threadIdx.x, p = blockIdx.x;
-    const int kf = a.kf[p], f = a.f[p];
-    const orbfe_keypoint *kK = a.kps + (int64_t)kf * a.cap, *kF = a.kps + (int64_t)f * a.cap;
-    int32_t *match = a.match + (int64_t)p * a.cap;
-    if (tid < ORBFE_HISTO_LENGTH) s_hist[tid] = 0;
-    if (tid == 0) s_count = 0;
-    __syncthreads();
-    if (a.check_ori) {
-        for (int i = tid; i < a.cap; i += 256) {
-            const int j = match[i];
-            if (j >= 0) atomicAdd(&s_hist[rot_bin(kK[j].angle, kF[i].angle)], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; ++i) {
-                const int s = s_hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
-            s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
-        }
-        __syncthreads();
-    }
-    int local = 0;
-    for (int i = tid; i < a.cap; i += 256) {
-        const int j = match[i];
-        if (j < 0) continue;
-        if (a.check_ori) {
-            const int bin = rot_bin(kK[j].angle, kF[i].angle);
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) { match[i] = -1; continue; }
-        }
-        ++local;
-    }
-    atomicAdd(&s_count, local);
-    __syncthreads();
-    if (tid == 0) a.nmatches[p] = s_count;
+    const int p = blockIdx.x;
+    const orbfe_keypoint *kK = a.kps + (int64_t)a.kf[p] * a.cap, *kF = a.kps + (int64_t)a.f[p] * a.cap;
+    rot_prune(a.match + (int64_t)p * a.cap, a.cap, a.check_ori, a.nmatches + p, [&](int, int j) { return kK[j].angle; },
+              [&](int i, int) { return kF[i].angle; });
 }
 
 extern "C" orbfe_status orbfe_bow_transform_batch_device(orbfe_matcher *m, const orbfe_vocabulary *v, const uint8_t *d_desc,

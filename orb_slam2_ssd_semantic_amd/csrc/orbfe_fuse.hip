@@ -19,12 +19,9 @@
 #include "orbfe_track_geom.h"
 
 static_assert(sizeof(orbfe_keypoint) == 7 * sizeof(float) && offsetof(orbfe_keypoint, octave) == 20, "keypoint record = 7 floats, octave sixth");
-static_assert(sizeof(TrkCam) == sizeof(orbfe_track_camera), "TrkCam is orbfe_track_camera");
 
 #define FUSE_ST 256              // threads of the search workgroup: four waves, one list entry each
 #define FUSE_RT 1024             // threads of the replay workgroup (one pair)
-#define FUSE_MAX_ENTRIES ((int64_t)1 << 25)
-#define FUSE_MAX_CAND ((int64_t)1 << 25)   // ntargets * cap of the candidates call
 #define FUSE_NOFIRST 0x7FFFFFFF
 
 struct FuseArgs {
@@ -51,19 +48,8 @@ struct FuseArgs {
 // the walk's view of keyframe row kf (0 <= kf < nkf); d_slot is not read: Fuse skips no occupied slot
 __device__ __forceinline__ ProjArgs fuse_frame_args(const FuseArgs &b, int kf)
 {
-    ProjArgs a;
-    const int64_t fb = (int64_t)kf * b.F.cap;
-    a.descF = b.F.d_desc + fb * 32;
-    a.xyF = (const float *)b.F.d_kps + fb * 7;
-    a.octF = (const int32_t *)b.F.d_kps + fb * 7 + 5;
-    a.nF = min(max(b.F.d_n[kf], 0), b.F.cap);
-    a.xs = 7; a.os = 7;
-    a.cell_off = b.F.d_cell_off + (int64_t)kf * (GRID_NC + 1);
-    a.cell_idx = b.F.d_cell_idx + fb;
-    a.minx = b.F.minx; a.miny = b.F.miny; a.gwi = b.F.gw_inv; a.ghi = b.F.gh_inv;
-    a.uRight = b.F.d_uright ? b.F.d_uright + fb : nullptr;
-    a.blocked = nullptr;
-    a.inv_sigma2 = nullptr;
+    ProjArgs a = proj_frame_view(b.F, kf);
+    if (b.F.d_uright) a.uRight = b.F.d_uright + (int64_t)kf * b.F.cap;
     a.nlevels = b.nlevels;
     a.th = b.th_low; a.ratio_rule = 0; a.nnratio = 0.f;
     return a;
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(FUSE_ST) void k_fuse_search(FuseArgs a)
         const ProjArgs pa = fuse_frame_args(a, kf);
         ProjRect R;
         if (proj_rect(pa, Q, R)) {
-            const Desc8 dq = proj_load_desc(a.map.d_desc + (int64_t)idx * 32);
+            const Desc8 dq = load_desc8(a.map.d_desc + (int64_t)idx * 32);
             proj_walk(pa, Q, R, sub, [&](uint32_t k) {
                 if (k >= (uint32_t)pa.nF) return;
                 const int o = pa.octF[(size_t)pa.os * k];
@@ -275,40 +261,24 @@ __global__ __launch_bounds__(TRK_GT) void k_fuse_cand_write(FuseCandArgs a)
 // ---------------------------------------------------------------------------------------------------
 namespace
 {
-TrkCam cam_of(const orbfe_track_camera *c)
-{
-    TrkCam t;
-    t.fx = c->fx; t.fy = c->fy; t.cx = c->cx; t.cy = c->cy; t.bf = c->bf;
-    t.minx = c->minx; t.maxx = c->maxx; t.miny = c->miny; t.maxy = c->maxy;
-    return t;
-}
-
-bool levels_of(const float *v, int32_t nlevels, TrkLevels *out)
-{
-    if (!v || nlevels < 1 || nlevels > TRK_MAX_LEVELS) return false;
-    for (int i = 0; i < TRK_MAX_LEVELS; ++i) out->v[i] = i < nlevels ? v[i] : 0.f;
-    return true;
-}
-
 // every refusal of the two batch calls, before any launch; fills `a` except the outputs
 orbfe_status fuse_check(const char *who, orbfe_matcher *m, const orbfe_track_frames *F, int32_t nkf, const orbfe_fuse_lists *L,
                         const orbfe_track_camera *cam, const orbfe_track_map *map, float th, const float *scale_factors,
                         const float *inv_level_sigma2, int32_t nlevels, float log_scale_factor, int32_t th_low, int32_t mode, FuseArgs *a)
 {
-    if (!m || !F || !L || !cam || !map || nkf < 0 || L->npairs < 0 || L->nentries < 0 || F->cap < 0 || map->npoints < 0 ||
-        !levels_of(scale_factors, nlevels, &a->sf) || !levels_of(inv_level_sigma2, nlevels, &a->inv_sigma2) ||
+    if (!m || !L || !cam || !map || nkf < 0 || L->npairs < 0 || L->nentries < 0 || !trk_frames_ok(F, nkf, 0) || map->npoints < 0 ||
+        !trk_levels_of(scale_factors, nlevels, &a->sf) || !trk_levels_of(inv_level_sigma2, nlevels, &a->inv_sigma2) ||
         (mode != ORBFE_FUSE_PLAIN && mode != ORBFE_FUSE_SIM3) || th_low < 0 || th_low > 255 ||
-        (nkf > 0 && (!F->d_kps || !F->d_desc || !F->d_n || !F->d_cell_off || !F->d_cell_idx)) ||
         (L->npairs > 0 && (!L->d_pair_kf || !L->d_Tcw || !L->d_Ow || !L->d_list_off)) || (L->nentries > 0 && !L->d_list_idx) ||
         (map->npoints > 0 && (!map->d_world_pos || !map->d_normal || !map->d_min_dist || !map->d_max_dist || !map->d_bad || !map->d_desc))) {
         orbfe_set_error("bad argument to %s (nlevels 1..%d, th_low 0..255, mode ORBFE_FUSE_PLAIN or ORBFE_FUSE_SIM3)", who, TRK_MAX_LEVELS);
         return ORBFE_ERR_ARG;
     }
     if (F->cap > PJ_MAX_NF) { orbfe_set_error("%s: at most %d features per keyframe", who, PJ_MAX_NF); return ORBFE_ERR_ARG; }
-    if (L->nentries > FUSE_MAX_ENTRIES) { orbfe_set_error("%s: at most 2^25 list entries per call", who); return ORBFE_ERR_ARG; }
+    if (L->nentries > TRK_MAX_SLOTS) { orbfe_set_error("%s: at most 2^25 list entries per call", who); return ORBFE_ERR_ARG; }
     a->F = *F;
     a->nkf = nkf;
-    a->cam = cam_of(cam);
+    a->cam = *cam;
     a->th = th; a->log_sf = log_scale_factor;
     a->nlevels = nlevels; a->th_low = th_low; a->mode = mode;
     a->map = *map;
@@ -340,7 +310,7 @@ extern "C" orbfe_status orbfe_fuse_gate_points(const float *Tcw, const float *Ow
         orbfe_set_error("bad argument to orbfe_fuse_gate_points");
         return ORBFE_ERR_ARG;
     }
-    const TrkCam c = cam_of(cam);
+    const TrkCam c = *cam;
     for (int i = 0; i < n; ++i) {
         orbfe_proj_query e;
         memset(&e, 0, sizeof(e));
@@ -360,7 +330,7 @@ extern "C" orbfe_status orbfe_fuse_gate_points(const float *Tcw, const float *Ow
 
 extern "C" int64_t orbfe_fuse_scratch_bytes(int32_t npoints, int32_t ntargets, int32_t cap)
 {
-    if (npoints < 0 || ntargets < 0 || cap < 1 || cap > PJ_MAX_NF || (int64_t)ntargets * cap >= FUSE_MAX_CAND) return -1;
+    if (npoints < 0 || ntargets < 0 || cap < 1 || cap > PJ_MAX_NF || (int64_t)ntargets * cap >= TRK_MAX_SLOTS) return -1;
     const size_t nb = (size_t)(((int64_t)ntargets * cap + TRK_GT - 1) / TRK_GT);
     // first positions | in-current flags | block counts | block offsets: what orbfe_fuse_candidates_device asks the scratch for
     return (int64_t)(orb_align256(std::max<size_t>((size_t)npoints * 4, 4)) + orb_align256(std::max<size_t>((size_t)npoints, 4)) +
@@ -426,7 +396,7 @@ extern "C" orbfe_status orbfe_fuse_candidates_device(orbfe_matcher *m, const int
         orbfe_set_error("bad argument to orbfe_fuse_candidates_device");
         return ORBFE_ERR_ARG;
     }
-    if (cap > PJ_MAX_NF || (int64_t)ntargets * cap >= FUSE_MAX_CAND) {
+    if (cap > PJ_MAX_NF || (int64_t)ntargets * cap >= TRK_MAX_SLOTS) {
         orbfe_set_error("orbfe_fuse_candidates_device: cap <= %d and ntargets * cap < 2^25", PJ_MAX_NF);
         return ORBFE_ERR_ARG;
     }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "orbfe_common.h"
+#include "orbfe_match_dev.h"   // rot_three_maxima, rot_keeps: host and device
 
 namespace
 {
@@ -144,23 +145,9 @@ extern "C" orbfe_status orbfe_rotation_consistency(const float *angle_a, const f
         bin_of[(size_t)i] = b;
         count[(size_t)b]++;
     }
-    // the three fullest bins, an earlier bin wins a tie; second / third dropped under a tenth of the first (:1912-1957)
-    int top[3] = {0, 0, 0}, idx[3] = {-1, -1, -1};
-    for (int b = 0; b < histo_len; ++b) {
-        const int c = count[(size_t)b];
-        int r = 3;
-        while (r > 0 && c > top[r - 1]) --r;
-        if (r == 3) continue;
-        for (int k = 2; k > r; --k) { top[k] = top[k - 1]; idx[k] = idx[k - 1]; }
-        top[r] = c;
-        idx[r] = b;
-    }
-    if ((float)top[1] < 0.1f * (float)top[0]) idx[1] = idx[2] = -1;
-    else if ((float)top[2] < 0.1f * (float)top[0]) idx[2] = -1;
-    for (int i = 0; i < n; ++i) {
-        const int b = bin_of[(size_t)i];
-        drop[i] = !(b == idx[0] || b == idx[1] || b == idx[2]);
-    }
+    int keep[3];
+    rot_three_maxima(count.data(), histo_len, keep);   // the kernels' own (orbfe_match_dev.h)
+    for (int i = 0; i < n; ++i) drop[i] = !rot_keeps(keep, bin_of[(size_t)i]);
     return ORBFE_OK;
 }
 

@@ -194,9 +194,7 @@ __global__ __launch_bounds__(TRK_GT) void k_isrch_finish(IsrchArgs x)
         if (a1) atomicAdd(&s_o1, a1);
         if (a2) atomicAdd(&s_o2, a2);
     }
-    auto bin_of = [&](int i1, int m) {
-        return min(max(rot_bin(k1[(int64_t)i1 * 7 + 3], k2[(int64_t)m * 7 + 3]), 0), ORBFE_HISTO_LENGTH - 1);
-    };
+    auto bin_of = [&](int i1, int m) { return rot_bin_clamped(k1[(int64_t)i1 * 7 + 3], k2[(int64_t)m * 7 + 3]); };
     if (!short_cap) {
         for (int i = tid; i < nq; i += TRK_GT) {
             const int m = match[i];
@@ -207,7 +205,7 @@ __global__ __launch_bounds__(TRK_GT) void k_isrch_finish(IsrchArgs x)
     }
     __syncthreads();
     if (x.check_ori) {
-        if (tid == 0) trk_three_maxima(s_hist, s_keep);
+        if (tid == 0) rot_three_maxima(s_hist, ORBFE_HISTO_LENGTH, s_keep);
         __syncthreads();
     }
     const int64_t o1 = s_o1, o2 = s_o2;
@@ -228,7 +226,7 @@ __global__ __launch_bounds__(TRK_GT) void k_isrch_finish(IsrchArgs x)
             const int m = match[pos];
             if (m >= 0 && m < n2 && s_holder[m] == pos) {
                 const int bin = x.check_ori ? bin_of(i, m) : 0;
-                if (!x.check_ori || bin == s_keep[0] || bin == s_keep[1] || bin == s_keep[2]) mm = m;
+                if (!x.check_ori || rot_keeps(s_keep, bin)) mm = m;
             }
         }
         x.matches12[fb1 + i] = mm;
@@ -291,7 +289,7 @@ orbfe_status limits(const char *who, int32_t npairs, int32_t cap1, int32_t cap2,
 {
     if (th_low > 255) { orbfe_set_error("%s: th_low must be below 256 (256 is the 'no candidate' distance)", who); return ORBFE_ERR_ARG; }
     if (cap1 > PJ_MAX_NF || cap2 > PJ_MAX_NF) { orbfe_set_error("%s: at most %d features per frame", who, PJ_MAX_NF); return ORBFE_ERR_SIZE; }
-    if ((int64_t)npairs * cap1 >= (int64_t)1 << 25 || ent_cap > 0xFFFFFFFFll) {
+    if ((int64_t)npairs * cap1 >= TRK_MAX_SLOTS || ent_cap > 0xFFFFFFFFll) {
         orbfe_set_error("%s: npairs * cap must stay below 2^25 and ent_cap below 2^32", who);
         return ORBFE_ERR_SIZE;
     }

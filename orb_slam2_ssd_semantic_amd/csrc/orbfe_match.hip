@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256) void k_match_popc(const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K10  rotation-consistency histogram over accepted matches, ComputeThreeMaxima, prune, count.
+// K10  rotation-consistency histogram over accepted matches, ComputeThreeMaxima, prune, count (rot_prune, orbfe_match_dev.h).
 // One workgroup per pair.  key i is kept when its bin is one of the three maxima.
 // angles: element i of side X is at X_ang[i * stride] (stride 1 for plain arrays, 7 for orbfe_keypoint).
 // ---------------------------------------------------------------------------------------------------
@@ -353,10 +353,7 @@ __global__ __launch_bounds__(256) void k_rot_prune(int32_t *__restrict__ match, 
                                                    const int32_t *__restrict__ bframe, int cap, int n_s,
                                                    int check_ori, int32_t *__restrict__ nmatches)
 {
-    __shared__ int s_hist[ORBFE_HISTO_LENGTH];
-    __shared__ int s_keep[3];
-    __shared__ int s_count;
-    const int pair = blockIdx.x, tid = threadIdx.x;
+    const int pair = blockIdx.x;
     int n = n_s;
     int32_t *mt = match;
     const float *aa = a_ang, *ba = b_ang;
@@ -367,51 +364,8 @@ __global__ __launch_bounds__(256) void k_rot_prune(int32_t *__restrict__ match, 
         aa = a_ang + (int64_t)af * cap * ang_stride;
         ba = b_ang + (int64_t)bf * cap * ang_stride;
     }
-    if (tid < ORBFE_HISTO_LENGTH) s_hist[tid] = 0;
-    if (tid == 0) s_count = 0;
-    __syncthreads();
-    if (check_ori) {
-        for (int i = tid; i < n; i += 256) {
-            const int j = mt[i];
-            if (j >= 0) atomicAdd(&s_hist[rot_bin(aa[(int64_t)i * ang_stride], ba[(int64_t)j * ang_stride])], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {  // ComputeThreeMaxima (:1912-1957)
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; ++i) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s; i3 = i;
-                }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
-            s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
-        }
-        __syncthreads();
-    }
-    int local = 0;
-    for (int i = tid; i < n; i += 256) {
-        const int j = mt[i];
-        if (j < 0) continue;
-        if (check_ori) {
-            const int bin = rot_bin(aa[(int64_t)i * ang_stride], ba[(int64_t)j * ang_stride]);
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
-                mt[i] = -1;
-                continue;
-            }
-        }
-        ++local;
-    }
-    atomicAdd(&s_count, local);
-    __syncthreads();
-    if (tid == 0) nmatches[pair] = s_count;
+    rot_prune(mt, n, check_ori, nmatches + pair, [&](int i, int) { return aa[(int64_t)i * ang_stride]; },
+              [&](int, int j) { return ba[(int64_t)j * ang_stride]; });
 }
 
 // 8(f).1: best / second-best over a per-query candidate list
@@ -423,7 +377,7 @@ __global__ __launch_bounds__(256) void k_hamming_csr(const uint8_t *__restrict__
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nq) return;
-    Desc8 dq;
+    Desc8 dq;   // not load_desc8: through it this kernel compiles to other code (profiles/search_helpers_shared.md)
     const uint32_t *p = (const uint32_t *)(q + (int64_t)i * 32);
 #pragma unroll
     for (int k = 0; k < 8; ++k) dq.w[k] = p[k];
@@ -452,10 +406,7 @@ __global__ __launch_bounds__(256) void k_hamming_csr_all(const uint8_t *__restri
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= nq) return;
     const int lane = threadIdx.x & 63;
-    Desc8 dq;
-    const uint32_t *p = (const uint32_t *)(q + (int64_t)i * 32);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dq.w[k] = p[k];
+    const Desc8 dq = load_desc8(q + (int64_t)i * 32);
     const uint32_t e = off[i + 1];
     for (uint32_t j = off[i] + (uint32_t)lane; j < e; j += 64u)
         dist[j] = (uint16_t)hamming8(dq, (const uint32_t *)(t + (int64_t)cand[j] * 32));

@@ -1,6 +1,11 @@
-// orbfe_match_dev.h -- the device helpers the matcher's translation units share (orbfe_match.hip, orbfe_grid.hip,
-// orbfe_projection.hip, orbfe_stereo.hip, orbfe_bow.hip).  The library is built without relocatable device code, so every
-// kernel gets its own inlined copy.
+// orbfe_match_dev.h -- the helpers the matcher's translation units share: the descriptor (Desc8, load_desc8, hamming8), the
+// ranking key of k_match_bf, the two-smallest merge (merge_best2) and the rotation-consistency check of the reference, stated
+// once: the bin (rot_bin, rot_bin_clamped), ComputeThreeMaxima (rot_three_maxima, host and device), the keep test (rot_keeps)
+// and the whole prune of one match row (rot_prune).  For orbfe_match.hip, orbfe_grid.hip, orbfe_projection.hip,
+// orbfe_stereo.hip and orbfe_bow.hip; through orbfe_proj_dev.h / orbfe_track_dev.h for the device-resident searches
+// (orbfe_track.hip, orbfe_init_search.hip, orbfe_tri_search.hip); and for the host entry point orbfe_rotation_consistency
+// (orbfe_hostgeom.hip), which runs the very rot_three_maxima / rot_keeps the kernels call.  The library is built without
+// relocatable device code, so every kernel gets its own inlined copy.
 #pragma once
 
 #include "orbfe_common.h"
@@ -11,6 +16,15 @@
 struct Desc8 {
     uint32_t w[8];
 };
+
+__device__ __forceinline__ Desc8 load_desc8(const uint8_t *row)
+{
+    Desc8 d;
+    const uint32_t *p = (const uint32_t *)row;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d.w[k] = p[k];
+    return d;
+}
 
 __device__ __forceinline__ int hamming8(const Desc8 &a, const uint32_t *__restrict__ b)
 {
@@ -108,4 +122,70 @@ __device__ __forceinline__ int rot_bin(float a1, float a2)
     int bin = (int)roundf(__fmul_rn(rot, factor));
     if (bin == ORBFE_HISTO_LENGTH) bin = 0;
     return bin;
+}
+
+// the replay kernels index their histogram with it: a NaN angle cannot reach outside the 30 bins
+__device__ __forceinline__ int rot_bin_clamped(float a1, float a2) { return min(max(rot_bin(a1, a2), 0), ORBFE_HISTO_LENGTH - 1); }
+
+// ComputeThreeMaxima (src/ORBmatcher.cc:1912-1957) over the `len` bins of a rotation histogram: keep[0..2] = the bins that stay,
+// the fullest first, an earlier bin winning a tie; -1 where there is none or where the second / third is under a tenth of the
+// first.  One thread calls it.  The library is built with -ffp-contract=off: the product is one rounded multiply on both sides.
+__host__ __device__ __forceinline__ void rot_three_maxima(const int *hist, int len, int keep[3])
+{
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+    for (int i = 0; i < len; ++i) {
+        const int s = hist[i];
+        if (s > max1) {
+            max3 = max2; max2 = max1; max1 = s;
+            i3 = i2; i2 = i1; i1 = i;
+        } else if (s > max2) {
+            max3 = max2; max2 = s;
+            i3 = i2; i2 = i;
+        } else if (s > max3) {
+            max3 = s; i3 = i;
+        }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+    keep[0] = i1; keep[1] = i2; keep[2] = i3;
+}
+
+// does a match whose rotation fell into `bin` stand?
+__host__ __device__ __forceinline__ bool rot_keeps(const int *keep, int bin) { return bin == keep[0] || bin == keep[1] || bin == keep[2]; }
+
+// The rotation prune of one match row by one workgroup of 256 threads (:308-313, :336-349): histogram over the matches
+// match[i] = j >= 0 of rot_bin(first(i, j), second(i, j)), three maxima, the matches of the other bins cleared, *nmatches = what
+// stands (all of them when check_ori is 0).  Every thread of the workgroup calls it with the same arguments.
+template <typename A1, typename A2>
+__device__ __forceinline__ void rot_prune(int32_t *match, int n, int check_ori, int32_t *nmatches, A1 first, A2 second)
+{
+    __shared__ int s_hist[ORBFE_HISTO_LENGTH];
+    __shared__ int s_keep[3];
+    __shared__ int s_count;
+    const int tid = threadIdx.x;
+    if (tid < ORBFE_HISTO_LENGTH) s_hist[tid] = 0;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    if (check_ori) {
+        for (int i = tid; i < n; i += 256) {
+            const int j = match[i];
+            if (j >= 0) atomicAdd(&s_hist[rot_bin(first(i, j), second(i, j))], 1);
+        }
+        __syncthreads();
+        if (tid == 0) rot_three_maxima(s_hist, ORBFE_HISTO_LENGTH, s_keep);
+        __syncthreads();
+    }
+    int local = 0;
+    for (int i = tid; i < n; i += 256) {
+        const int j = match[i];
+        if (j < 0) continue;
+        if (check_ori && !rot_keeps(s_keep, rot_bin(first(i, j), second(i, j)))) {
+            match[i] = -1;
+            continue;
+        }
+        ++local;
+    }
+    atomicAdd(&s_count, local);
+    __syncthreads();
+    if (tid == 0) *nmatches = s_count;
 }

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(NP_T) void k_np_claim(NpClaimArgs a)
 // ---------------------------------------------------------------------------------------------------
 namespace
 {
-bool np_limits_ok(int64_t npairs, int64_t cap) { return npairs >= 0 && cap >= 1 && cap <= NP_MAX_CAP && npairs * cap < ((int64_t)1 << 25); }
+bool np_limits_ok(int64_t npairs, int64_t cap) { return npairs >= 0 && cap >= 1 && cap <= NP_MAX_CAP && npairs * cap < TRK_MAX_SLOTS; }
 size_t np_xyz_bytes(int64_t npairs, int64_t cap) { return orb_align256(std::max<size_t>((size_t)npairs * (size_t)cap * 12, 4)); }
 // the layout of b[7]: xyz_all, F12, epi, pair_skip, median
 struct NpScratch {

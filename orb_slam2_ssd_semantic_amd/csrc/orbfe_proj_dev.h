@@ -1,9 +1,13 @@
 // orbfe_proj_dev.h -- the device side of the projection-gated search, once, for orbfe_projection.hip (one frame, host buffers) and
 // orbfe_track.hip (a batch of frames, device-resident), in the order it runs: the argument block, the cell rectangle
 // (proj_rect), the walk (proj_walk), the count (proj_count), the gates (proj_gate_skip) and the distance (proj_dist), the
-// two-smallest merge (proj_reduce2), the acceptance rule (proj_decide).  NOT the relaxation rounds: k_proj_resolve and
+// two-smallest merge (proj_reduce2), the acceptance rule (proj_decide).  The query descriptor is loaded with orbfe_match_dev.h's
+// load_desc8.  Two things are NOT here, because shared they measured slower.  The relaxation rounds: k_proj_resolve and
 // k_trk_resolve each keep their loop, which inside a shared inlined function compiled to a candidate scan 3 us slower
-// (profiles/proj_core_shared.md).  Behind them the per-candidate test of SearchForTriangulation (tri_line, tri_candidate), for
+// (profiles/proj_core_shared.md).  The one-wave first-minimum search of k_fuse_search (orbfe_fuse.hip) and k_s3_search
+// (orbfe_sim3_search.hip): each keeps its copy, since through one inlined function k_s3_search ran 5 % slower at 256 pairs
+// (profiles/search_helpers_shared.md).
+// At the end of the file stands the per-candidate test of SearchForTriangulation (tri_line, tri_candidate), for
 // orbfe_projection.hip and orbfe_tri_search.hip.  No relocatable device code: every kernel gets its own inlined copy.
 #pragma once
 
@@ -118,15 +122,6 @@ __device__ __forceinline__ void proj_count(const ProjArgs &a, const orbfe_proj_q
 #pragma unroll
     for (int o = PJ_LC / 2; o > 0; o >>= 1) tot += __shfl_xor(tot, o, PJ_LC);
     if (sub == 0) cnt[g] = (uint32_t)tot;
-}
-
-__device__ __forceinline__ Desc8 proj_load_desc(const uint8_t *row)
-{
-    Desc8 d;
-    const uint32_t *p = (const uint32_t *)row;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) d.w[k] = p[k];
-    return d;
 }
 
 // Does candidate f of query Q get PJ_SKIP for a distance?  When its slot is blocked before the call (a.blocked[f] >= blocks_from:

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_proj_fill(ProjArgs a)
     if (!proj_rect(a, Q, R)) return;   // wave-uniform
     const int mine = a.lcnt[(size_t)i * PJ_LC + sub];
     uint32_t o = a.off[i] + (uint32_t)(wave_incl_scan_m(mine) - mine);
-    const Desc8 dq = proj_load_desc(a.qdesc + (int64_t)i * 32);
+    const Desc8 dq = load_desc8(a.qdesc + (int64_t)i * 32);
     proj_walk(a, Q, R, sub, [&](uint32_t f) {
         const bool skip = proj_gate_skip(a, Q, f, 1, a.inv_sigma2 != nullptr, [&](int lv) { return a.inv_sigma2[lv]; });
         const uint32_t d = proj_dist(a, dq, f, skip);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(PJ_FT) void k_proj_fused(ProjFusedArgs p)
             } else if (tot > 0) {
                 uint32_t o = (uint32_t)(incl - n);
                 uint32_t *ent = a.ent + (size_t)i * PJ_SLAB;
-                const Desc8 dq = proj_load_desc(a.qdesc + (int64_t)i * 32);
+                const Desc8 dq = load_desc8(a.qdesc + (int64_t)i * 32);
                 proj_walk(a, Q, R, lane, [&](uint32_t f) {
                     const bool skip = proj_gate_skip(a, Q, f, 1, a.inv_sigma2 != nullptr, [&](int lv) { return a.inv_sigma2[lv]; });
                     const uint32_t d = proj_dist(a, dq, f, skip);
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256) void k_triangulation(TriArgs a)
     int best = -1;
     const int lo = a.range1[2 * f1], hi = a.range1[2 * f1 + 1];
     if (hi > lo && a.elig1[f1]) {
-        const Desc8 d1 = proj_load_desc(a.desc1 + (int64_t)f1 * 32);
+        const Desc8 d1 = load_desc8(a.desc1 + (int64_t)f1 * 32);
         const bool st1 = a.stereo1[f1] != 0;
         const TriLine l = tri_line(a.xy1[2 * f1], a.xy1[2 * f1 + 1], a.F);
         int bestDist = a.th_low;   // never above th_low: `dist > bestDist` is the whole of :895

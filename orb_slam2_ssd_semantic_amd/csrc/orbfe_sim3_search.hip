@@ -26,12 +26,10 @@
 #include "orbfe_track_geom.h"
 
 static_assert(sizeof(orbfe_keypoint) == 7 * sizeof(float) && offsetof(orbfe_keypoint, octave) == 20, "keypoint record = 7 floats, octave sixth");
-static_assert(sizeof(TrkCam) == sizeof(orbfe_track_camera), "TrkCam is orbfe_track_camera");
 
 #define S3_ST 256                // threads of the search workgroup: four waves, one live query each per turn
 #define S3_SG 128                // search workgroups per (pair, direction) at most: the waves stride over the live queries
 #define S3_MT 1024               // threads of the member workgroup (one pair)
-#define S3_MAX_SLOTS ((int64_t)1 << 25)   // npairs * 2 * cap of the Sim3 search, npairs * qcap and nentries of the projection search
 
 struct S3Args {
     orbfe_track_frames F;
@@ -65,19 +63,7 @@ __device__ __forceinline__ int s3_count(const S3Args &a, int kf) { return min(ma
 // the walk's view of keyframe row kf (0 <= kf < nkf): no blocked slots, no right-image gate, no chi2 gate
 __device__ __forceinline__ ProjArgs s3_frame_args(const S3Args &b, int kf)
 {
-    ProjArgs a;
-    const int64_t fb = (int64_t)kf * b.F.cap;
-    a.descF = b.F.d_desc + fb * 32;
-    a.xyF = (const float *)b.F.d_kps + fb * 7;
-    a.octF = (const int32_t *)b.F.d_kps + fb * 7 + 5;
-    a.nF = s3_count(b, kf);
-    a.xs = 7; a.os = 7;
-    a.cell_off = b.F.d_cell_off + (int64_t)kf * (GRID_NC + 1);
-    a.cell_idx = b.F.d_cell_idx + fb;
-    a.minx = b.F.minx; a.miny = b.F.miny; a.gwi = b.F.gw_inv; a.ghi = b.F.gh_inv;
-    a.uRight = nullptr;
-    a.blocked = nullptr;
-    a.inv_sigma2 = nullptr;
+    ProjArgs a = proj_frame_view(b.F, kf);
     a.nlevels = b.nlevels;
     a.th = b.th_high; a.ratio_rule = 0; a.nnratio = 0.f;
     return a;
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(S3_ST) void k_s3_search(S3Args a)
         int best = 256, bestIdx = -1;
         ProjRect R;
         if (proj_rect(pa, Q, R)) {
-            const Desc8 dq = proj_load_desc(a.map.d_desc + (int64_t)mp * 32);
+            const Desc8 dq = load_desc8(a.map.d_desc + (int64_t)mp * 32);
             proj_walk(pa, Q, R, sub, [&](uint32_t k) {
                 if (k >= (uint32_t)pa.nF) return;
                 const int dist = (int)proj_dist(pa, dq, k, false);
@@ -476,26 +462,6 @@ __global__ __launch_bounds__(TRK_GT) void k_s3_keep(S3GlueArgs a)
 // ---------------------------------------------------------------------------------------------------
 namespace
 {
-TrkCam cam_of(const orbfe_track_camera *c)
-{
-    TrkCam t;
-    t.fx = c->fx; t.fy = c->fy; t.cx = c->cx; t.cy = c->cy; t.bf = c->bf;
-    t.minx = c->minx; t.maxx = c->maxx; t.miny = c->miny; t.maxy = c->maxy;
-    return t;
-}
-
-bool levels_of(const float *v, int32_t nlevels, TrkLevels *out)
-{
-    if (!v || nlevels < 1 || nlevels > TRK_MAX_LEVELS) return false;
-    for (int i = 0; i < TRK_MAX_LEVELS; ++i) out->v[i] = i < nlevels ? v[i] : 0.f;
-    return true;
-}
-
-bool frames_ok(const orbfe_track_frames *F, int32_t nframes)
-{
-    return F && F->cap >= 1 && (nframes == 0 || (F->d_kps && F->d_desc && F->d_n && F->d_cell_off && F->d_cell_idx));
-}
-
 // table size of the member set for `cap` row entries: a power of two >= 2 * cap, at least 64
 int member_log2(int32_t cap)
 {
@@ -540,7 +506,7 @@ extern "C" orbfe_status orbfe_sim3_gate_points(const float *T_own, const float *
         orbfe_set_error("bad argument to orbfe_sim3_gate_points");
         return ORBFE_ERR_ARG;
     }
-    const TrkCam c = cam_of(cam);
+    const TrkCam c = *cam;
     for (int i = 0; i < n; ++i) {
         orbfe_proj_query e;
         memset(&e, 0, sizeof(e));
@@ -580,8 +546,8 @@ extern "C" orbfe_status orbfe_sim3_pair_poses_device(orbfe_matcher *m, const voi
 
 extern "C" int64_t orbfe_sim3_search_scratch_bytes(int32_t npairs, int32_t cap, int32_t qcap, int64_t nentries, int64_t ent_cap)
 {
-    if (npairs < 0 || cap < 1 || cap > PJ_MAX_NF || qcap < 0 || nentries < 0 || ent_cap < 0 || (int64_t)npairs * 2 * cap >= S3_MAX_SLOTS ||
-        (int64_t)npairs * qcap >= S3_MAX_SLOTS || nentries > S3_MAX_SLOTS || ent_cap > 0xFFFFFFFFll)
+    if (npairs < 0 || cap < 1 || cap > PJ_MAX_NF || qcap < 0 || nentries < 0 || ent_cap < 0 || (int64_t)npairs * 2 * cap >= TRK_MAX_SLOTS ||
+        (int64_t)npairs * qcap >= TRK_MAX_SLOTS || nentries > TRK_MAX_SLOTS || ent_cap > 0xFFFFFFFFll)
         return -1;
     if (qcap == 0) {
         // orbfe_search_by_sim3_batch_device: queries | slots | points | counts | vnMatch1 / vnMatch2
@@ -608,14 +574,14 @@ extern "C" orbfe_status orbfe_search_by_sim3_batch_device(orbfe_matcher *m, cons
                                                           int32_t *d_match1, int32_t *d_match2, void *stream)
 {
     S3Args a;
-    if (!m || !cam || !map || nkf < 0 || npairs < 0 || !frames_ok(kf, nkf) || !levels_of(scale_factors, nlevels, &a.sf) || th_high < 0 ||
+    if (!m || !cam || !map || nkf < 0 || npairs < 0 || !trk_frames_ok(kf, nkf, 1) || !trk_levels_of(scale_factors, nlevels, &a.sf) || th_high < 0 ||
         th_high > 255 || map->npoints < 0 || (nkf > 0 && (!d_Tcw || !d_slot_mp)) ||
         (npairs > 0 && (!d_kf1 || !d_kf2 || !d_T12 || !d_T21 || !d_match12 || !d_nfound)) ||
         (map->npoints > 0 && (!map->d_world_pos || !map->d_min_dist || !map->d_max_dist || !map->d_bad || !map->d_desc))) {
         orbfe_set_error("bad argument to orbfe_search_by_sim3_batch_device (nlevels 1..%d, th_high 0..255)", TRK_MAX_LEVELS);
         return ORBFE_ERR_ARG;
     }
-    if (kf->cap > PJ_MAX_NF || (int64_t)npairs * 2 * kf->cap >= S3_MAX_SLOTS) {
+    if (kf->cap > PJ_MAX_NF || (int64_t)npairs * 2 * kf->cap >= TRK_MAX_SLOTS) {
         orbfe_set_error("orbfe_search_by_sim3_batch_device: cap <= %d and npairs * 2 * cap < 2^25", PJ_MAX_NF);
         return ORBFE_ERR_ARG;
     }
@@ -632,7 +598,7 @@ extern "C" orbfe_status orbfe_search_by_sim3_batch_device(orbfe_matcher *m, cons
     ORBFE_HIP(m->b[12].ensure((size_t)npairs * 8));
     a.F = *kf;
     a.nkf = nkf;
-    a.cam = cam_of(cam);
+    a.cam = *cam;
     a.th = th; a.log_sf = log_scale_factor; a.nlevels = nlevels; a.th_high = th_high;
     a.map = *map;
     a.Tcw = d_Tcw; a.slot_mp = d_slot_mp;
@@ -658,7 +624,7 @@ extern "C" orbfe_status orbfe_mark_list_members_device(orbfe_matcher *m, const i
         orbfe_set_error("bad argument to orbfe_mark_list_members_device");
         return ORBFE_ERR_ARG;
     }
-    if (cap > PJ_MAX_NF || nentries > S3_MAX_SLOTS) {
+    if (cap > PJ_MAX_NF || nentries > TRK_MAX_SLOTS) {
         orbfe_set_error("orbfe_mark_list_members_device: cap <= %d and nentries <= 2^25", PJ_MAX_NF);
         return ORBFE_ERR_ARG;
     }
@@ -676,14 +642,14 @@ extern "C" orbfe_status orbfe_search_by_projection_sim3_batch_device(orbfe_match
                                                                      int32_t *d_matched, int32_t *d_nmatches, int32_t *d_status, void *stream)
 {
     PS3Args a;
-    if (!m || !cam || !map || npairs < 0 || nentries < 0 || qcap < 1 || ent_cap < 0 || !frames_ok(kf, npairs) ||
-        !levels_of(scale_factors, nlevels, &a.sf) || th_low < 0 || th_low > 255 || map->npoints < 0 ||
+    if (!m || !cam || !map || npairs < 0 || nentries < 0 || qcap < 1 || ent_cap < 0 || !trk_frames_ok(kf, npairs, 1) ||
+        !trk_levels_of(scale_factors, nlevels, &a.sf) || th_low < 0 || th_low > 255 || map->npoints < 0 ||
         (npairs > 0 && (!d_Tcw || !d_Ow || !d_list_off || !d_matched || !d_nmatches || !d_status)) || (nentries > 0 && !d_list_idx) ||
         (map->npoints > 0 && (!map->d_world_pos || !map->d_normal || !map->d_min_dist || !map->d_max_dist || !map->d_bad || !map->d_desc))) {
         orbfe_set_error("bad argument to orbfe_search_by_projection_sim3_batch_device (nlevels 1..%d, th_low 0..255, qcap >= 1)", TRK_MAX_LEVELS);
         return ORBFE_ERR_ARG;
     }
-    if (kf->cap > PJ_MAX_NF || (int64_t)npairs * qcap >= S3_MAX_SLOTS || nentries > S3_MAX_SLOTS || ent_cap > 0xFFFFFFFFll) {
+    if (kf->cap > PJ_MAX_NF || (int64_t)npairs * qcap >= TRK_MAX_SLOTS || nentries > TRK_MAX_SLOTS || ent_cap > 0xFFFFFFFFll) {
         orbfe_set_error("orbfe_search_by_projection_sim3_batch_device: cap <= %d, npairs * qcap < 2^25, nentries <= 2^25, ent_cap < 2^32", PJ_MAX_NF);
         return ORBFE_ERR_ARG;
     }
@@ -703,7 +669,7 @@ extern "C" orbfe_status orbfe_search_by_projection_sim3_batch_device(orbfe_match
     ORBFE_HIP(m->b[15].ensure((size_t)nentries));
     a.npairs = npairs; a.cap = cap; a.qcap = qcap;
     a.Tcw = d_Tcw; a.Ow = d_Ow;
-    a.cam = cam_of(cam);
+    a.cam = *cam;
     a.th = th; a.log_sf = log_scale_factor; a.nlevels = nlevels;
     a.map = *map;
     a.list_off = d_list_off; a.list_idx = d_list_idx; a.nentries = (uint32_t)nentries;
@@ -740,7 +706,7 @@ extern "C" orbfe_status orbfe_search_by_projection_sim3_batch_device(orbfe_match
 extern "C" orbfe_status orbfe_sim3_invert_matches_device(orbfe_matcher *m, const int32_t *d_bow_match, const int32_t *d_kf2, const int32_t *d_n,
                                                          int32_t nkf, int32_t cap, int32_t npairs, int32_t *d_match12, void *stream)
 {
-    if (!m || nkf < 0 || cap < 1 || cap > PJ_MAX_NF || npairs < 0 || (int64_t)npairs * cap >= S3_MAX_SLOTS ||
+    if (!m || nkf < 0 || cap < 1 || cap > PJ_MAX_NF || npairs < 0 || (int64_t)npairs * cap >= TRK_MAX_SLOTS ||
         (npairs > 0 && (!d_bow_match || !d_kf2 || !d_n || !d_match12))) {
         orbfe_set_error("bad argument to orbfe_sim3_invert_matches_device (cap <= %d, npairs * cap < 2^25)", PJ_MAX_NF);
         return ORBFE_ERR_ARG;
@@ -765,8 +731,8 @@ extern "C" orbfe_status orbfe_sim3_correspondences_device(orbfe_matcher *m, cons
 {
     S3GlueArgs a;
     memset(&a, 0, sizeof(a));
-    if (!m || !map || nkf < 0 || npairs < 0 || corr_cap < 0 || !kf || kf->cap < 1 || kf->cap > PJ_MAX_NF || !levels_of(level_sigma2, nlevels, &a.sigma2) ||
-        (int64_t)npairs * kf->cap >= S3_MAX_SLOTS || corr_cap < (int64_t)npairs * kf->cap || map->npoints < 0 || !d_offsets ||
+    if (!m || !map || nkf < 0 || npairs < 0 || corr_cap < 0 || !kf || kf->cap < 1 || kf->cap > PJ_MAX_NF || !trk_levels_of(level_sigma2, nlevels, &a.sigma2) ||
+        (int64_t)npairs * kf->cap >= TRK_MAX_SLOTS || corr_cap < (int64_t)npairs * kf->cap || map->npoints < 0 || !d_offsets ||
         (npairs > 0 && (!kf->d_kps || !kf->d_n || !d_Tcw || !d_slot_mp || !d_kf1 || !d_kf2 || !d_match12)) ||
         (corr_cap > 0 && (!d_X1 || !d_X2 || !d_sigma2_1 || !d_sigma2_2 || !d_idx1)) || (map->npoints > 0 && (!map->d_world_pos || !map->d_bad))) {
         orbfe_set_error("bad argument to orbfe_sim3_correspondences_device (cap <= %d, nlevels 1..%d, npairs * cap < 2^25, corr_cap >= npairs * cap)", PJ_MAX_NF, TRK_MAX_LEVELS);
@@ -798,7 +764,7 @@ extern "C" orbfe_status orbfe_sim3_correspondences_device(orbfe_matcher *m, cons
 extern "C" orbfe_status orbfe_sim3_keep_inliers_device(orbfe_matcher *m, const uint8_t *d_key_mask, int32_t cap, int32_t npairs,
                                                        int32_t *d_match12, void *stream)
 {
-    if (!m || cap < 1 || npairs < 0 || (int64_t)npairs * cap >= S3_MAX_SLOTS || (npairs > 0 && (!d_key_mask || !d_match12))) {
+    if (!m || cap < 1 || npairs < 0 || (int64_t)npairs * cap >= TRK_MAX_SLOTS || (npairs > 0 && (!d_key_mask || !d_match12))) {
         orbfe_set_error("bad argument to orbfe_sim3_keep_inliers_device (npairs * cap < 2^25)");
         return ORBFE_ERR_ARG;
     }

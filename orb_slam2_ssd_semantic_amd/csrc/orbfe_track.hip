@@ -20,7 +20,6 @@
 
 static_assert(sizeof(orbfe_keypoint) == 7 * sizeof(float) && offsetof(orbfe_keypoint, octave) == 20 && offsetof(orbfe_keypoint, angle) == 12,
               "keypoint record = 7 floats: (x, y) first, angle fourth, octave sixth");
-static_assert(sizeof(TrkCam) == sizeof(orbfe_track_camera), "TrkCam is orbfe_track_camera");
 
 #define TRK_UT 1024              // threads of the unproject / selection workgroup
 
@@ -235,7 +234,7 @@ __global__ __launch_bounds__(256) void k_trk_fill(TrkCoreArgs b)
     if (!trk_query(b, f, i, a, Q, R, src)) return;   // wave-uniform
     const int mine = b.lcnt[g * PJ_LC + sub];
     uint32_t o = b.off[g] + (uint32_t)(wave_incl_scan_m(mine) - mine);
-    const Desc8 dq = proj_load_desc(b.pool + ((int64_t)f * b.pool_frame_rows + src) * 32);
+    const Desc8 dq = load_desc8(b.pool + ((int64_t)f * b.pool_frame_rows + src) * 32);
     // a slot blocks from state 2 on: a MapPoint with observations before the call
     proj_walk(a, Q, R, sub, [&](uint32_t k) {
         const bool skip = proj_gate_skip(a, Q, k, 2, b.has_sigma2 != 0, [&](int lv) { return b.inv_sigma2.v[lv]; });
@@ -354,7 +353,7 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_replay(TrkReplayArgs a)
     __syncthreads();
     auto bin_of = [&](int i, int m) {
         const int src = min(max(a.qsrc[g0 + i], 0), a.cap_last - 1);
-        return min(max(rot_bin(ang_last[(int64_t)src * 7], ang_cur[(int64_t)m * 7]), 0), ORBFE_HISTO_LENGTH - 1);
+        return rot_bin_clamped(ang_last[(int64_t)src * 7], ang_cur[(int64_t)m * 7]);
     };
     int base = 0;
     for (int i0 = 0; i0 < nq; i0 += TRK_GT) {   // workgroup-uniform trip count
@@ -376,14 +375,13 @@ __global__ __launch_bounds__(TRK_GT) void k_trk_replay(TrkReplayArgs a)
     }
     __syncthreads();
     if (a.check_ori) {
-        if (tid == 0) trk_three_maxima(s_hist, s_keep);
+        if (tid == 0) rot_three_maxima(s_hist, ORBFE_HISTO_LENGTH, s_keep);
         __syncthreads();
         int dropped = 0;
         for (int i = tid; i < nq; i += TRK_GT) {
             const int m = a.match[g0 + i];
             if (m < 0 || m >= nF) continue;
-            const int bin = bin_of(i, m);
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+            if (!rot_keeps(s_keep, bin_of(i, m))) {
                 s_last[m] = -2;   // every writer of this phase writes -2; nobody reads before the barrier
                 ++dropped;
             }
@@ -430,26 +428,6 @@ orbfe_status orbfe_internal_track_lists_launch(orbfe_matcher *m, TrkCoreArgs &b,
 
 namespace
 {
-bool frames_ok(const orbfe_track_frames *F, int32_t nframes)
-{
-    return F && F->cap >= 0 && (nframes == 0 || (F->d_kps && F->d_desc && F->d_n && F->d_cell_off && F->d_cell_idx));
-}
-
-bool levels_ok(const float *v, int32_t nlevels, TrkLevels *out)
-{
-    if (!v || nlevels < 1 || nlevels > TRK_MAX_LEVELS) return false;
-    for (int i = 0; i < TRK_MAX_LEVELS; ++i) out->v[i] = i < nlevels ? v[i] : 0.f;
-    return true;
-}
-
-TrkCam cam_of(const orbfe_track_camera *c)
-{
-    TrkCam t;
-    t.fx = c->fx; t.fy = c->fy; t.cx = c->cx; t.cy = c->cy; t.bf = c->bf;
-    t.minx = c->minx; t.maxx = c->maxx; t.miny = c->miny; t.maxy = c->maxy;
-    return t;
-}
-
 // the launches of the search core on `st`: the lists (orbfe_internal_track_lists_launch sizes the scratch blocks), then the rounds
 orbfe_status core_launch(orbfe_matcher *m, const orbfe_track_frames *F, int32_t nframes, const orbfe_proj_query *d_q, const int32_t *d_qsrc,
                          const int32_t *d_nq, int32_t qcap, const uint8_t *d_qpool, int32_t pool_rows, int32_t pool_frame_rows,
@@ -476,13 +454,13 @@ orbfe_status core_launch(orbfe_matcher *m, const orbfe_track_frames *F, int32_t 
 orbfe_status core_check(const char *who, orbfe_matcher *m, const orbfe_track_frames *F, int32_t nframes, int32_t qcap, int32_t th,
                         int64_t ent_cap, const float *inv_level_sigma2, int32_t nlevels)
 {
-    if (!m || nframes < 0 || qcap < 1 || ent_cap < 0 || !frames_ok(F, nframes) || (inv_level_sigma2 && (nlevels < 1 || nlevels > TRK_MAX_LEVELS))) {
+    if (!m || nframes < 0 || qcap < 1 || ent_cap < 0 || !trk_frames_ok(F, nframes, 0) || (inv_level_sigma2 && (nlevels < 1 || nlevels > TRK_MAX_LEVELS))) {
         orbfe_set_error("bad argument to %s", who);
         return ORBFE_ERR_ARG;
     }
     if (F->cap > PJ_MAX_NF) { orbfe_set_error("%s: at most %d features per frame", who, PJ_MAX_NF); return ORBFE_ERR_SIZE; }
     if (th > 255) { orbfe_set_error("%s: th must be below 256 (256 is the 'no candidate' distance)", who); return ORBFE_ERR_ARG; }
-    if ((int64_t)nframes * qcap >= (int64_t)1 << 25 || ent_cap > 0xFFFFFFFFll) {
+    if ((int64_t)nframes * qcap >= TRK_MAX_SLOTS || ent_cap > 0xFFFFFFFFll) {
         orbfe_set_error("%s: nframes * qcap must stay below 2^25 and ent_cap below 2^32", who);
         return ORBFE_ERR_SIZE;
     }
@@ -509,7 +487,7 @@ orbfe_status gate_last_launch(const float *d_Tcw_cur, const orbfe_track_last *L,
 {
     TrkGateLastArgs g;
     g.Tcw_cur = d_Tcw_cur; g.Tcw_last = L->d_Tcw;
-    g.cam = cam_of(cam);
+    g.cam = *cam;
     g.mb = mb; g.th = th; g.mono = mono ? 1 : 0; g.nlevels = nlevels; g.sf = sf;
     g.valid = L->d_valid; g.obs_gt0 = L->d_obs_gt0; g.world_pos = L->d_world_pos;
     g.last_kps = (const float *)L->d_kps;
@@ -532,7 +510,7 @@ orbfe_status gate_map_launch(const float *d_Tcw, const orbfe_track_camera *cam, 
 {
     TrkGateMapArgs g;
     g.Tcw = d_Tcw;
-    g.cam = cam_of(cam);
+    g.cam = *cam;
     g.th = th; g.log_sf = log_scale_factor; g.nlevels = nlevels; g.sf = sf;
     g.map = *map;
     g.list_off = d_list_off; g.list_idx = d_list_idx; g.seen = d_seen; g.nentries = nentries; g.qcap = qcap;
@@ -551,7 +529,7 @@ bool map_ok(const orbfe_track_map *M)
 
 extern "C" int64_t orbfe_track_scratch_bytes(int32_t nframes, int32_t qcap, int64_t ent_cap)
 {
-    if (nframes < 0 || qcap < 1 || ent_cap < 0 || (int64_t)nframes * qcap >= (int64_t)1 << 25 || ent_cap > 0xFFFFFFFFll) return -1;
+    if (nframes < 0 || qcap < 1 || ent_cap < 0 || (int64_t)nframes * qcap >= TRK_MAX_SLOTS || ent_cap > 0xFFFFFFFFll) return -1;
     const size_t ng = (size_t)nframes * (size_t)qcap;
     // counts | per-lane counts | offsets | entries: the blocks core_launch asks the matcher's scratch for
     return (int64_t)(orb_align256(std::max<size_t>(ng * 4, 4)) + orb_align256(std::max<size_t>(ng * PJ_LC * 2, 4)) + orb_align256((ng + 1) * 4) +
@@ -567,7 +545,7 @@ extern "C" orbfe_status orbfe_frustum_points(const float *Tcw, const orbfe_track
         orbfe_set_error("bad argument to orbfe_frustum_points");
         return ORBFE_ERR_ARG;
     }
-    const TrkCam c = cam_of(cam);
+    const TrkCam c = *cam;
     float Ow[3];
     trk_camera_centre(Tcw, Ow);
     for (int i = 0; i < n; ++i) {
@@ -600,7 +578,7 @@ extern "C" orbfe_status orbfe_unproject_select_batch_device(orbfe_matcher *m, co
     DeviceGuard g(m->device);
     TrkUnprojArgs a;
     a.kps = (const float *)d_kps; a.depth = d_depth; a.n = d_n; a.cap = cap; a.Tcw = d_Tcw;
-    a.cam = cam_of(cam);
+    a.cam = *cam;
     a.invfx = 1.0f / cam->fx;   // Frame's invfx / invfy
     a.invfy = 1.0f / cam->fy;
     a.th_depth = th_depth;
@@ -617,7 +595,7 @@ extern "C" orbfe_status orbfe_gate_last_frame_batch_device(orbfe_matcher *m, con
                                                            void *stream)
 {
     TrkLevels sf;
-    if (!m || !cam || nframes < 0 || qcap < 1 || !last_ok(last, nframes) || !levels_ok(scale_factors, nlevels, &sf) ||
+    if (!m || !cam || nframes < 0 || qcap < 1 || !last_ok(last, nframes) || !trk_levels_of(scale_factors, nlevels, &sf) ||
         (nframes > 0 && (!d_Tcw_cur || !d_q || !d_qsrc || !d_nq))) {
         orbfe_set_error("bad argument to orbfe_gate_last_frame_batch_device");
         return ORBFE_ERR_ARG;
@@ -636,7 +614,7 @@ extern "C" orbfe_status orbfe_gate_local_map_batch_device(orbfe_matcher *m, cons
 {
     TrkLevels sf;
     if (!m || !cam || nframes < 0 || qcap < 1 || nentries < 0 || nentries > 0x7FFFFFFFll || !map_ok(map) ||
-        !levels_ok(scale_factors, nlevels, &sf) || (nframes > 0 && (!d_Tcw || !d_list_off || !d_q || !d_qsrc || !d_nq)) ||
+        !trk_levels_of(scale_factors, nlevels, &sf) || (nframes > 0 && (!d_Tcw || !d_list_off || !d_q || !d_qsrc || !d_nq)) ||
         (nentries > 0 && !d_list_idx)) {
         orbfe_set_error("bad argument to orbfe_gate_local_map_batch_device");
         return ORBFE_ERR_ARG;
@@ -706,7 +684,7 @@ extern "C" orbfe_status orbfe_track_last_frame_batch_device(orbfe_matcher *m, co
                                                             const orbfe_track_out *out, void *stream)
 {
     TrkLevels sf;
-    if (!out_ok(out, nframes) || !cam || !last_ok(last, nframes) || !levels_ok(scale_factors, nlevels, &sf) || (nframes > 0 && (!d_Tcw_cur || !last->d_mpdesc))) {
+    if (!out_ok(out, nframes) || !cam || !last_ok(last, nframes) || !trk_levels_of(scale_factors, nlevels, &sf) || (nframes > 0 && (!d_Tcw_cur || !last->d_mpdesc))) {
         orbfe_set_error("bad argument to orbfe_track_last_frame_batch_device");
         return ORBFE_ERR_ARG;
     }
@@ -738,7 +716,7 @@ extern "C" orbfe_status orbfe_track_local_map_batch_device(orbfe_matcher *m, con
                                                            orbfe_track_proj *d_proj, void *stream)
 {
     TrkLevels sf;
-    if (!out_ok(out, nframes) || !cam || !map_ok(map) || nentries < 0 || nentries > 0x7FFFFFFFll || !levels_ok(scale_factors, nlevels, &sf) ||
+    if (!out_ok(out, nframes) || !cam || !map_ok(map) || nentries < 0 || nentries > 0x7FFFFFFFll || !trk_levels_of(scale_factors, nlevels, &sf) ||
         (nframes > 0 && (!d_Tcw || !d_list_off || (map->npoints > 0 && !map->d_desc))) || (nentries > 0 && !d_list_idx)) {
         orbfe_set_error("bad argument to orbfe_track_local_map_batch_device");
         return ORBFE_ERR_ARG;

@@ -1,8 +1,13 @@
-// orbfe_track_dev.h -- what the batched, device-resident searches share: the argument block of the search core with a frame
-// dimension (TrkCoreArgs), a frame's view of it (trk_frame_args, trk_query), the order-preserving compaction of the gating
-// kernels (trk_compact_pos) and the one launch site of the core's count -> scan -> fill.  For orbfe_track.hip (the tracker's two
-// SearchByProjection calls) and orbfe_init_search.hip (SearchForInitialization), which differ in their gating and in their
-// acceptance rule, not in how the candidate lists are made.
+// orbfe_track_dev.h -- what the batched, device-resident searches share.  Device side: the order-preserving compaction of the
+// gating and replay kernels (trk_compact_pos), a row of an orbfe_track_frames block as the walk's ProjArgs (proj_frame_view), the
+// argument block of the search core with a frame dimension (TrkCoreArgs) with its view of a frame (trk_frame_args, trk_query)
+// and the one launch site of the core's count -> scan -> fill.  The slot limit of a call (TRK_MAX_SLOTS) stands with the other
+// limits at the top; host side, at the end: the level tables (trk_levels_of) and the frame-block check (trk_frames_ok).  The rotation histogram's rules are
+// orbfe_match_dev.h's (rot_bin_clamped, rot_three_maxima, rot_keeps); the camera block is orbfe_track_geom.h's TrkCam.
+// For orbfe_track.hip (the tracker's two SearchByProjection calls) and orbfe_init_search.hip (SearchForInitialization), which
+// share the core and differ in their gating and acceptance rule; for orbfe_fuse.hip and orbfe_sim3_search.hip, which take the
+// frame view, the compaction and the host checks; for orbfe_tri_search.hip and orbfe_newpoints.hip, which take the compaction
+// and the slot limit.
 #pragma once
 
 #include "orbfe_common.h"
@@ -11,6 +16,9 @@
 
 #define TRK_MAX_LEVELS 16        // orbfe_params.nlevels is 1..16: the per-level tables travel in the kernel arguments
 #define TRK_GT 256               // threads of the gating and replay workgroups
+// what one call may address -- frames x queries, pairs x features, list entries: every device-resident search refuses more, and
+// every message that names the limit says 2^25
+#define TRK_MAX_SLOTS ((int64_t)1 << 25)
 
 struct TrkLevels {
     float v[TRK_MAX_LEVELS];
@@ -39,26 +47,25 @@ __device__ __forceinline__ int trk_compact_pos(bool ok, int *s_wave /* [TRK_GT /
     return base + prefix;
 }
 
-// ComputeThreeMaxima (src/ORBmatcher.cc:1912-1957) over the 30 bins of a rotation histogram: keep[0..2] = the bins that stay, -1
-// where the second / third is under a tenth of the first.  One thread calls it.
-__device__ __forceinline__ void trk_three_maxima(const int *hist, int *keep)
+// Row `row` of a block of frames as the walk sees it: every field of ProjArgs that the block alone decides.  No slot blocks, no
+// right-image gate and no chi2 table until the form sets them (trk_frame_args, fuse_frame_args, s3_frame_args), with its
+// nlevels, th, ratio_rule and nnratio.
+__device__ __forceinline__ ProjArgs proj_frame_view(const orbfe_track_frames &F, int row)
 {
-    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int i = 0; i < ORBFE_HISTO_LENGTH; ++i) {
-        const int s = hist[i];
-        if (s > max1) {
-            max3 = max2; max2 = max1; max1 = s;
-            i3 = i2; i2 = i1; i1 = i;
-        } else if (s > max2) {
-            max3 = max2; max2 = s;
-            i3 = i2; i2 = i;
-        } else if (s > max3) {
-            max3 = s; i3 = i;
-        }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
-    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
-    keep[0] = i1; keep[1] = i2; keep[2] = i3;
+    ProjArgs a;
+    const int64_t fb = (int64_t)row * F.cap;
+    a.descF = F.d_desc + fb * 32;
+    a.xyF = (const float *)F.d_kps + fb * 7;
+    a.octF = (const int32_t *)F.d_kps + fb * 7 + 5;
+    a.nF = min(max(F.d_n[row], 0), F.cap);
+    a.xs = 7; a.os = 7;
+    a.cell_off = F.d_cell_off + (int64_t)row * (GRID_NC + 1);
+    a.cell_idx = F.d_cell_idx + fb;
+    a.minx = F.minx; a.miny = F.miny; a.gwi = F.gw_inv; a.ghi = F.gh_inv;
+    a.uRight = nullptr;
+    a.blocked = nullptr;
+    a.inv_sigma2 = nullptr;
+    return a;
 }
 
 // The search core with a frame dimension.  Global query g = f * qcap + i; lanes of queries beyond nq[f] count zero
@@ -90,18 +97,10 @@ struct TrkCoreArgs {
 // the walk's view of frame f
 __device__ __forceinline__ ProjArgs trk_frame_args(const TrkCoreArgs &b, int f)
 {
-    ProjArgs a;
+    ProjArgs a = proj_frame_view(b.F, f);
     const int64_t fb = (int64_t)f * b.F.cap;
-    a.descF = b.F.d_desc + fb * 32;
-    a.xyF = (const float *)b.F.d_kps + fb * 7;
-    a.octF = (const int32_t *)b.F.d_kps + fb * 7 + 5;
-    a.nF = min(max(b.F.d_n[f], 0), b.F.cap);
-    a.xs = 7; a.os = 7;
-    a.cell_off = b.F.d_cell_off + (int64_t)f * (GRID_NC + 1);
-    a.cell_idx = b.F.d_cell_idx + fb;
-    a.minx = b.F.minx; a.miny = b.F.miny; a.gwi = b.F.gw_inv; a.ghi = b.F.gh_inv;
-    a.uRight = b.F.d_uright ? b.F.d_uright + fb : nullptr;
-    a.blocked = b.F.d_slot ? b.F.d_slot + fb : nullptr;
+    if (b.F.d_uright) a.uRight = b.F.d_uright + fb;
+    if (b.F.d_slot) a.blocked = b.F.d_slot + fb;
     a.nlevels = b.nlevels;
     a.th = b.th; a.ratio_rule = b.ratio_rule; a.nnratio = b.nnratio;
     return a;
@@ -123,3 +122,21 @@ __device__ __forceinline__ bool trk_query(const TrkCoreArgs &b, int f, int i, co
 // b.status[0..1] are zeroed by the count.  The caller's acceptance kernel runs behind it on the same stream.
 __attribute__((visibility("hidden"))) orbfe_status orbfe_internal_track_lists_launch(orbfe_matcher *m, TrkCoreArgs &b, int64_t ent_cap,
                                                                                      hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------
+// host side: the refusals and conversions the entry points of these searches share
+// ---------------------------------------------------------------------------------------------------
+// a per-level table of the caller (nlevels 1..TRK_MAX_LEVELS entries) as the kernel-argument array, zero behind nlevels
+inline bool trk_levels_of(const float *v, int32_t nlevels, TrkLevels *out)
+{
+    if (!v || nlevels < 1 || nlevels > TRK_MAX_LEVELS) return false;
+    for (int i = 0; i < TRK_MAX_LEVELS; ++i) out->v[i] = i < nlevels ? v[i] : 0.f;
+    return true;
+}
+
+// a block of frames with its required pointers; min_cap is the form's: 0 for the tracker and Fuse (an empty block is a no-op), 1
+// for the Sim3 searches
+inline bool trk_frames_ok(const orbfe_track_frames *F, int32_t nframes, int32_t min_cap)
+{
+    return F && F->cap >= min_cap && (nframes == 0 || (F->d_kps && F->d_desc && F->d_n && F->d_cell_off && F->d_cell_idx));
+}

@@ -21,10 +21,7 @@
 
 #include "orbfe.h"
 
-struct TrkCam {
-    float fx, fy, cx, cy, bf;
-    float minx, maxx, miny, maxy;   // Frame::mnMinX .. mnMaxY
-};
+using TrkCam = orbfe_track_camera;   // fx, fy, cx, cy, bf, then Frame::mnMinX .. mnMaxY as minx, maxx, miny, maxy
 
 __host__ __device__ inline float trk_div(float a, float b)
 {

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(TRI_T) void k_tri_search(TriBatchArgs a)
             TriLine line;
             bool st1 = false;
             if (qok) {
-                d1 = proj_load_desc(F1.desc + (int64_t)f1 * 32);
+                d1 = load_desc8(F1.desc + (int64_t)f1 * 32);
                 st1 = tri_stereo(F1, (int)f1);
                 line = tri_line(F1.kps[(int64_t)f1 * 7], F1.kps[(int64_t)f1 * 7 + 1], F);
             }
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(TRI_T) void k_tri_search_flat(TriBatchArgs a)
     if (!tri_pair(a, p, F1, F2) || f1 >= F1.n) return;
     const int lo = a.range[((int64_t)p * cap + f1) * 2], hi = a.range[((int64_t)p * cap + f1) * 2 + 1];
     if (hi <= lo || !tri_elig(a, F1, f1)) return;
-    const Desc8 d1 = proj_load_desc(F1.desc + (int64_t)f1 * 32);
+    const Desc8 d1 = load_desc8(F1.desc + (int64_t)f1 * 32);
     const bool st1 = tri_stereo(F1, f1);
     float F[9];
 #pragma unroll
@@ -312,9 +312,7 @@ __global__ __launch_bounds__(TRI_T) void k_tri_replay(TriBatchArgs a)
     const bool live = tri_pair(a, p, F1, F2);   // workgroup-uniform
     const int n1 = live ? F1.n : 0, n2 = live ? F2.n : 0;
     int32_t *match12 = a.O.d_match12 + (int64_t)p * cap;
-    auto bin_of = [&](int i, int m) {
-        return min(max(rot_bin(F1.kps[(int64_t)i * 7 + 3], F2.kps[(int64_t)m * 7 + 3]), 0), ORBFE_HISTO_LENGTH - 1);
-    };
+    auto bin_of = [&](int i, int m) { return rot_bin_clamped(F1.kps[(int64_t)i * 7 + 3], F2.kps[(int64_t)m * 7 + 3]); };
     if (a.check_ori) {
         if (tid < ORBFE_HISTO_LENGTH) s_hist[tid] = 0;
         __syncthreads();
@@ -323,7 +321,7 @@ __global__ __launch_bounds__(TRI_T) void k_tri_replay(TriBatchArgs a)
             if (m >= 0 && m < n2) atomicAdd(&s_hist[bin_of(i, m)], 1);
         }
         __syncthreads();
-        if (tid == 0) trk_three_maxima(s_hist, s_keep);
+        if (tid == 0) rot_three_maxima(s_hist, ORBFE_HISTO_LENGTH, s_keep);
         __syncthreads();
     }
     int base = 0;
@@ -331,10 +329,7 @@ __global__ __launch_bounds__(TRI_T) void k_tri_replay(TriBatchArgs a)
         const int i = i0 + tid;
         int m = i < n1 ? match12[i] : -1;
         if (m >= n2) m = -1;
-        if (m >= 0 && a.check_ori) {
-            const int bin = bin_of(i, m);
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) m = -1;
-        }
+        if (m >= 0 && a.check_ori && !rot_keeps(s_keep, bin_of(i, m))) m = -1;
         if (i < cap) match12[i] = m;
         int tot;
         const int pos = base + trk_compact_pos(m >= 0, s_wave, &tot);
@@ -355,7 +350,7 @@ __global__ __launch_bounds__(TRI_T) void k_tri_replay(TriBatchArgs a)
 // ---------------------------------------------------------------------------------------------------
 namespace
 {
-bool tri_limits_ok(int64_t npairs, int64_t cap) { return npairs >= 0 && cap >= 1 && cap <= TRI_MAX_CAP && npairs * cap < ((int64_t)1 << 25); }
+bool tri_limits_ok(int64_t npairs, int64_t cap) { return npairs >= 0 && cap >= 1 && cap <= TRI_MAX_CAP && npairs * cap < TRK_MAX_SLOTS; }
 size_t tri_range_bytes(int32_t npairs, int32_t cap) { return orb_align256(std::max<size_t>((size_t)npairs * (size_t)cap * 8, 4)); }
 }  // namespace
 

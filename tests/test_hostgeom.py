@@ -10,6 +10,7 @@ import pytest
 
 from orb_slam2_ssd_semantic_amd import _ffi
 from orb_slam2_ssd_semantic_amd._ffi import ptr
+from rotation_cases import ROTATION_CASES, ROTATION_KEPT, _rotation_groups
 
 F32 = np.float32
 PJ_NEG_DEPTH, PJ_NEG_INVZ, PJ_CHAINED, PJ_CLOSED = 1, 2, 4, 8
@@ -170,6 +171,21 @@ def test_rotation_consistency_equals_bins_plus_three_maxima(oracle):
         counts = np.bincount(bins, minlength=30)[:30]
         keep = set(int(i) for i in oracle.three_maxima(counts) if i >= 0)
         assert np.array_equal(drop[:n].astype(bool), np.array([bb not in keep for bb in bins], bool)), case
+
+
+@pytest.mark.parametrize("name", list(ROTATION_CASES))
+def test_rotation_consistency_at_the_prune_kernels_edges(oracle, name):
+    """orbfe_rotation_consistency runs the three-maxima and keep test the prune kernels call (rot_three_maxima, rot_keeps): the
+    cases of the kernels' table -- exact half-bin rotations, the binary32 0.1f * max1 boundary, equal counts -- on the CPU."""
+    L = _ffi.lib()
+    a, b = _rotation_groups(ROTATION_CASES[name])
+    n = len(a)
+    drop = np.full(n, 7, np.uint8)
+    assert L.orbfe_rotation_consistency(ptr(a), ptr(b), n, 30, ptr(drop)) == 0
+    bins = np.array([oracle.rot_bin(float(x), float(y)) for x, y in zip(a, b)], np.int64)
+    keep = [int(i) for i in oracle.three_maxima(np.bincount(bins, minlength=30)[:30]) if i >= 0]
+    assert np.array_equal(drop, (~np.isin(bins, keep)).astype(np.uint8))
+    assert n - int(drop.sum()) == ROTATION_KEPT[name]
 
 
 def test_rotation_consistency_rejects_bins_outside_the_histogram():
